@@ -11,14 +11,16 @@ k = 128, 7 power iterations (the crate's default, src/pca.rs:679-680), its rows 
 The only data-path exchange is the all-reduce of the small replicated matrices (RCCL); the record carries
 `allreduce_calls`, `allreduce_bytes` and the stream time spent in them per fit.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with an extra object:
   roofline      the dominant power-iteration GEMM kernel: algorithmic bytes (default split-product mode: the kernel
                 is paced by the X stream, bound "hbm") or flops (--gemm fp32: bound "mfma") per launch / average
                 launch duration measured with HIP events on the launch stream inside the timed region
-  cpu_baseline  the numpy/LAPACK oracle ("port") timed on this box's host cores on the same workload
-and informational ones (fp32_mfma_mode: the same fit on the fp32-MFMA kernels; northstar_gemm: the two GEMM kernels
-alone at 1e6 x 512 in both modes; fastica_cfg3; pca_cfg1: the exact Pca on configs[0]; host_in: fit() fed a host ndarray, PCIe
-included -- never `value`).
+A plain run does only what that line needs: set-up, clock ramp, warm-up, the timed steps.  --full adds what takes runs of
+its own: cpu_baseline (the numpy/LAPACK oracle, "port", timed on this box's host cores on the same workload) and informational
+objects (serial_chain / predicted_scaling; fp32_mfma_mode: the same fit on the fp32-MFMA kernels; exact_mode; redo_case;
+northstar_gemm: the two GEMM kernels alone at 1e6 x 512 in both modes; fastica_cfg3; pca_cfg1: the exact Pca on configs[0]; host_in:
+fit() fed a host ndarray, PCIe included; one_gpu_same_matrix at N > 1 -- never `value`).
+--dump-outputs DIR writes what the last timed step returned to its caller (components, singular values, ...) as DIR/<name>.npy.
 """
 import argparse
 import datetime
@@ -157,6 +159,12 @@ def main():
                     help="seconds of untimed fits in front of the warm-up steps (brings the GPU clocks up after the host-side data generation)")
     ap.add_argument("--no-strong-baseline", action="store_true",
                     help="cfg4s at N > 1: skip the single-GPU fit of the whole matrix that rank 0 times after the sharded run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own beside the timed steps: CPU baseline, other modes / sizes / configurations, "
+                         "serial-chain breakdown, the one-GPU fit of the same matrix at N > 1 (--no-cpu-baseline / --no-northstar / "
+                         "--no-strong-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.config is None:
         args.config = default_config(args.gpus)
@@ -294,6 +302,9 @@ def main():
         t = torch.tensor([elapsed], device="cpu" if args.share_gpu else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:   # (before any --full extra refits the model)
+        dump_outputs(args.dump_outputs, {"components": model.components(), "singular_values": model.singular_values(),
+                                         "mean": model.mean(), "explained_variance_ratio": model.explained_variance_ratio()})
 
     # every rank's own view of the collective (gathered: a SCALE line can then show N distinct devices inside ONE communicator)
     me = {"rank": rank, **ctx.collective_info()}
@@ -312,7 +323,7 @@ def main():
 
     # (the chain's extra fits are SHARDED fits where world > 1 -- a weak-scaling run, `--config cfg2 / cfg4 --gpus N`: every rank has to run
     # them, not rank 0 alone beside ranks already waiting at the last barrier; round 6)
-    chain = serial_chain(ctx, model, x, omega, elapsed / args.steps * 1e3) if (not strong or world == 1) else None
+    chain = serial_chain(ctx, model, x, omega, elapsed / args.steps * 1e3) if args.full and (not strong or world == 1) else None
     out = None
     if rank == 0:
         # dominant kernel = the power-iteration GEMM kind with the larger summed time
@@ -367,7 +378,7 @@ def main():
             out["serial_chain"] = chain
             if cfg["model"] == "rpca" and world == 1:
                 out["predicted_scaling"] = predicted_scaling(out["ms_per_step"], out["serial_chain"], n_iter, d, l, strong)
-        if world == 1 and x_host is not None:
+        if args.full and world == 1 and x_host is not None:
             # host-ndarray-in rate (H2D over PCIe included) -- informational, never `value`
             model.fit(x_host, omega=omega)
             t1 = time.perf_counter()
@@ -380,30 +391,30 @@ def main():
                               "note": "fit() fed a pageable host ndarray: PCIe H2D inside the timed region; the copy lands with a "
                                       "padded device row pitch when the natural one is a multiple of 1 KiB (memory-channel spread)"}
 
-        if world == 1 and not strong and not args.no_northstar:
+        if args.full and world == 1 and not strong and not args.no_northstar:
             out["x_padded_pitch"] = padded_pitch_extra(petal, ctx, torch, model, x, omega)
 
-        if world == 1 and args.gemm == "bf16x3" and not args.no_northstar:
+        if args.full and world == 1 and args.gemm == "bf16x3" and not args.no_northstar:
             out["fp32_mfma_mode"] = fp32_mode_extra(petal, ctx, model, x, omega)
             # the two figures that price the optimism of `value`: the same fit with three-plane operands in every pass
             # (no steering passes, no verdict), and a fit whose spectrum the verdict refuses -- the caller then pays for two runs
             out["exact_mode"] = exact_mode_extra(petal, ctx, model, x, omega)
             out["redo_case"] = redo_case_extra(petal, ctx, torch, dev, n, d, k, n_iter)
 
-        if world == 1 and not args.no_northstar and not strong:
+        if args.full and world == 1 and not args.no_northstar and not strong:
             del x
             torch.cuda.empty_cache()
             out["northstar_gemm"] = northstar(petal, ctx, torch, dev)
             ctx.set_gemm_mode(args.gemm)
             out["northstar_fit"] = northstar_fit(petal, ctx, torch, dev, args.gemm)
 
-        if world == 1 and not args.no_northstar and not strong:
+        if args.full and world == 1 and not args.no_northstar and not strong:
             out["fastica_cfg3"] = fastica_cfg3(petal, ctx, torch, dev)
             out["pca_cfg1"] = pca_cfg1(petal, ctx, torch, dev)
 
-        if world == 1 and not args.no_cpu_baseline and x_host is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and x_host is not None:
             out["cpu_baseline"] = cpu_baseline(x_host, omega, k, n_iter)
-    if strong and world > 1 and not args.no_strong_baseline:
+    if args.full and strong and world > 1 and not args.no_strong_baseline:
         # the same matrix on ONE GPU, timed by rank 0 alone after the sharded run (the other ranks wait at the barrier below):
         # the denominator of the strong-scaling ratio, measured in the same job on the same box
         del x
@@ -419,12 +430,27 @@ def main():
                 out["one_gpu_same_matrix"] = {"error": repr(e)}
                 out["speedup_vs_one_gpu_same_matrix"] = None
     if rank == 0 and out is not None and world > 1 and "speedup_vs_one_gpu_same_matrix" not in out:
-        out["speedup_vs_one_gpu_same_matrix"] = None   # (weak-scaling configs / --no-strong-baseline: no same-matrix one-GPU fit in this job)
+        out["speedup_vs_one_gpu_same_matrix"] = None   # (weak-scaling configs / no --full / --no-strong-baseline: no same-matrix one-GPU fit in this job)
     if rank == 0:
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays, max_bytes=64 << 20):
+    """--dump-outputs: one out_dir/<name>.npy per array, float32 / float64 as the fit returned it (anything else as float64).  An array
+    past its share of max_bytes is replaced by a fixed, seeded sample of its elements (flattened, ascending index order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = max_bytes // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def ramp(fn, seconds=0.25, dist=None, torch=None, dev=None):
@@ -866,6 +892,8 @@ def bench_fastica(args, cfg, petal, ctx, torch, dist, dev, rank, world, collecti
         t = torch.tensor([elapsed], device="cpu" if args.share_gpu else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"components": m.components, "means": m.means, "n_iter": np.array([m.n_iter], dtype=np.float64)})
     avg = step_ms / max(step_cnt, 1)
     tf = st["ica_step_flops"] / (avg * 1e-3) / 1e12 if avg > 0 else 0.0
     if args.gemm == "fp32":

@@ -6,21 +6,25 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "roofline"]
+# what only `--full` measures (runs of its own beside the timed steps)
+FULL_ONLY = ["cpu_baseline", "serial_chain", "predicted_scaling", "host_in", "x_padded_pitch", "fp32_mfma_mode", "exact_mode", "redo_case",
+             "northstar_gemm", "northstar_fit", "fastica_cfg3", "pca_cfg1", "one_gpu_same_matrix"]
 
 
-def _run(*extra, launcher_env=True, n_gpus=1):
+def _run(*extra, launcher_env=True, n_gpus=1, steps=3):
     env = dict(os.environ)
     if launcher_env:
         env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29577", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     else:  # as the driver runs it at N = 1 / as a user runs `python bench.py --gpus N`: no launcher variables at all
         for key in ("MASTER_ADDR", "MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
             env.pop(key, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-northstar", *extra],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no-northstar", *extra],
                          capture_output=True, text=True, timeout=420, env=env, cwd=ROOT)   # (a run takes 10 - 60 s)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.split("\n") if ln.strip()]
@@ -28,7 +32,7 @@ def _run(*extra, launcher_env=True, n_gpus=1):
     rec = json.loads(lines[0])
     for key in REQUIRED:
         assert key in rec, key
-    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == n_gpus
+    assert rec["steps"] == steps and rec["warmup"] == 1 and rec["n_gpus"] == n_gpus
     assert rec["value"] > 0 and rec["higher_is_better"] is True and rec["vs_baseline"] is None
     assert set(["bound", "achieved", "peak", "unit", "frac", "traffic"]) <= set(rec["roofline"])
     assert abs(rec["roofline"]["frac"] - rec["roofline"]["achieved"] / rec["roofline"]["peak"]) < 1e-3
@@ -123,7 +127,7 @@ def test_help_runs_without_a_gpu():
 
 @pytest.mark.gpu
 def test_single_gpu_record():
-    rec = _run()
+    rec = _run("--full")
     cb = rec["cpu_baseline"]
     assert set(["value", "unit", "cores", "kind", "sample"]) <= set(cb) and cb["kind"] in ("port", "reference") and cb["value"] > 0
     assert rec["config"]["collective"] == "none"
@@ -165,8 +169,11 @@ def test_self_launch_single_gpu_without_launcher_variables():
 @pytest.mark.parametrize("config", ["cfg2", "cfg5"])
 def test_weak_scaling_line_with_two_ranks_sharing_the_gpu(config):
     """`--config cfg2 / cfg5 --gpus 2`: per-GPU workloads (weak scaling).  The replicated-chain measurement behind `serial_chain` is a few more
-    SHARDED fits: until round 6 rank 0 ran them alone, beside ranks already waiting at the last barrier -- a hung job."""
-    rec = _run("--config", config, "--gpus", "2", "--share-gpu", "--no-cpu-baseline", launcher_env=False, n_gpus=2)
+    SHARDED fits: until round 6 rank 0 ran them alone, beside ranks already waiting at the last barrier -- a hung job.
+    serial_chain_ms is time per fit minus the medians of the bracketed kernels and all-reduce waits, which on two ranks time-sharing one
+    GPU swing by a millisecond from run to run: a time per fit averaged over 3 fits (3.2 - 5.2 ms between runs) made it negative in
+    one of seven runs, so the time per fit here is averaged over 30."""
+    rec = _run("--config", config, "--gpus", "2", "--share-gpu", "--no-cpu-baseline", "--full", launcher_env=False, n_gpus=2, steps=30)
     assert rec["scaling"] == "weak" and rec["config"]["parallelism"] == "sample-sharded x2" and "speedup_vs_one_gpu_same_matrix" in rec
     if config == "cfg2":
         assert rec["serial_chain"]["serial_chain_ms"] > 0 and rec["collective"]["allreduce_calls_per_fit"] == 5 + 3
@@ -176,7 +183,7 @@ def test_weak_scaling_line_with_two_ranks_sharing_the_gpu(config):
 def test_self_launch_two_ranks_sharing_the_gpu():
     """The launcher path end to end with N = 2 on the one-GPU box: bench.py starts two rank processes itself (fresh children,
     before any GPU call), they share GPU 0 and all-reduce over gloo; rank 0 prints the one record with n_gpus = 2."""
-    rec = _run("--gpus", "2", "--share-gpu", "--no-cpu-baseline", launcher_env=False, n_gpus=2)
+    rec = _run("--gpus", "2", "--share-gpu", "--no-cpu-baseline", "--full", launcher_env=False, n_gpus=2)
     assert "SHARE GPU 0" in rec["config"]["collective"] and rec["config"]["parallelism"] == "sample-sharded x2"
     # no --config at N = 2: configs[3] split two ways, strong scaling, total samples per second
     assert rec["scaling"] == "strong" and rec["config"]["rows_per_gpu"] == 1000000 and rec["config"]["rows_total"] == 2000000
@@ -190,7 +197,7 @@ def test_self_launch_two_ranks_sharing_the_gpu():
 @pytest.mark.gpu
 def test_single_gpu_record_has_the_northstar_fit():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=420, env=env, cwd=ROOT)   # (a run takes 10 - 60 s)
     assert res.returncode == 0, res.stderr[-2000:]
     rec = json.loads(res.stdout.strip().split("\n")[-1])
@@ -202,3 +209,48 @@ def test_single_gpu_record_has_the_northstar_fit():
     assert rec["fused_pass"]["launches_per_fit"] == 6 and rec["roofline"]["kernel"].startswith("K3")
     assert rec["serial_chain"]["serial_chain_ms"] > 0
     assert rec["host_in"]["row_pitch_bytes"] == 2048 + 128
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path):
+    """--dump-outputs: one <name>.npy per array in float32 / float64; an array past its share of the byte budget is replaced by a fixed,
+    seeded sample of its elements -- the same elements in every run, so two builds compare output for output."""
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {"components": np.arange(12, dtype=np.float32).reshape(3, 4), "singular": np.ones(3), "n_iter": np.array([7]),
+              "big": np.arange(4096, dtype=np.float64)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, max_bytes=4 * 8192)
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "components.npy", "n_iter.npy", "singular.npy"]
+    c = np.load(tmp_path / "a" / "components.npy")
+    assert c.dtype == np.float32 and np.array_equal(c, arrays["components"])
+    n_iter = np.load(tmp_path / "a" / "n_iter.npy")
+    assert n_iter.dtype == np.float64 and n_iter.tolist() == [7.0]
+    big = np.load(tmp_path / "a" / "big.npy")
+    assert big.dtype == np.float64 and big.size == 8192 // 8 and np.all(np.diff(big) > 0)   # a sorted sample of the elements
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_timed_outputs(tmp_path):
+    """A plain run (no --full) carries only what its timed steps measured; --dump-outputs writes the outputs of the last timed fit.  With the
+    same arguments the inputs are the same from run to run, so the outputs are too, whatever the number of steps."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    names = ["components", "explained_variance_ratio", "mean", "singular_values"]
+    dumps = []
+    for steps in (2, 3):
+        out = tmp_path / f"steps{steps}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                              "--dump-outputs", str(out)], capture_output=True, text=True, timeout=420, env=env, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.split("\n") if ln.strip()]
+        assert len(lines) == 1, res.stdout[:500]
+        rec = json.loads(lines[0])
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0 and rec["value"] > 0 and "roofline" in rec
+        assert not [key for key in FULL_ONLY if key in rec], [key for key in FULL_ONLY if key in rec]
+        assert sorted(os.listdir(out)) == [f"{name}.npy" for name in names]
+        dumps.append({name: np.load(out / f"{name}.npy") for name in names})
+    c = dumps[0]["components"]
+    assert c.shape == (64, 512) and c.dtype in (np.float32, np.float64) and np.all(np.isfinite(c))
+    assert dumps[0]["singular_values"].shape == (64,) and dumps[0]["mean"].shape == (512,)
+    for name in names:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
