@@ -222,7 +222,7 @@ bool op_gram_split(Dev* d, const void* X, int64_t n, int64_t dd, int64_t dp, int
     return true;
 }
 void op_flip_key(Dev*, const double* t, double* key, int64_t L, const int* flag) {
-    if (flag) key[L] = flag[0] != 0 ? 3.0 : (flag[1] != 0 ? 1.0 : (flag[2] != 0 ? 2.0 : 0.0));
+    if (flag) key[L] = verdict_code(flag);
     for (int64_t j = 0; j < L; ++j) {
         uint64_t bits = 0;
         const double a = t[j] < 0 ? 0.0 : t[j];

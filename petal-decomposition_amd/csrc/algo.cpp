@@ -118,19 +118,20 @@ std::vector<double> signs_from_triple(const std::vector<double>& h, int64_t L) {
     for (int64_t j = 0; j < L; ++j) sg[j] = h[2 * L + j] < 0 ? -1.0 : 1.0;
     return sg;
 }
-// `deferred` given (single rank, or sharded fp32): the decision data is only QUEUED for the host (no sync here); the
-// caller decodes it with signs_from_triple() after its own dev_sync, so a fit ends with one synchronisation.
 // `slot` (device, 4 L doubles): the decision data is only WRITTEN there -- [absmax | row | sign] in the first 3 L, the
 // all-reduced keys of the sharded fp32 form in the last L -- for a caller that ships it to the host with its other results
 // (flip_slot_keys() says which part to decode with signs_from_triple()).  Not for sharded fp64 (three dependent rounds).
 bool flip_slot_keys(const petal_ctx& c, int dtype) { return sharded(c) && dtype == F32; }
-// scanned = true: the product kernel already left the (max, row, sign) triple in the slot (op_gemm_xp_prod_absmax)
+// svd_flip's signs from such a slot after it came back to the host (L columns)
+std::vector<double> signs_from_slot(const petal_ctx& c, int dtype, const double* slot, int64_t L) {
+    return flip_slot_keys(c, dtype) ? signs_from_triple(std::vector<double>(slot + 3 * L, slot + 4 * L), L)
+                                    : signs_from_triple(std::vector<double>(slot, slot + 3 * L), L);
+}
+// (the product kernel has left the (max, row, sign) triple in the slot: op_gemm_xp_prod_absmax, op_gemm_xp_absmax)
 // `verdict` (sharded fp32 only; device int): slot[4 L] = (*verdict != 0) rides the same MAX all-reduce, so every rank reads the
 // AGREED redo decision (a rank that branched on its own copy of a replicated flag could leave the others waiting in a collective).
-void flip_signs_to_slot(petal_ctx& c, int dtype, const void* U, int64_t n, int64_t L, int64_t ldu, int64_t row_offset, double* slot,
-                        bool scanned = false, const int* verdict = nullptr) {
+void flip_signs_to_slot(petal_ctx& c, int dtype, int64_t L, double* slot, const int* verdict = nullptr) {
     if (L == 0 && !(verdict && flip_slot_keys(c, dtype))) return;
-    if (!scanned && L > 0) op_col_absmax(c.dev, dtype, U, n, L, ldu, row_offset, slot, slot + L, slot + 2 * L);
     if (flip_slot_keys(c, dtype)) {
         op_flip_key(c.dev, slot, slot + 3 * L, L, verdict);
         allreduce_f64(c, slot + 3 * L, L + (verdict ? 1 : 0), PETAL_MAX);
@@ -151,18 +152,12 @@ double agree_max(petal_ctx& c, double local) {
     return v;
 }
 bool agree_any(petal_ctx& c, bool local) { return agree_max(c, local ? 1.0 : 0.0) != 0.0; }
-std::vector<double> flip_signs(petal_ctx& c, int dtype, const void* U, int64_t n, int64_t L, int64_t ldu,
-                               int64_t row_offset, std::vector<double>* deferred = nullptr) {
+std::vector<double> flip_signs(petal_ctx& c, int dtype, const void* U, int64_t n, int64_t L, int64_t ldu, int64_t row_offset) {
     std::vector<double> h(3 * L), sg(L, 1.0);
-    if (L == 0) { if (deferred) deferred->assign(3 * L, 0.0); return sg; }
+    if (L == 0) return sg;
     DBuf r(c.dev, sizeof(double) * 3 * L);
     op_col_absmax(c.dev, dtype, U, n, L, ldu, row_offset, r.f64(), r.f64() + L, r.f64() + 2 * L);
     if (!sharded(c)) {
-        if (deferred) {
-            deferred->assign(3 * L, 0.0);
-            dev_d2h(c.dev, deferred->data(), r.p, r.bytes);
-            return sg;
-        }
         dev_d2h(c.dev, h.data(), r.p, r.bytes);
         dev_sync(c.dev);
         return signs_from_triple(h, L);
@@ -176,11 +171,6 @@ std::vector<double> flip_signs(petal_ctx& c, int dtype, const void* U, int64_t n
         // packed on the device (op_flip_key), so nothing here waits for the host.
         op_flip_key(c.dev, r.f64(), g.f64(), L);
         allreduce_f64(c, g.f64(), L, PETAL_MAX);
-        if (deferred) {
-            deferred->assign(L, 0.0);
-            dev_d2h(c.dev, deferred->data(), g.p, g.bytes);
-            return sg;
-        }
         dev_d2h(c.dev, win.data(), g.p, g.bytes);
         dev_sync(c.dev);
         return signs_from_triple(win, L);
@@ -302,7 +292,6 @@ bool topk_eigh(petal_ctx& c, const double* C, int64_t d, int64_t dp, int64_t nc,
         op_dgemm(dv, false, false, dp, nc, p, 1.0, Y.f64(), p, S.f64(), p, 0.0, R.f64(), p);   // C (Q S)
         op_ritz_residual(dv, R.f64(), p, V, dp, dp, nc, th.f64(), resid3 ? vf.as<int>() : nullptr, out3, w, ndrop);
     };
-    auto deliver = [&] {};
     double h3[3], prev_rel = -1.0;
     int bad_rates = 0;   // consecutive checks whose measured rate said "cannot get there" (one transient stall must not
                          // send a spectrum that converges a few checks later to the full eigen-solve)
@@ -313,13 +302,12 @@ bool topk_eigh(petal_ctx& c, const double* C, int64_t d, int64_t dp, int64_t nc,
         if (it % 2 == 1) {  // Rayleigh-Ritz + residual check every second product (never converged after the first)
             if (resid3) {
                 rayleigh_ritz(resid3);
-                deliver();
                 return true;
             }
             rayleigh_ritz(r3.f64());
             dev_d2h(dv, h3, r3.p, sizeof(h3));
             dev_sync(dv);
-            if (topk_verdict_ok(h3, verdict_tol)) { deliver(); return true; }
+            if (topk_verdict_ok(h3, verdict_tol)) return true;
             if (h3[2] != 0.0) return false;   // (a non-finite residual, or an orthonormalisation dropped a pivot: the full eigen-solve)
             // No gap behind the wanted pairs (a smoothly decaying spectrum): the residual falls by (lambda_{p+1} / lambda_nc)^2 per
             // check and would need hundreds of them.  Give up as soon as the measured rate says the remaining budget cannot get
@@ -382,6 +370,28 @@ bool accurate_small_svd(petal_ctx& c, const DevMat& X, const void* muT, const do
 }
 // (sigma_k / sigma_1 of the Gram route's own eigenvalues below this: its sigma_k is no longer good to 1e-9)
 constexpr double GRAM_ROUTE_FLOOR = 3.1622776601683794e-4;  // 10^-3.5
+// ratio = sigma_k / sigma_1 of the spectrum [first ... last] below that floor?  Never on rank-deficient data (last <= 0, n < d): the accurate
+// route's Cholesky would only break down -- after allocating a second copy of X and two more passes; ADVICE round 3.
+bool below_gram_floor(double first, double last, double ratio, int64_t n_total, int64_t d) {
+    return first > 0 && last > 0 && n_total >= d && ratio < GRAM_ROUTE_FLOOR;
+}
+// ... on the first nc eigenvalues lam (device) of the Gram route: one round trip; the ranks of a sharded fit agree
+bool lam_below_gram_floor(petal_ctx& c, const double* lam, int64_t nc, int64_t n_total, int64_t d) {
+    std::vector<double> hl(nc);
+    dev_d2h(c.dev, hl.data(), lam, sizeof(double) * nc);
+    dev_sync(c.dev);
+    return agree_any(c, below_gram_floor(hl[0], hl[nc - 1], std::sqrt(hl[nc - 1] / hl[0]), n_total, d));
+}
+// The Gram eigen step as Pca and FastICA share it: fp64 keeps a copy of C (the eigen-solvers may destroy it; the accurate route factors it
+// again), then topk_eigh (r3: its optimistic form; vtol: its residual tolerance).  topk false: the caller runs the full eigen-solver.
+struct GramEigen { DBuf Ckeep; double vtol; bool topk; };
+GramEigen gram_topk_eigh(petal_ctx& c, int dt, const DBuf& C, int64_t d, int64_t dp, int64_t nc, double* V, double* w, double* r3) {
+    GramEigen g;
+    if (dt == F64) { g.Ckeep = DBuf(c.dev, C.bytes); dev_d2d(c.dev, g.Ckeep.p, C.p, C.bytes); }
+    g.vtol = dt == F32 ? 1e-12 : 3e-14;
+    g.topk = topk_eigh(c, C.f64(), d, dp, nc, V, w, dt == F32 ? 1e-8 : 1e-5, r3, g.vtol);
+    return g;
+}
 
 struct Timer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -404,6 +414,55 @@ void finish_stats(petal_ctx& c, const Timer& t) {
     c.stats.stream_launches = kt.launches[TAG_STREAM];
     c.stats.allreduce_ms = kt.ms[TAG_COMM];
     c.stats.allreduce_timed = kt.launches[TAG_COMM];
+}
+
+// the start of every fit: the clock, cleared kernel timing and stats, the input's check
+Timer start_fit(petal_ctx& c, const petal_matrix& x) {
+    Timer t;
+    dev_reset_timing(c.dev);
+    c.stats = petal_stats{};
+    check_matrix(x, "input");
+    return t;
+}
+// A fit's input and its rows over all ranks.  Sharded: X and the prologue (`sums` column sums per column: 1, or 2 with the sums of squares;
+// rank 0's draw).  Single rank: only the row count -- the caller ingests X once its own checks have passed.
+struct FitInput { DevMat X; ShardPrologue pro; RankInfo ri; int64_t n_total = 0; };
+FitInput fit_input(petal_ctx& c, const petal_matrix& x, int sums, const void* draw, int64_t ndraw) {
+    FitInput in;
+    if (sharded(c)) {
+        in.X = ingest(c, x);
+        in.pro = shard_prologue(c, in.X, sums * in.X.dp, sums == 2, x.dtype, draw, ndraw);
+        in.ri = in.pro.ri;
+    } else {
+        in.ri.n_total = double(x.rows);
+    }
+    in.n_total = int64_t(in.ri.n_total);
+    return in;
+}
+
+struct PcaOutputs { void *components, *means, *singular, *total_variance; const petal_matrix* y_out; };
+// A Pca / RandomizedPca fit's results to the caller's arrays: the rows of `comp` (host; may be out.components) with svd_flip's sign (pca.rs:684,
+// 223), singular values, means, total variance, and fit_transform's U[:, :k] * sg * sigma (transform_with_u, pca.rs:758-779; U: device).
+void write_pca_outputs(petal_ctx& c, const PcaOutputs& out, int dt, int64_t k, int64_t d, const void* comp, const double* sg,
+                       const double* hs, const double* hmu, double tv, const void* U, int64_t n, int64_t ldu) {
+    const auto rows = [&](const auto* src, auto* dst) {
+        for (int64_t j = 0; j < k; ++j) {
+            if (sg[j] < 0) for (int64_t i = 0; i < d; ++i) dst[j * d + i] = -src[j * d + i];
+            else if (dst != src) std::memcpy(dst + j * d, src + j * d, sizeof(*dst) * size_t(d));
+            put_elem(out.singular, dt, j, hs[j]);
+        }
+    };
+    if (dt == F32) rows(static_cast<const float*>(comp), static_cast<float*>(out.components));
+    else rows(static_cast<const double*>(comp), static_cast<double*>(out.components));
+    for (int64_t i = 0; i < d; ++i) put_elem(out.means, dt, i, hmu[i]);
+    put_elem(out.total_variance, dt, 0, tv);
+    if (out.y_out) {
+        std::vector<double> sc(ldu, 0.0);
+        for (int64_t j = 0; j < k; ++j) sc[j] = sg[j] * hs[j];
+        DBuf dsc(c.dev, sizeof(double) * ldu);
+        dev_h2d(c.dev, dsc.p, sc.data(), dsc.bytes);
+        emit(c, dt, U, n, k, ldu, *out.y_out, dsc.f64());
+    }
 }
 
 }  // namespace
@@ -506,135 +565,81 @@ void emit(petal_ctx& c, int dtype, const void* src, int64_t n, int64_t cols, int
 
 // ---------------------------------------------------------------------------------------------
 // RandomizedPca::inner_fit (pca.rs:509-550) -> randomized_svd (pca.rs:668-686) -> range finder (689-718)
-void rpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, int64_t n_oversample, int64_t n_iter, bool centering,
-              const void* omega, void* components, void* means, void* singular, void* total_variance,
-              const petal_matrix* y_out) {
-    Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
-    check_matrix(x, "input");
-    if (k < 0 || n_oversample < 0 || n_iter < 0) invalid_input("negative parameter");
-    const int dt = x.dtype;
-    const int64_t d = x.cols, l_req = k + n_oversample;
-    // fp32 input: the total variance comes from column sums of squares gathered in the means pass (exact products, fp64
+namespace {
+// One attempt of a RandomizedPca fit.  robust: the robust pipeline; exact: three-plane operands; jacobi: the small stage alone is repeated
+// with the Jacobi eigen-solver; rebase_now: the sketch is re-based on the tall side before its first product with Xc^T.
+struct Attempt { bool robust = false, exact = false, jacobi = false, rebase_now = false; };
+// The attempt policy: false when the fit is done, else `a` becomes the next attempt and the stats record the redo (the last one wins).
+// A robust run is final.  The verdict (verdict_code): pivot breakdowns -> the robust path; a heavy tail behind the block -> the same pipeline with
+// three-plane operands; a cluster among the wanted eigenvalues -> the small stage again with the Jacobi solver (the passes
+// over X stand).  Sharded fits branch on the MAX over the ranks.
+bool next_attempt(Attempt& a, double verdict, int64_t n_iter, petal_stats& st) {
+    if (a.robust) return false;
+    if (verdict >= VERDICT_PIVOT && !a.rebase_now && n_iter >= 1) {
+        // A lost pivot is, on full-rank data, the FIRST product pair's: from a random start every column of Xc^T (Xc Omega)
+        // is dominated by sigma_1, and beyond sigma_1 / sigma_l ~ 5e3 its Gram matrix is singular to fp64 (uncentred data far off
+        // centre: the mean direction is sigma_1).  The robust path would answer with a different iteration (dependent columns dropped
+        // and refilled): 1.9e-3 / 5e-4 off the oracle at n_iter 4 / 5 on such data, where the same pipeline with the sketch re-based
+        // on the tall side first -- what short iterations do anyway, and the crate's first LU -- holds 1e-4 / 3e-5.  So that is
+        // tried first; rank-deficient data loses its pivot again and takes the robust path one run later.  (fp64 data too: its first pair
+        // breaks down beyond sigma_1 / sigma_l ~ 5e3 all the same -- (sigma_1 / sigma_l)^4 against 1e-15 -- while the re-based sketch's
+        // tall-side Gram matrix holds to ~3e6; uncentred fp64 data 300 sigma off centre came back 1e-5 ... 1e-7 off at n_iter 1 - 3 on the
+        // robust path: dev/fuzz_hostsim6.py)
+        a.rebase_now = true; a.jacobi = false; st.rpca_redo = 3;
+        return true;
+    }
+    if (verdict >= VERDICT_PIVOT) { a.robust = true; a.exact = true; a.jacobi = false; st.rpca_redo = 2; return true; }
+    if (verdict == VERDICT_TAIL && !a.exact) { a.exact = true; a.jacobi = false; st.rpca_redo = 1; return true; }
+    if (verdict == VERDICT_EIG && !a.jacobi) { a.jacobi = true; st.eigh_redo = 1; return true; }
+    return false;
+}
+// Everything the host reads back sits in ONE device buffer behind the all-reduced [Yp | tv] pair, so a fit ends with one
+// device-to-host copy (five separate small copies cost 4 us each):
+//   res = [ Yp (dp LP) | tv | verdict words (two doubles) | lam (LP) | mu64 (2 dp) | flip (4 LP) | + 1 ]
+// and the components leave in their own k x d buffer, already in the caller's layout and type (op_components_out): 128 KB at
+// configs[1] instead of the 320 KB fp64 d x l matrix V, and nothing for the host to transpose.
+// Offsets in doubles.  verdict: three int words, verdict_code's order; flip: the slot of the kp signed columns (flip_signs_to_slot:
+// [absmax | row | sign | key]) and right behind the keys the agreed verdict of a sharded fp32 fit.
+struct ResultBlock {
+    int64_t tv, verdict, lam, mu, flip, agreed, len;
+    ResultBlock(int64_t dp, int64_t LP, int64_t kp)
+        : tv(dp * LP), verdict(tv + 1), lam(verdict + 2), mu(lam + LP), flip(mu + 2 * dp), agreed(flip + 4 * kp), len(flip + 4 * LP + 1) {}
+};
+// One RandomizedPca fit: sizes, device buffers, the read-back block and the flags its stages share.  rpca_fit's attempt loop runs
+// pipeline() (first_products, power_iterations, range_basis), small_stage() and read_back(); write_out() delivers the last attempt.
+struct RpcaRun {
+    petal_ctx& c;
+    const FitInput& in;
+    const DevMat& X;
+    const petal_matrix* const y_out;
+    const int dt;
+    const int64_t d, k, n_iter, l_req, L, LP, n, dp, kp;
+    const size_t esz, comp_bytes;   // (comp_bytes: the components sit right behind the block: both leave in one copy)
+    // (tv_from_sq) fp32 input: the total variance comes from column sums of squares gathered in the means pass (exact products, fp64
     // sums: the cancellation in sum x^2 - n mu^2 costs (mu / sigma)^2 ulps of fp64, far below fp32 resolution); fp64 input
     // keeps the centred sum fused into the first product
-    const bool tv_from_sq = centering && dt == F32;
-    DevMat X;
-    ShardPrologue pro;
-    RankInfo ri;
-    if (sharded(c)) {
-        // (argument errors that every rank sees alike are raised BEFORE the collective, so no rank is left waiting in it)
-        if (d > 0 && l_req > 0 && omega == nullptr) invalid_input("omega is required");
-        X = ingest(c, x);
-        pro = shard_prologue(c, X, centering ? (tv_from_sq ? 2 * X.dp : X.dp) : 0, tv_from_sq, dt, omega, d * l_req);
-        ri = pro.ri;
-    } else {
-        ri.n_total = double(x.rows);
-    }
-    const int64_t n_total = int64_t(ri.n_total);
-    if (n_total < k || d < k)  // pca.rs:513-518
-        invalid_input("every dimension should be at least " + std::to_string(k));
-    if (centering && n_total == 0) {  // mean_axis -> None (pca.rs:521-525): Ok, model untouched
-        if (y_out && (y_out->rows != 0)) invalid_input("output has the wrong shape");
-        return;
-    }
-    const int64_t L = std::min(l_req, std::min(n_total, d));  // the reference's min(nrows, ncols) slices, pca.rs:710/713
-    if (L > 0 && omega == nullptr) invalid_input("omega is required");
-    if (d == 0 || L == 0) {  // nothing to decompose: k == 0 here
-        if (total_variance) put_elem(total_variance, dt, 0, 0.0);
-        if (y_out) emit(c, dt, nullptr, x.rows, 0, 0, *y_out);
-        return;
-    }
-    const int64_t LP = round_up(L, 16);
-    if (!sharded(c)) X = ingest(c, x);
-    const int64_t n = X.n, dp = X.dp;
-    const size_t esz = dtype_size(dt);
-    const double tol_drop = (dt == F32 ? 1e-6 : 1e-13);
-    const double tol_tall = (dt == F32 ? 1e-12 : 1e-13);   // dependence test of the tall-side Gram matrices (fp64 products of the stored iterate)
-
-    // Everything the host reads back sits in ONE device buffer behind the all-reduced [Yp | tv] pair, so a fit ends with one
-    // device-to-host copy (five separate small copies cost 4 us each):
-    //   res = [ Yp (dp LP) | tv | ndead (pivot, heavy tail) | neig (eigen-solver) | lam (LP) | mu64 (2 dp) | flip (4 LP) ]
-    // and the components leave in their own k x d buffer, already in the caller's layout and type (op_components_out): 128 KB at
-    // configs[1] instead of the 320 KB fp64 d x l matrix V, and nothing for the host to transpose.
-    const int64_t o_tv = dp * LP, o_dead = o_tv + 1, o_eig = o_dead + 1, o_lam = o_eig + 1, o_mu = o_lam + LP, o_flip = o_mu + 2 * dp, res_len = o_flip + 4 * LP + 1;  // (+ 1: the agreed redo verdict of a sharded fp32 fit)
-    // (the components sit right behind the block: both leave in one copy)
-    const size_t comp_bytes = esz * size_t(k) * d;
-    DBuf res(c.dev, sizeof(double) * res_len + std::max<size_t>(comp_bytes, 8));
-    void* const comp_dev = res.f64() + res_len;
-    double* const Yp = res.f64();
-    double* const tvp = res.f64() + o_tv;
-    int* const ndead = reinterpret_cast<int*>(res.f64() + o_dead);   // three verdict words in a row: [0] pivot breakdowns, [1] heavy tail,
-    int* const neig = ndead + 2;                                     // [2] eigenvalues too close for the two-stage eigen-solver's vectors
-    static_assert(sizeof(double) == 2 * sizeof(int), "verdict words");
-    double* const lam = res.f64() + o_lam;
-    double* const mu64 = res.f64() + o_mu;
-    double* const flip = res.f64() + o_flip;
+    const bool centering, tv_from_sq;
+    // (tol_tall: the dependence test of the tall-side Gram matrices -- fp64 products of the stored iterate)
+    const double tol_drop, tol_tall;
+    const ResultBlock o;
+    DBuf res;
+    double *const Yp, *const tvp, *const lam, *const mu64, *const flip;
+    int *const ndead, *const neig;   // the verdict words
+    void* const comp_dev;
     DBuf muT;
     // Omega (pca.rs:701-705): d x l_req row-major host draw -> first L columns, padded to dp x LP, f64.  Single rank: the raw draw
     // is staged in the pinned ring without a host wait and widened on the device; sharded: rank 0's draw came back from the
     // prologue's all-reduce, already fp64.
     DBuf P;
-    // The column-means pass is queued FIRST: the device starts on it at once, and the host's copy of Omega into the pinned ring
-    // runs beside it.
-    // Single-rank fp32 fits whose first product is a FUSED pass gather the means inside it (op_power_pass_means: X is read once for
-    // the means, the sums of squares and the first power iteration together -- round 4 spent a pass of its own on the first two,
-    // the reference three: pca.rs:520-533): the means pass is then not queued here but decided in the pipeline.
-    // (From 200000 rows on: at configs[1]'s 100000 x 512 the matrix sits in the Infinity Cache, the means pass costs 37 us and what
-    // replaces it -- the sample's means, the all-ones column and the squares in the first pass, the move to the true centre -- costs
-    // the same; at 1e6 rows the pass is 0.33 ms of HBM time and the fold takes 5 % off the fit.)
-    // (fp32 data, up to FOUR iterations: the sketch Z = Xc Omega is re-based on the tall side before its product with Xc^T -- see the
-    // pipeline -- so the first product pair is not a fused pass and cannot gather the means)
-    const bool rebase_sketch = dt == F32 && n_iter >= 1 && n_iter <= 4;
-    // (... and, at any n_iter, the second attempt of a fit whose first one lost a pivot: see the attempt loop)
-    bool rebase_now = rebase_sketch;
-    const double fold_rows = dev_option(c.dev, OPT_MEANS_FOLD_ROWS);   // (PETAL_OPT_MEANS_FOLD_ROWS; negative: never)
-    const bool fold_means = !sharded(c) && tv_from_sq && dev_gemm_mode(c.dev) == 0 && n_iter >= 3 && !rebase_sketch && L < LP && fold_rows >= 0 && double(n) >= fold_rows &&
-                            op_power_pass_applies(c.dev, dt, X.p, n, dp, X.ld, X.p, LP) && dev_option(c.dev, OPT_TWO_PLANE) != 0;
-    bool means_done = false, tv_direct = false;
-    auto means_pass = [&] {
-        if (!tv_from_sq) dev_memset(c.dev, mu64 + dp, 0, sizeof(double) * dp);
-        dev_set_tag(c.dev, TAG_STREAM);
-        column_means_into(c, X, ri.n_total, centering, mu64, muT, tv_from_sq, sharded(c) && centering ? pro.sums : nullptr);
-        dev_set_tag(c.dev, TAG_NONE);
-        means_done = true;
-    };
-    if (!fold_means) means_pass();
-    else muT = DBuf(c.dev, esz * size_t(dp));   // (mu64: means and, in its second half's first slot, the variance -- both written by the pass)
-    if (sharded(c)) {
-        P = DBuf(c.dev, sizeof(double) * dp * LP);
-        op_pad_to_f64(c.dev, F64, P.f64(), dp, LP, pro.draw, d, L, l_req, tvp, 3 + LP);
-    } else {
-        // (queued behind the means pass, so the host's copy into the ring runs beside it.  No transfer of its own: the widening
-        // kernel reads the draw from the pinned ring over the link.  A side stream for this, joined in front of the first product,
-        // measured the same; one for the components' write-out further down COST 46 us a fit -- an event recorded on the main
-        // stream and the wait for the join are bubbles of their own, far longer than the kernel trace shows: EXPERIMENTS.md)
-        P = DBuf(c.dev, sizeof(double) * dp * LP);
-        const void* view = dev_h2d_view(c.dev, omega, esz * size_t(d) * l_req);
-        if (view) {
-            op_pad_to_f64(c.dev, dt, P.f64(), dp, LP, view, d, L, l_req, tvp, 3 + LP);  // (also clears tv, ndead, lam for the first pipeline run)
-        } else {   // a draw beyond a ring slot
-            DBuf raw(c.dev, esz * size_t(d) * l_req);
-            dev_h2d_async(c.dev, raw.p, omega, raw.bytes);
-            op_pad_to_f64(c.dev, dt, P.f64(), dp, LP, raw.p, d, L, l_req, tvp, 3 + LP);
-        }
-    }
-    DBuf Z(c.dev, esz * size_t(std::max<int64_t>(n, 1)) * LP), Z1(c.dev, esz * size_t(std::max<int64_t>(n, 1)) * LP);
-    c.stats.pass_flops = 2.0 * double(n) * double(d) * double(l_req);
-    c.stats.pass_bytes = double(esz) * (double(n) * d + double(n) * l_req + double(d) * l_req);
-
-    DBuf Gb(c.dev, sizeof(double) * LP * LP);
-    double* const G = Gb.f64();
-    DBuf T(c.dev, sizeof(double) * LP * LP), Y(c.dev, sizeof(double) * dp * LP);
-    DBuf Bt(c.dev, sizeof(double) * dp * LP), S(c.dev, sizeof(double) * LP * LP), Uh(c.dev, sizeof(double) * LP * LP);
-    DBuf M2(c.dev, sizeof(double) * LP * LP);
+    // (fp32 data, up to FOUR iterations: the sketch Z = Xc Omega is re-based on the tall side before its product with Xc^T -- see
+    // first_products() -- so the first product pair is not a fused pass and cannot gather the means)
+    // (... and, at any n_iter, the second attempt of a fit whose first one lost a pivot: see next_attempt())
+    const bool rebase_sketch;
+    bool fold_means = false, means_done = false, tv_direct = false;
+    DBuf Z, Z1, Gb, T, Y, Bt, S, Uh, M2;
+    double* G = nullptr;   // Gb's
     void* Uout = nullptr;  // where the pipeline left U (n x LP; its first kp columns)
-    const bool slot_flip = !sharded(c) || dt == F32;  // (sharded fp64 decides the signs in three dependent all-reduce rounds)
-    const int64_t kp = std::min(LP, round_up(std::max<int64_t>(k, 1), 16));
-    // The whole device pipeline.  It runs OPTIMISTICALLY first (robust = false): every power iteration re-bases with
-    // the single-Cholesky fast path and no host round trip; the kernels record the worst pivot breakdown in `ndead`,
-    // which is read together with the results.  Only if a breakdown happened is the fit redone with robust = true.
+    const bool slot_flip;  // (sharded fp64 decides the signs in three dependent all-reduce rounds)
     // Two operands of the split-product K1 may be ROUNDED to 16 significant bits (two bf16 planes: five piece products instead
     // of six) -- the sketch matrix when power iterations follow, and the re-based iterates.  That is a change of basis plus a
     // perturbation of the spanned subspace: harmless when the spectrum falls off behind the block (what the rounding injects from
@@ -643,177 +648,255 @@ void rpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, int64_t n_oversamp
     // and a verdict formed from the spectrum the fit itself found (op_tail_verdict) sends a heavy-tailed fit back through the
     // pipeline with three planes everywhere (exact = true).  Nothing is remembered from fit to fit: the same input gives the same
     // bits whatever the ctx ran before (a caller who knows the data selects PETAL_GEMM_SPLIT_BF16X3_EXACT and skips the first run).
-    const bool two_plane_applies = dt == F32 && dev_gemm_mode(c.dev) == 0 && n_iter > 0;
-    const double p2_thr = dev_option(c.dev, OPT_VERDICT_THRESHOLD);
-    // (what the small stage below needs from the passes: hoisted so that it can run again by itself)
+    const bool two_plane_applies;
+    const double p2_thr;
+    // (what the small stage needs from the passes: kept here so that it can run again by itself)
     const void* Usrc = nullptr;  // the n x LP matrix U is formed from (U = Usrc . M2) ...
     void* Ubuf = nullptr;        // ... and the buffer it goes to
     bool t_rt = false;           // T holds R in RT form (op_chol_rt), not the explicit inverse
     bool steered = false;        // fused / steering passes ran: the heavy-tail verdict prices their rounding too
     int pipeline_runs = 0;       // (every run after the first clears the verdict words itself -- the re-based retry of an OPTIMISTIC run too)
-    auto pipeline = [&](bool robust, bool exact) {
-    const int planes = (n_iter > 0 && !robust && !exact) ? 2 : 3;
-    if (pipeline_runs++ > 0) dev_memset(c.dev, tvp, 0, sizeof(double) * (3 + LP));  // tv, ndead, neig, lam (only lam[0 .. L) is written below); the first run's were cleared with Omega
-    // The FUSED power-iteration pass Y' = Xc^T (Xc P) (one pass over X where K1 + K2 make two; it needs P on two planes, so it
-    // belongs to the optimistic run): every product pair of the loop below, the last one also storing Z.
-    const bool use_pow = planes == 2 && op_power_pass_applies(c.dev, dt, X.p, n, dp, X.ld, muT.p, LP);
-    // STEERING products: every product of the optimistic run whose result only feeds the next re-basing may round its
-    // large operands to two bf16 planes like the iterate (the fused passes do; K1 / K2 in their forms for more than 80 columns do)
-    const bool steer = planes == 2 && dt == F32 && n_iter >= 3;
-    bool have_yp = false;   // Yp already holds Xc^T Z for the current basis
-    if (!means_done) {      // (fold_means: the first run of the pipeline)
-        if (use_pow) {
-            dev_set_tag(c.dev, TAG_POW);
-            // mu64 = [means | tv, scratch, 0 ...]: the total variance lands where the sums of squares would have
-            have_yp = op_power_pass_means(c.dev, dt, X.p, n, dp, d, X.ld, ri.n_total, P.f64(), LP, LP, L, Yp, LP, mu64, muT.p, mu64 + dp + 1, mu64 + dp);
-            dev_set_tag(c.dev, TAG_NONE);
-        }
-        if (have_yp) { means_done = true; tv_direct = true; }
-        else means_pass();
-    }
-    if (!have_yp && use_pow && n_iter >= 3 && !rebase_now && tv_from_sq) {
-        dev_set_tag(c.dev, TAG_POW);
-        have_yp = op_power_pass(c.dev, dt, X.p, n, dp, X.ld, muT.p, P.f64(), LP, LP, nullptr, LP, Yp, LP, /*steering=*/true);   // pca.rs:707 + 711
-        dev_set_tag(c.dev, TAG_NONE);
-        if (have_yp) allreduce_f64(c, Yp, dp * LP, PETAL_SUM);
-    }
-    if (!have_yp) {
-    // Z = Xc . Omega (pca.rs:707); total_variance = sum Xc^2 (pca.rs:533) is fused into this product unless tv_from_sq
-    dev_set_tag(c.dev, TAG_XP);
-    // (with power iterations behind it the sketch matrix may be ANY matrix: the optimistic run lets the kernel round Omega to two
-    // bf16 planes -- five piece products; n_iter = 0 and the robust redo keep Omega as given)
-    op_gemm_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, P.f64(), LP, LP, nullptr, Z.p, LP, tv_from_sq ? nullptr : tvp, planes, steer);
-    dev_set_tag(c.dev, TAG_NONE);
-
-    // A SHORT iteration (n_iter 1 - 4) on fp32 data re-bases the sketch Z = Xc Omega on the tall side first, as the crate does
-    // with its first LU (pca.rs:709).  Every column of Z is dominated by sigma_1, so the un-rebased double product Xc^T (Xc Omega)
-    // carries direction j at (sigma_j / sigma_1)^2 of a column -- 1e-6 on the planted spectra -- under an fp32 accumulation that
-    // is good to 6e-8 of it: the block's weakest directions come back 6 % junk, and with only one or two products behind it the
-    // fit is off by 2e-4 where the crate's own f32 path holds 1e-5 (measured, EXPERIMENTS.md round 5).  With Z = Q R first, a
-    // column of Xc^T Q carries direction j at sigma_j / sigma_1.  Later products wash the junk out at the rate of the spectrum's
-    // gaps: at n_iter = 3 it was gone for k = 64 of 512 features (3e-6) but NOT for 87 ... 126 components (1.5e-4 ... 3.6e-4
-    // where the oracle run in float32 holds 1.4e-5 ... 8e-5: dev/fuzz_round6.py, round 6), so three iterations re-base too --
-    // only their first product pair: the later ones are fused / steering passes as for any n_iter >= 3.  FOUR iterations likewise: a later
-    // seed of the same sweep had 60000 x 1024, k = 93, n_iter = 4 at 1.07e-4 against the float32 oracle's 1.0e-5.  From five iterations
-    // on the two extra passes over Z are not spent (no miss of this kind in ~220 random cases at n_iter 5 / 7 with up to 127 components, 425 in all).
-    }
-    const void* Zfirst = Z.p;   // what the first product with Xc^T reads
-    if (rebase_now && !robust) {
-        op_gemm_atb(c.dev, dt, Z.p, LP, LP, nullptr, Z.p, LP, LP, nullptr, n, G, LP, /*precise=*/true);
-        allreduce_f64(c, G, LP * LP, PETAL_SUM);
-        op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_tall, nullptr, LP);
-        op_gemm_xp(c.dev, dt, Z.p, n, LP, LP, nullptr, T.f64(), LP, LP, nullptr, Z1.p, LP, nullptr);
-        Zfirst = Z1.p;
-    }
-    double* Pcur = P.f64();  // the orthonormal basis the current Z was formed with
-    for (int64_t it = 0; it < n_iter; ++it) {  // pca.rs:708-715
-        if (!have_yp) {
-            dev_set_tag(c.dev, TAG_ATB);
-            op_gemm_atb(c.dev, dt, X.p, X.ld, dp, muT.p, it == 0 ? Zfirst : Z.p, LP, LP, nullptr, n, Yp, LP, false, steer);  // Yp = Xc^T Z (pca.rs:711)
-            dev_set_tag(c.dev, TAG_NONE);
-            allreduce_f64(c, Yp, dp * LP, PETAL_SUM);
-        }
-        have_yp = false;
-        // Re-base the d x l iterate (stands for the two pivoted-LU re-basings of pca.rs:709-713).  The next product only
-        // needs SOME well-conditioned basis of range(Yp): P = Yp T spans range(Yp) exactly for any invertible
-        // triangular T, so the accuracy of T only decides how well-conditioned P is, never which subspace it spans (the
-        // final thin QR restores orthonormality).
-        if (!robust) {
-            // fast path: one fp64 Cholesky of Yp^T Yp, valid while every pivot stays positive (cond(Yp) <~ 3e7: errors
-            // of a few per cent in the weakest pivots merely leave cond(P) ~ 1.x); breakdowns are recorded in ndead.
-            // Y = Yp R^-1 is formed inside the next product's operand-packing kernel (op_rebase_xp), by substitution, not by a
-            // launch of its own; R^-1 itself is not needed during the iteration.
-            op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Yp, LP, Yp, LP, 0.0, G, LP);
-            if (use_pow) {   // re-base, then BOTH products of the next iteration in one pass (the last one keeps Z for U = Z (T Uh))
-                const bool last = it + 1 == n_iter;
-                dev_set_tag(c.dev, TAG_POW);
-                have_yp = op_rebase_power_pass(c.dev, dt, X.p, n, dp, X.ld, muT.p, G, L, LP, 1e-15, ndead, Yp, LP, LP, T.f64(), LP, Y.f64(), LP,
-                                               last ? Z.p : nullptr, LP, Yp, LP, /*steering=*/steer && !last);   // pca.rs:714 + 711
-                // (steer: n_iter >= 3 -- the short iterations keep every pass at five / six piece products: ADVICE round 5)
-                dev_set_tag(c.dev, TAG_NONE);
-                if (have_yp) allreduce_f64(c, Yp, dp * LP + (last ? 1 : 0), PETAL_SUM);   // (the last one: [ Xc^T Z | sum Xc^2 ])
-            }
-            if (!have_yp) {
-            dev_set_tag(c.dev, TAG_XP);   // (only the product kernel itself is bracketed)
-            op_rebase_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, G, L, LP, 1e-15, ndead, Yp, LP, LP, T.f64(), LP, Y.f64(), LP, Z.p, LP, planes,
-                         steer && it + 1 < n_iter);  // pca.rs:714 (the last iteration's Z is the iterate the results are made of: exact)
-            dev_set_tag(c.dev, TAG_NONE);
-            }
+    // set by pipeline() for the stages of one run
+    int planes = 3;
+    bool use_pow = false, steer = false, have_yp = false;   // (have_yp: Yp already holds Xc^T Z for the current basis)
+    // the host's copy of the block from tv on, and the components
+    std::vector<double> keep;
+    std::vector<char> comp_keep;
+    const void* hcomp = nullptr;
+    RpcaRun(petal_ctx& c_, const FitInput& in_, const petal_matrix* y_out_, int64_t k_, int64_t l_req_, int64_t n_iter_, int64_t L_,
+            bool centering_, const void* omega)
+        : c(c_), in(in_), X(in_.X), y_out(y_out_), dt(X.dtype), d(X.d), k(k_), n_iter(n_iter_), l_req(l_req_), L(L_), LP(round_up(L_, 16)),
+          n(X.n), dp(X.dp), kp(std::min(LP, round_up(std::max<int64_t>(k_, 1), 16))), esz(dtype_size(dt)), comp_bytes(esz * size_t(k) * d),
+          centering(centering_), tv_from_sq(centering_ && dt == F32), tol_drop(dt == F32 ? 1e-6 : 1e-13), tol_tall(dt == F32 ? 1e-12 : 1e-13),
+          o(dp, LP, kp), res(c.dev, sizeof(double) * o.len + std::max<size_t>(comp_bytes, 8)), Yp(res.f64()),
+          tvp(res.f64() + o.tv), lam(res.f64() + o.lam), mu64(res.f64() + o.mu), flip(res.f64() + o.flip),
+          ndead(reinterpret_cast<int*>(res.f64() + o.verdict)), neig(ndead + 2), comp_dev(res.f64() + o.len),
+          rebase_sketch(dt == F32 && n_iter >= 1 && n_iter <= 4), slot_flip(!sharded(c) || dt == F32),
+          two_plane_applies(dt == F32 && dev_gemm_mode(c.dev) == 0 && n_iter > 0), p2_thr(dev_option(c.dev, OPT_VERDICT_THRESHOLD)) {
+        static_assert(sizeof(double) == 2 * sizeof(int), "verdict words");
+        // The column-means pass is queued FIRST: the device starts on it at once, and the host's copy of Omega into the pinned ring
+        // runs beside it.
+        // Single-rank fp32 fits whose first product is a FUSED pass gather the means inside it (op_power_pass_means: X is read once for
+        // the means, the sums of squares and the first power iteration together -- round 4 spent a pass of its own on the first two,
+        // the reference three: pca.rs:520-533): the means pass is then not queued here but decided in the pipeline.
+        // (From 200000 rows on: at configs[1]'s 100000 x 512 the matrix sits in the Infinity Cache, the means pass costs 37 us and what
+        // replaces it -- the sample's means, the all-ones column and the squares in the first pass, the move to the true centre -- costs
+        // the same; at 1e6 rows the pass is 0.33 ms of HBM time and the fold takes 5 % off the fit.)
+        const double fold_rows = dev_option(c.dev, OPT_MEANS_FOLD_ROWS);   // (PETAL_OPT_MEANS_FOLD_ROWS; negative: never)
+        fold_means = !sharded(c) && tv_from_sq && dev_gemm_mode(c.dev) == 0 && n_iter >= 3 && !rebase_sketch && L < LP && fold_rows >= 0 &&
+                     double(n) >= fold_rows && op_power_pass_applies(c.dev, dt, X.p, n, dp, X.ld, X.p, LP) && dev_option(c.dev, OPT_TWO_PLANE) != 0;
+        if (!fold_means) means_pass();
+        else muT = DBuf(c.dev, esz * size_t(dp));   // (mu64: means and, in its second half's first slot, the variance -- both written by the pass)
+        P = DBuf(c.dev, sizeof(double) * dp * LP);
+        if (sharded(c)) {
+            op_pad_to_f64(c.dev, F64, P.f64(), dp, LP, in.pro.draw, d, L, l_req, tvp, 3 + LP);
         } else {
-            // ill-conditioned iterate: precondition with the tall side first.  Z = Xc P gives Z^T Z = P^T (Xc^T Z) =
-            // P^T Yp without a pass over Z (op_chol_inv reads the upper triangle only); T = chol(Z^T Z)^-1 is applied on
-            // the small side, Xc^T (Z T) = Yp T, and the now moderately conditioned Yp T gets its own Cholesky-QR.
-            op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Pcur, LP, Yp, LP, 0.0, G, LP);
-            op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_drop, nullptr, LP);
-            op_dgemm(c.dev, false, false, dp, LP, LP, 1.0, Yp, LP, T.f64(), LP, 0.0, Y.f64(), LP);
-            // A column the dependence test dropped (its part of Z below ~1e-3 of the part already spanned: from a random start
-            // every column of Z = Xc Omega is dominated by sigma_1, so a spectrum wider than 1e3 loses its tail here) is
-            // refilled with the matching column of Omega instead of staying zero: orthogonalised against the kept columns
-            // below, the next product shows it the largest direction still missing, and the block regains its width within an
-            // iteration or two -- what the crate's pivoted LU (pca.rs:709-713) achieves by never letting the block lose
-            // rank.  Truly rank-deficient data keeps dropping the refilled columns, down to the final QR (sigma = 0).
-            op_refill_zero_cols(c.dev, Y.f64(), dp, L, LP, P.f64(), LP);
-            orthonormalize_small(c, Y, dp, L, LP, 1e-13);
-            dev_set_tag(c.dev, TAG_XP);
-            op_gemm_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, Y.f64(), LP, LP, nullptr, Z.p, LP, nullptr);  // pca.rs:714
-            dev_set_tag(c.dev, TAG_NONE);
+            // (queued behind the means pass, so the host's copy into the ring runs beside it.  No transfer of its own: the widening
+            // kernel reads the draw from the pinned ring over the link.  A side stream for this, joined in front of the first product,
+            // measured the same; one for the components' write-out further down COST 46 us a fit -- an event recorded on the main
+            // stream and the wait for the join are bubbles of their own, far longer than the kernel trace shows: EXPERIMENTS.md)
+            const void* view = dev_h2d_view(c.dev, omega, esz * size_t(d) * l_req);
+            if (view) {
+                op_pad_to_f64(c.dev, dt, P.f64(), dp, LP, view, d, L, l_req, tvp, 3 + LP);  // (also clears tv, ndead, lam for the first pipeline run)
+            } else {   // a draw beyond a ring slot
+                DBuf raw(c.dev, esz * size_t(d) * l_req);
+                dev_h2d_async(c.dev, raw.p, omega, raw.bytes);
+                op_pad_to_f64(c.dev, dt, P.f64(), dp, LP, raw.p, d, L, l_req, tvp, 3 + LP);
+            }
         }
-        Pcur = Y.f64();
+        Z = DBuf(c.dev, esz * size_t(std::max<int64_t>(n, 1)) * LP);
+        Z1 = DBuf(c.dev, esz * size_t(std::max<int64_t>(n, 1)) * LP);
+        c.stats.pass_flops = 2.0 * double(n) * double(d) * double(l_req);
+        c.stats.pass_bytes = double(esz) * (double(n) * d + double(n) * l_req + double(d) * l_req);
+        Gb = DBuf(c.dev, sizeof(double) * LP * LP);
+        G = Gb.f64();
+        T = DBuf(c.dev, sizeof(double) * LP * LP);
+        Y = DBuf(c.dev, sizeof(double) * dp * LP);
+        Bt = DBuf(c.dev, sizeof(double) * dp * LP);
+        S = DBuf(c.dev, sizeof(double) * LP * LP);
+        Uh = DBuf(c.dev, sizeof(double) * LP * LP);
+        M2 = DBuf(c.dev, sizeof(double) * LP * LP);
     }
-
-    // thin QR of Z (pca.rs:716) and B = Q^T Xc (pca.rs:681).
-    t_rt = false;
-    steered = use_pow || steer;
-    if (n_iter > 0 && !robust) {
-        // ONE more pass over X serves both.  Z = Xc Pcur, so Z^T Z = Pcur^T (Xc^T Z) = Pcur^T Yp with Yp = Xc^T Z, the very
-        // product B needs: with H = Pcur^T Yp = R^T R and T = R^-1, Q = Z T and B = Q^T Xc = (Yp T)^T.  No pass over Z, no
-        // second Gram matrix.  Why one Cholesky suffices here although cond(Z)^2 ~ 1e7 exceeds fp32: Pcur is orthonormal and
-        // spans a nearly invariant subspace of Xc^T Xc, so the fp32 rounding of Pcur and Z perturbs Z^T Z MULTIPLICATIVELY,
-        // (I + E)^T H with ||E|| ~ 1e-8, and ||Q^T Q - I|| ~ ||E|| cond(R) ~ 1e-5 instead of eps cond(Z)^2 (measured 1e-6 ..
-        // 1e-5 up to cond(Z) = 2.5e4; the singular values match the two-pass Cholesky-QR2 form to its own accuracy).  Not so
-        // for a non-orthonormal Pcur (n_iter = 0: the raw Omega) and on the robust redo: those keep Cholesky-QR2 below.
-        if (!have_yp) {   // (the fused pass of the last iteration has formed this product already)
-            dev_set_tag(c.dev, TAG_ATB);
-            op_gemm_atb(c.dev, dt, X.p, X.ld, dp, muT.p, Z.p, LP, LP, nullptr, n, Yp, LP);
-            dev_set_tag(c.dev, TAG_NONE);
-            allreduce_f64(c, Yp, dp * LP + 1, PETAL_SUM);  // [ Xc^T Z | sum Xc^2 ]
+    void means_pass() {
+        if (!tv_from_sq) dev_memset(c.dev, mu64 + dp, 0, sizeof(double) * dp);
+        dev_set_tag(c.dev, TAG_STREAM);
+        column_means_into(c, X, in.ri.n_total, centering, mu64, muT, tv_from_sq, sharded(c) && centering ? in.pro.sums : nullptr);
+        dev_set_tag(c.dev, TAG_NONE);
+        means_done = true;
+    }
+    // The whole device pipeline.  It runs OPTIMISTICALLY first (robust = false): every power iteration re-bases with
+    // the single-Cholesky fast path and no host round trip; the kernels record the worst pivot breakdown in `ndead`,
+    // which is read together with the results.  Only if a breakdown happened is the fit redone with robust = true.
+    void pipeline(const Attempt& a) {
+        planes = (n_iter > 0 && !a.robust && !a.exact) ? 2 : 3;
+        if (pipeline_runs++ > 0) dev_memset(c.dev, tvp, 0, sizeof(double) * (3 + LP));  // tv, ndead, neig, lam (only lam[0 .. L) is written below); the first run's were cleared with Omega
+        // The FUSED power-iteration pass Y' = Xc^T (Xc P) (one pass over X where K1 + K2 make two; it needs P on two planes, so it
+        // belongs to the optimistic run): every product pair of the loop below, the last one also storing Z.
+        use_pow = planes == 2 && op_power_pass_applies(c.dev, dt, X.p, n, dp, X.ld, muT.p, LP);
+        // STEERING products: every product of the optimistic run whose result only feeds the next re-basing may round its
+        // large operands to two bf16 planes like the iterate (the fused passes do; K1 / K2 in their forms for more than 80 columns do)
+        steer = planes == 2 && dt == F32 && n_iter >= 3;
+        have_yp = false;
+        range_basis(a, power_iterations(a, first_products(a)));
+    }
+    // The first product pair: the means pass, or the means folded into the first fused pass; K1 and the optional re-basing of the
+    // sketch on the tall side.  Returns what the first product with Xc^T reads.
+    const void* first_products(const Attempt& a) {
+        if (!means_done) {      // (fold_means: the first run of the pipeline)
+            if (use_pow) {
+                dev_set_tag(c.dev, TAG_POW);
+                // mu64 = [means | tv, scratch, 0 ...]: the total variance lands where the sums of squares would have
+                have_yp = op_power_pass_means(c.dev, dt, X.p, n, dp, d, X.ld, in.ri.n_total, P.f64(), LP, LP, L, Yp, LP, mu64, muT.p, mu64 + dp + 1, mu64 + dp);
+                dev_set_tag(c.dev, TAG_NONE);
+            }
+            if (have_yp) { means_done = true; tv_direct = true; }
+            else means_pass();
         }
-        op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Pcur, LP, Yp, LP, 0.0, G, LP);
-        // (a pivot lost here -- H is only symmetric / positive up to the fp32 rounding of Pcur and Z -- is recorded like the
-        // breakdowns of the power iterations: the fit is then redone on the robust Cholesky-QR2 path instead of silently
-        // dropping a component.  On the planted spectra the pivot ratios r_jj^2 / H_jj stay above 0.9: Pcur's columns come out
-        // of a Cholesky-QR ordered like the singular vectors, so Z's columns are nearly orthogonal.)
-        // (only a lost pivot among the first k columns touches an output component: exactly low-rank fp32 data, whose columns beyond
-        // the rank are dropped here with sigma = 0 -- the correct answer -- no longer pays for a second, robust fit)
-        // (the inverse of R is not needed explicitly either: B^T = Yp R^-1 and R^-1 Uh are triangular solves -- where the device has the
-        // kernels the factorisation is the register-resident one of the power iterations, 15 instead of 40 us at l = 74)
-        t_rt = slot_flip && op_chol_rt(c.dev, dt, n, G, L, LP, T.f64(), LP, tol_drop, ndead, LP, std::max<int64_t>(k, 1));
-        if (!slot_flip) op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_drop, ndead, LP, std::max<int64_t>(k, 1));
-        Usrc = Z.p; Ubuf = Z1.p;
-    } else {
-        // Cholesky-QR2: Z1 = Z T1, Q = Z1 T2 with T2 folded into the small side.  The Gram matrices of the tall side are formed
-        // with fp64 products (`precise`): Z = Xc Omega of a wide spectrum has cond(Z)^2 ~ 1e7 .. 1e8, and a Gram matrix from fp32
-        // products (good to 6e-8 of its norm) would have to DROP the weakest columns as noise -- n_iter = 0 on a planted 1e3
-        // spectrum then lost a column of the oversampling tail and came back 9e-3 off where the crate's f32 QR (linalg.rs:127-147)
-        // holds 5e-6; with exact products every pivot above the rounding of Z itself is kept.
+        if (!have_yp && use_pow && n_iter >= 3 && !a.rebase_now && tv_from_sq) {
+            dev_set_tag(c.dev, TAG_POW);
+            have_yp = op_power_pass(c.dev, dt, X.p, n, dp, X.ld, muT.p, P.f64(), LP, LP, nullptr, LP, Yp, LP, /*steering=*/true);   // pca.rs:707 + 711
+            dev_set_tag(c.dev, TAG_NONE);
+            if (have_yp) allreduce_f64(c, Yp, dp * LP, PETAL_SUM);
+        }
+        if (!have_yp) {
+            // Z = Xc . Omega (pca.rs:707); total_variance = sum Xc^2 (pca.rs:533) is fused into this product unless tv_from_sq
+            dev_set_tag(c.dev, TAG_XP);
+            // (with power iterations behind it the sketch matrix may be ANY matrix: the optimistic run lets the kernel round Omega to two
+            // bf16 planes -- five piece products; n_iter = 0 and the robust redo keep Omega as given)
+            op_gemm_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, P.f64(), LP, LP, nullptr, Z.p, LP, tv_from_sq ? nullptr : tvp, planes, steer);
+            dev_set_tag(c.dev, TAG_NONE);
+
+            // A SHORT iteration (n_iter 1 - 4) on fp32 data re-bases the sketch Z = Xc Omega on the tall side first, as the crate does
+            // with its first LU (pca.rs:709).  Every column of Z is dominated by sigma_1, so the un-rebased double product Xc^T (Xc Omega)
+            // carries direction j at (sigma_j / sigma_1)^2 of a column -- 1e-6 on the planted spectra -- under an fp32 accumulation that
+            // is good to 6e-8 of it: the block's weakest directions come back 6 % junk, and with only one or two products behind it the
+            // fit is off by 2e-4 where the crate's own f32 path holds 1e-5 (measured, EXPERIMENTS.md round 5).  With Z = Q R first, a
+            // column of Xc^T Q carries direction j at sigma_j / sigma_1.  Later products wash the junk out at the rate of the spectrum's
+            // gaps: at n_iter = 3 it was gone for k = 64 of 512 features (3e-6) but NOT for 87 ... 126 components (1.5e-4 ... 3.6e-4
+            // where the oracle run in float32 holds 1.4e-5 ... 8e-5: dev/fuzz_round6.py, round 6), so three iterations re-base too --
+            // only their first product pair: the later ones are fused / steering passes as for any n_iter >= 3.  FOUR iterations likewise: a later
+            // seed of the same sweep had 60000 x 1024, k = 93, n_iter = 4 at 1.07e-4 against the float32 oracle's 1.0e-5.  From five iterations
+            // on the two extra passes over Z are not spent (no miss of this kind in ~220 random cases at n_iter 5 / 7 with up to 127 components, 425 in all).
+        }
+        if (!(a.rebase_now && !a.robust)) return Z.p;
         op_gemm_atb(c.dev, dt, Z.p, LP, LP, nullptr, Z.p, LP, LP, nullptr, n, G, LP, /*precise=*/true);
         allreduce_f64(c, G, LP * LP, PETAL_SUM);
         op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_tall, nullptr, LP);
         op_gemm_xp(c.dev, dt, Z.p, n, LP, LP, nullptr, T.f64(), LP, LP, nullptr, Z1.p, LP, nullptr);
-        op_gemm_atb(c.dev, dt, Z1.p, LP, LP, nullptr, Z1.p, LP, LP, nullptr, n, G, LP, /*precise=*/true);
-        dev_set_tag(c.dev, TAG_ATB);
-        op_gemm_atb(c.dev, dt, X.p, X.ld, dp, muT.p, Z1.p, LP, LP, nullptr, n, Yp, LP);  // B^T = Xc^T Q (pca.rs:681)
-        dev_set_tag(c.dev, TAG_NONE);
-        allreduce_f64(c, G, LP * LP, PETAL_SUM);
-        allreduce_f64(c, Yp, dp * LP + 1, PETAL_SUM);
-        op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_tall, nullptr, LP);  // T2
-        Usrc = Z1.p; Ubuf = Z.p;
+        return Z1.p;
     }
-    if (t_rt) op_trsm_right(c.dev, Yp, dp, LP, T.f64(), LP, LP, Bt.f64(), LP);
-    else op_dgemm(c.dev, false, false, dp, LP, LP, 1.0, Yp, LP, T.f64(), LP, 0.0, Bt.f64(), LP);
-
-    };  // pipeline
-
+    // The power iterations (pca.rs:708-715): the fast re-base with the fused pass or op_rebase_xp, or the robust re-base.  Returns
+    // the orthonormal basis the current Z was formed with.
+    double* power_iterations(const Attempt& a, const void* Zfirst) {
+        double* Pcur = P.f64();
+        for (int64_t it = 0; it < n_iter; ++it) {
+            if (!have_yp) {
+                dev_set_tag(c.dev, TAG_ATB);
+                op_gemm_atb(c.dev, dt, X.p, X.ld, dp, muT.p, it == 0 ? Zfirst : Z.p, LP, LP, nullptr, n, Yp, LP, false, steer);  // Yp = Xc^T Z (pca.rs:711)
+                dev_set_tag(c.dev, TAG_NONE);
+                allreduce_f64(c, Yp, dp * LP, PETAL_SUM);
+            }
+            have_yp = false;
+            // Re-base the d x l iterate (stands for the two pivoted-LU re-basings of pca.rs:709-713).  The next product only
+            // needs SOME well-conditioned basis of range(Yp): P = Yp T spans range(Yp) exactly for any invertible
+            // triangular T, so the accuracy of T only decides how well-conditioned P is, never which subspace it spans (the
+            // final thin QR restores orthonormality).
+            if (!a.robust) {
+                // fast path: one fp64 Cholesky of Yp^T Yp, valid while every pivot stays positive (cond(Yp) <~ 3e7: errors
+                // of a few per cent in the weakest pivots merely leave cond(P) ~ 1.x); breakdowns are recorded in ndead.
+                // Y = Yp R^-1 is formed inside the next product's operand-packing kernel (op_rebase_xp), by substitution, not by a
+                // launch of its own; R^-1 itself is not needed during the iteration.
+                op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Yp, LP, Yp, LP, 0.0, G, LP);
+                if (use_pow) {   // re-base, then BOTH products of the next iteration in one pass (the last one keeps Z for U = Z (T Uh))
+                    const bool last = it + 1 == n_iter;
+                    dev_set_tag(c.dev, TAG_POW);
+                    have_yp = op_rebase_power_pass(c.dev, dt, X.p, n, dp, X.ld, muT.p, G, L, LP, 1e-15, ndead, Yp, LP, LP, T.f64(), LP, Y.f64(), LP,
+                                                   last ? Z.p : nullptr, LP, Yp, LP, /*steering=*/steer && !last);   // pca.rs:714 + 711
+                    // (steer: n_iter >= 3 -- the short iterations keep every pass at five / six piece products: ADVICE round 5)
+                    dev_set_tag(c.dev, TAG_NONE);
+                    if (have_yp) allreduce_f64(c, Yp, dp * LP + (last ? 1 : 0), PETAL_SUM);   // (the last one: [ Xc^T Z | sum Xc^2 ])
+                }
+                if (!have_yp) {
+                    dev_set_tag(c.dev, TAG_XP);   // (only the product kernel itself is bracketed)
+                    op_rebase_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, G, L, LP, 1e-15, ndead, Yp, LP, LP, T.f64(), LP, Y.f64(), LP, Z.p, LP, planes,
+                                 steer && it + 1 < n_iter);  // pca.rs:714 (the last iteration's Z is the iterate the results are made of: exact)
+                    dev_set_tag(c.dev, TAG_NONE);
+                }
+            } else {
+                // ill-conditioned iterate: precondition with the tall side first.  Z = Xc P gives Z^T Z = P^T (Xc^T Z) =
+                // P^T Yp without a pass over Z (op_chol_inv reads the upper triangle only); T = chol(Z^T Z)^-1 is applied on
+                // the small side, Xc^T (Z T) = Yp T, and the now moderately conditioned Yp T gets its own Cholesky-QR.
+                op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Pcur, LP, Yp, LP, 0.0, G, LP);
+                op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_drop, nullptr, LP);
+                op_dgemm(c.dev, false, false, dp, LP, LP, 1.0, Yp, LP, T.f64(), LP, 0.0, Y.f64(), LP);
+                // A column the dependence test dropped (its part of Z below ~1e-3 of the part already spanned: from a random start
+                // every column of Z = Xc Omega is dominated by sigma_1, so a spectrum wider than 1e3 loses its tail here) is
+                // refilled with the matching column of Omega instead of staying zero: orthogonalised against the kept columns
+                // below, the next product shows it the largest direction still missing, and the block regains its width within an
+                // iteration or two -- what the crate's pivoted LU (pca.rs:709-713) achieves by never letting the block lose
+                // rank.  Truly rank-deficient data keeps dropping the refilled columns, down to the final QR (sigma = 0).
+                op_refill_zero_cols(c.dev, Y.f64(), dp, L, LP, P.f64(), LP);
+                orthonormalize_small(c, Y, dp, L, LP, 1e-13);
+                dev_set_tag(c.dev, TAG_XP);
+                op_gemm_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, Y.f64(), LP, LP, nullptr, Z.p, LP, nullptr);  // pca.rs:714
+                dev_set_tag(c.dev, TAG_NONE);
+            }
+            Pcur = Y.f64();
+        }
+        return Pcur;
+    }
+    // thin QR of Z (pca.rs:716) and B = Q^T Xc (pca.rs:681): the one-pass RT / inverse form, or Cholesky-QR2.
+    void range_basis(const Attempt& a, const double* Pcur) {
+        t_rt = false;
+        steered = use_pow || steer;
+        if (n_iter > 0 && !a.robust) {
+            // ONE more pass over X serves both.  Z = Xc Pcur, so Z^T Z = Pcur^T (Xc^T Z) = Pcur^T Yp with Yp = Xc^T Z, the very
+            // product B needs: with H = Pcur^T Yp = R^T R and T = R^-1, Q = Z T and B = Q^T Xc = (Yp T)^T.  No pass over Z, no
+            // second Gram matrix.  Why one Cholesky suffices here although cond(Z)^2 ~ 1e7 exceeds fp32: Pcur is orthonormal and
+            // spans a nearly invariant subspace of Xc^T Xc, so the fp32 rounding of Pcur and Z perturbs Z^T Z MULTIPLICATIVELY,
+            // (I + E)^T H with ||E|| ~ 1e-8, and ||Q^T Q - I|| ~ ||E|| cond(R) ~ 1e-5 instead of eps cond(Z)^2 (measured 1e-6 ..
+            // 1e-5 up to cond(Z) = 2.5e4; the singular values match the two-pass Cholesky-QR2 form to its own accuracy).  Not so
+            // for a non-orthonormal Pcur (n_iter = 0: the raw Omega) and on the robust redo: those keep Cholesky-QR2 below.
+            if (!have_yp) {   // (the fused pass of the last iteration has formed this product already)
+                dev_set_tag(c.dev, TAG_ATB);
+                op_gemm_atb(c.dev, dt, X.p, X.ld, dp, muT.p, Z.p, LP, LP, nullptr, n, Yp, LP);
+                dev_set_tag(c.dev, TAG_NONE);
+                allreduce_f64(c, Yp, dp * LP + 1, PETAL_SUM);  // [ Xc^T Z | sum Xc^2 ]
+            }
+            op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Pcur, LP, Yp, LP, 0.0, G, LP);
+            // (a pivot lost here -- H is only symmetric / positive up to the fp32 rounding of Pcur and Z -- is recorded like the
+            // breakdowns of the power iterations: the fit is then redone on the robust Cholesky-QR2 path instead of silently
+            // dropping a component.  On the planted spectra the pivot ratios r_jj^2 / H_jj stay above 0.9: Pcur's columns come out
+            // of a Cholesky-QR ordered like the singular vectors, so Z's columns are nearly orthogonal.)
+            // (only a lost pivot among the first k columns touches an output component: exactly low-rank fp32 data, whose columns beyond
+            // the rank are dropped here with sigma = 0 -- the correct answer -- no longer pays for a second, robust fit)
+            // (the inverse of R is not needed explicitly either: B^T = Yp R^-1 and R^-1 Uh are triangular solves -- where the device has the
+            // kernels the factorisation is the register-resident one of the power iterations, 15 instead of 40 us at l = 74)
+            t_rt = slot_flip && op_chol_rt(c.dev, dt, n, G, L, LP, T.f64(), LP, tol_drop, ndead, LP, std::max<int64_t>(k, 1));
+            if (!slot_flip) op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_drop, ndead, LP, std::max<int64_t>(k, 1));
+            Usrc = Z.p; Ubuf = Z1.p;
+        } else {
+            // Cholesky-QR2: Z1 = Z T1, Q = Z1 T2 with T2 folded into the small side.  The Gram matrices of the tall side are formed
+            // with fp64 products (`precise`): Z = Xc Omega of a wide spectrum has cond(Z)^2 ~ 1e7 .. 1e8, and a Gram matrix from fp32
+            // products (good to 6e-8 of its norm) would have to DROP the weakest columns as noise -- n_iter = 0 on a planted 1e3
+            // spectrum then lost a column of the oversampling tail and came back 9e-3 off where the crate's f32 QR (linalg.rs:127-147)
+            // holds 5e-6; with exact products every pivot above the rounding of Z itself is kept.
+            op_gemm_atb(c.dev, dt, Z.p, LP, LP, nullptr, Z.p, LP, LP, nullptr, n, G, LP, /*precise=*/true);
+            allreduce_f64(c, G, LP * LP, PETAL_SUM);
+            op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_tall, nullptr, LP);
+            op_gemm_xp(c.dev, dt, Z.p, n, LP, LP, nullptr, T.f64(), LP, LP, nullptr, Z1.p, LP, nullptr);
+            op_gemm_atb(c.dev, dt, Z1.p, LP, LP, nullptr, Z1.p, LP, LP, nullptr, n, G, LP, /*precise=*/true);
+            dev_set_tag(c.dev, TAG_ATB);
+            op_gemm_atb(c.dev, dt, X.p, X.ld, dp, muT.p, Z1.p, LP, LP, nullptr, n, Yp, LP);  // B^T = Xc^T Q (pca.rs:681)
+            dev_set_tag(c.dev, TAG_NONE);
+            allreduce_f64(c, G, LP * LP, PETAL_SUM);
+            allreduce_f64(c, Yp, dp * LP + 1, PETAL_SUM);
+            op_chol_inv(c.dev, G, L, LP, T.f64(), LP, tol_tall, nullptr, LP);  // T2
+            Usrc = Z1.p; Ubuf = Z.p;
+        }
+        if (t_rt) op_trsm_right(c.dev, Yp, dp, LP, T.f64(), LP, LP, Bt.f64(), LP);
+        else op_dgemm(c.dev, false, false, dp, LP, LP, 1.0, Yp, LP, T.f64(), LP, 0.0, Bt.f64(), LP);
+    }
     // The small stage: economy SVD of B, the verdicts, the components, U and svd_flip's column scan.  It runs behind every pipeline
     // and ONCE MORE BY ITSELF (jacobi = true) when the only complaint about a run is the eigen-solver's: eigenvalues among the k
     // wanted ones too close, relative to ||B B^T||, for the two-stage solver's vectors.  Until round 6 that verdict shared a word with
@@ -822,66 +905,53 @@ void rpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, int64_t n_oversamp
     // centre (the mean direction 1.6e4 x the block's weakest singular value), k = 100, came back 6.7e-3 / 1.9e-3 / 5.0e-4 off the oracle at
     // n_iter 3 / 4 / 5 where this stage alone, repeated with the Jacobi solver on the same B, gives 2.0e-5 / 1.2e-4 / 3.0e-5
     // (dev/fuzz_round6.py, dev/r6_case_a.py).
-    auto small_stage = [&](bool robust, bool exact, bool jacobi) {
-    if (jacobi) dev_memset(c.dev, ndead, 0, 2 * sizeof(double));   // (the heavy-tail verdict is formed again from the new spectrum)
-    // economy SVD of B (l x d) (svddc, pca.rs:682): eigen-decomposition of B B^T in fp64
-    op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Bt.f64(), LP, Bt.f64(), LP, 0.0, S.f64(), LP);
-    // only the leading L x L block of S is non-zero (columns L..LP-1 of every iterate are exact zero padding)
-    // Optimistic run: the two-stage solver alone, its closeness verdict restricted to the k pairs that reach the outputs
-    // (the oversampling tail may cluster at the noise floor: its vectors only have to span it) and OR-ed into `ndead` -- a
-    // flagged spectrum (exact multiplicities among the wanted singular values) redoes the fit on the robust path, which
-    // solves with Jacobi.  Saves the two fallback launches that return at once on every separated spectrum.
-    if (!robust && !jacobi) op_eigh(c.dev, S.f64(), L, LP, Uh.f64(), LP, lam, dt == F32 ? 1e-8 : 1e-15, false, LP, std::max<int64_t>(k, 1), neig);
-    else op_eigh(c.dev, S.f64(), L, LP, Uh.f64(), LP, lam, dt == F32 ? 1e-8 : 1e-15, true, LP);  // (zero padding of Uh included)
-    // (the two-plane verdict, from the spectrum just found)
-    if (!robust && !exact && two_plane_applies)
-        op_tail_verdict(c.dev, lam, L, std::max<int64_t>(k, 1), (tv_from_sq && !tv_direct) ? mu64 : nullptr, dp, d, ri.n_total,
-                        tv_direct ? mu64 + dp : tvp, steered ? 4e-6 * 1.2 : 4e-6, p2_thr, ndead);   // (steering passes round Xc and z too: where the estimate
-                        // matters -- slowly decaying spectra -- that adds at most 16 % to what P's rounding costs: dev/x2_model.py)
-    // rows of V^T: v_j = B^T u_j / sigma_j, sigma_j = sqrt(lam_j) (the host takes the same square roots of lam)
-    op_components_out(c.dev, dt, Bt.f64(), LP, Uh.f64(), LP, lam, dt == F32 ? 1e-7 : 1e-12, d, L, k, comp_dev);
+    void small_stage(const Attempt& a) {
+        if (a.jacobi) dev_memset(c.dev, ndead, 0, 2 * sizeof(double));   // (the heavy-tail verdict is formed again from the new spectrum)
+        // economy SVD of B (l x d) (svddc, pca.rs:682): eigen-decomposition of B B^T in fp64
+        op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Bt.f64(), LP, Bt.f64(), LP, 0.0, S.f64(), LP);
+        // only the leading L x L block of S is non-zero (columns L..LP-1 of every iterate are exact zero padding)
+        // Optimistic run: the two-stage solver alone, its closeness verdict restricted to the k pairs that reach the outputs
+        // (the oversampling tail may cluster at the noise floor: its vectors only have to span it) and OR-ed into `ndead` -- a
+        // flagged spectrum (exact multiplicities among the wanted singular values) redoes the fit on the robust path, which
+        // solves with Jacobi.  Saves the two fallback launches that return at once on every separated spectrum.
+        if (!a.robust && !a.jacobi) op_eigh(c.dev, S.f64(), L, LP, Uh.f64(), LP, lam, dt == F32 ? 1e-8 : 1e-15, false, LP, std::max<int64_t>(k, 1), neig);
+        else op_eigh(c.dev, S.f64(), L, LP, Uh.f64(), LP, lam, dt == F32 ? 1e-8 : 1e-15, true, LP);  // (zero padding of Uh included)
+        // (the two-plane verdict, from the spectrum just found)
+        if (!a.robust && !a.exact && two_plane_applies)
+            op_tail_verdict(c.dev, lam, L, std::max<int64_t>(k, 1), (tv_from_sq && !tv_direct) ? mu64 : nullptr, dp, d, in.ri.n_total,
+                            tv_direct ? mu64 + dp : tvp, steered ? 4e-6 * 1.2 : 4e-6, p2_thr, ndead);   // (steering passes round Xc and z too: where the estimate
+                            // matters -- slowly decaying spectra -- that adds at most 16 % to what P's rounding costs: dev/x2_model.py)
+        // rows of V^T: v_j = B^T u_j / sigma_j, sigma_j = sqrt(lam_j) (the host takes the same square roots of lam)
+        op_components_out(c.dev, dt, Bt.f64(), LP, Uh.f64(), LP, lam, dt == F32 ? 1e-7 : 1e-12, d, L, k, comp_dev);
 
-    // U = Q Uh = Usrc (T Uh) (pca.rs:683) and svd_flip (pca.rs:684)
-    // (only the k columns svd_flip signs and fit_transform returns: kp = k rounded up to whole 16-column tiles; the small
-    // product T Uh is formed by the operand-packing kernel of the n x l product)
-    dev_set_tag(c.dev, TAG_STREAM);
-    if (slot_flip)   // ... and svd_flip's column scan by its epilogue
-        op_gemm_xp_prod_absmax(c.dev, dt, Usrc, n, LP, LP, nullptr, T.f64(), LP, LP, Uh.f64(), kp, LP, M2.f64(), LP, Ubuf, LP,
-                               ri.row_offset, flip, flip + kp, flip + 2 * kp, /*store_product=*/y_out != nullptr, /*a_rt=*/t_rt);
-    else
-        op_gemm_xp_prod(c.dev, dt, Usrc, n, LP, LP, nullptr, T.f64(), LP, LP, Uh.f64(), kp, LP, M2.f64(), LP, Ubuf, LP);
-    dev_set_tag(c.dev, TAG_NONE);
-    Uout = Ubuf;
-    };  // small_stage
-
+        // U = Q Uh = Usrc (T Uh) (pca.rs:683) and svd_flip (pca.rs:684)
+        // (only the k columns svd_flip signs and fit_transform returns: kp = k rounded up to whole 16-column tiles; the small
+        // product T Uh is formed by the operand-packing kernel of the n x l product)
+        dev_set_tag(c.dev, TAG_STREAM);
+        if (slot_flip)   // ... and svd_flip's column scan by its epilogue
+            op_gemm_xp_prod_absmax(c.dev, dt, Usrc, n, LP, LP, nullptr, T.f64(), LP, LP, Uh.f64(), kp, LP, M2.f64(), LP, Ubuf, LP,
+                                   in.ri.row_offset, flip, flip + kp, flip + 2 * kp, /*store_product=*/y_out != nullptr, /*a_rt=*/t_rt);
+        else
+            op_gemm_xp_prod(c.dev, dt, Usrc, n, LP, LP, nullptr, T.f64(), LP, LP, Uh.f64(), kp, LP, M2.f64(), LP, Ubuf, LP);
+        dev_set_tag(c.dev, TAG_NONE);
+        Uout = Ubuf;
+    }
     // results (pca.rs:543-547): ONE small copy queued behind the pipeline, ONE synchronisation; the host reads it where it
     // lands (the pinned ring) and writes the caller's arrays in one pass, svd_flip's sign applied on the way
-    const size_t hres_len = size_t(res_len - o_tv);
-    const double* hres = nullptr;
-    const void* hcomp = nullptr;
-    std::vector<double> sg, keep;
-    std::vector<char> comp_keep;
-    double t_q = 0, t_s = 0;
-    const bool never_p2 = dev_option(c.dev, OPT_TWO_PLANE) == 0;
-    bool robust = false, exact = !two_plane_applies || never_p2;
-    bool jacobi = false;   // the small stage alone is being repeated with the Jacobi eigen-solver
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        if (!jacobi) pipeline(robust, exact);
-        small_stage(robust, exact, jacobi);
-        if (slot_flip) flip_signs_to_slot(c, dt, Uout, n, kp, LP, ri.row_offset, flip, true, !robust ? ndead : nullptr);
+    void read_back(const Attempt& a) {
+        if (slot_flip) flip_signs_to_slot(c, dt, kp, flip, !a.robust ? ndead : nullptr);
+        const size_t hres_len = size_t(o.len - o.tv);
         // (one view for both while they fit a ring slot; large components -- k = 128 at d = 16384, k = 512 at d = 4096 -- leave by a
         // plain copy of their own and only the small block is viewed: ADVICE round 4)
         const bool one_view = sizeof(double) * hres_len + comp_bytes <= dev_view_limit(c.dev);
-        hres = static_cast<const double*>(dev_d2h_view(c.dev, tvp, sizeof(double) * hres_len + (one_view ? comp_bytes : 0)));
+        const double* hres = static_cast<const double*>(dev_d2h_view(c.dev, tvp, sizeof(double) * hres_len + (one_view ? comp_bytes : 0)));
         hcomp = hres + hres_len;
         if (!one_view) {
             comp_keep.resize(comp_bytes);
             dev_d2h(c.dev, comp_keep.data(), comp_dev, comp_bytes);
             hcomp = comp_keep.data();
         }
-        t_q = timer.ms();
         dev_sync(c.dev);
-        t_s = timer.ms();
         // (the sharded fp64 path queues more copies through the ring below -- agree_any(), flip_signs(): it takes everything out
         // first; the small block is copied on every path)
         keep.assign(hres, hres + hres_len);
@@ -889,82 +959,78 @@ void rpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, int64_t n_oversamp
             comp_keep.assign(static_cast<const char*>(hcomp), static_cast<const char*>(hcomp) + comp_bytes);
             hcomp = comp_keep.data();
         }
-        if (robust) break;
-        // the verdict words: [0] pivot breakdowns -> the robust path; [1] a heavy tail behind the block -> the same pipeline with
-        // three-plane operands; [2] a cluster among the wanted eigenvalues -> the small stage again with the Jacobi solver (the passes
-        // over X stand).  Sharded fits branch on the MAX over the ranks.
+    }
+    const double* host(int64_t offset) const { return &keep[size_t(offset - o.tv)]; }   // the host copy of the block's word `offset`
+    // the verdict words' code (verdict_code); sharded fits branch on the MAX over the ranks: the agreed verdict
+    double verdict() {
         int hdead[3] = {0, 0, 0};
-        std::memcpy(hdead, &keep[o_dead - o_tv], sizeof(hdead));
-        double code = hdead[0] != 0 ? 3.0 : (hdead[1] != 0 ? 1.0 : (hdead[2] != 0 ? 2.0 : 0.0));
-        if (sharded(c)) code = flip_slot_keys(c, dt) ? keep[o_flip - o_tv + 4 * kp] : agree_max(c, code);  // the agreed verdict
-        if (code >= 3.0 && !rebase_now && n_iter >= 1) {
-            // A lost pivot is, on full-rank data, the FIRST product pair's: from a random start every column of Xc^T (Xc Omega)
-            // is dominated by sigma_1, and beyond sigma_1 / sigma_l ~ 5e3 its Gram matrix is singular to fp64 (uncentred data far off
-            // centre: the mean direction is sigma_1).  The robust path would answer with a different iteration (dependent columns dropped
-            // and refilled): 1.9e-3 / 5e-4 off the oracle at n_iter 4 / 5 on such data, where the same pipeline with the sketch re-based
-            // on the tall side first -- what short iterations do anyway, and the crate's first LU -- holds 1e-4 / 3e-5.  So that is
-            // tried first; rank-deficient data loses its pivot again and takes the robust path one run later.  (fp64 data too: its first pair
-            // breaks down beyond sigma_1 / sigma_l ~ 5e3 all the same -- (sigma_1 / sigma_l)^4 against 1e-15 -- while the re-based sketch's
-            // tall-side Gram matrix holds to ~3e6; uncentred fp64 data 300 sigma off centre came back 1e-5 ... 1e-7 off at n_iter 1 - 3 on the
-            // robust path: dev/fuzz_hostsim6.py)
-            rebase_now = true; jacobi = false; c.stats.rpca_redo = 3;
-            continue;
+        std::memcpy(hdead, host(o.verdict), sizeof(hdead));
+        double code = verdict_code(hdead);
+        if (sharded(c)) code = flip_slot_keys(c, dt) ? *host(o.agreed) : agree_max(c, code);
+        return code;
+    }
+    // The last attempt's results to the caller: svd_flip's signs, the singular values, means and total variance.
+    void write_out(const PcaOutputs& out) {
+        const std::vector<double> sg = slot_flip ? signs_from_slot(c, dt, host(o.flip), kp)
+                                                 : flip_signs(c, dt, Uout, n, kp, LP, in.ri.row_offset);   // (sharded fp64: three more dependent rounds)
+        const double* hlam = host(o.lam);
+        std::vector<double> hs(size_t(std::max<int64_t>(k, 1)), 0.0);
+        for (int64_t j = 0; j < k; ++j) hs[j] = std::sqrt(std::max(hlam[j], 0.0));
+        const double* hmu = host(o.mu);
+        double htv = keep[0];
+        if (tv_direct) htv = hmu[dp];   // (the means were gathered inside the first fused pass: the variance came with them)
+        else if (tv_from_sq) {  // sum (x - mu)^2 = sum x^2 - n mu^2 per column, in fp64
+            htv = 0;
+            for (int64_t j = 0; j < d; ++j) htv += std::max(0.0, hmu[dp + j] - in.ri.n_total * hmu[j] * hmu[j]);
         }
-        if (code >= 3.0) { robust = true; exact = true; jacobi = false; c.stats.rpca_redo = 2; continue; }
-        if (code == 1.0 && !exact) { exact = true; jacobi = false; c.stats.rpca_redo = 1; continue; }
-        if (code == 2.0 && !jacobi) { jacobi = true; c.stats.eigh_redo = 1; continue; }
-        break;
-    }
-    if (slot_flip) {
-        const double* hf = &keep[o_flip - o_tv];
-        sg = flip_slot_keys(c, dt) ? signs_from_triple(std::vector<double>(hf + 3 * kp, hf + 4 * kp), kp)
-                                   : signs_from_triple(std::vector<double>(hf, hf + 3 * kp), kp);
-    }
-    if (!slot_flip) sg = flip_signs(c, dt, Uout, n, kp, LP, ri.row_offset);   // (sharded fp64: three more dependent rounds)
-    const double* hlam = &keep[o_lam - o_tv];
-    std::vector<double> hs(size_t(std::max<int64_t>(k, 1)), 0.0);
-    for (int64_t j = 0; j < k; ++j) hs[j] = std::sqrt(std::max(hlam[j], 0.0));
-    const double* hmu = &keep[o_mu - o_tv];
-    double htv = keep[0];
-    if (tv_direct) htv = hmu[dp];   // (the means were gathered inside the first fused pass: the variance came with them)
-    else if (tv_from_sq) {  // sum (x - mu)^2 = sum x^2 - n mu^2 per column, in fp64
-        htv = 0;
-        for (int64_t j = 0; j < d; ++j) htv += std::max(0.0, hmu[dp + j] - ri.n_total * hmu[j] * hmu[j]);
-    }
-    {   // non-finite input: the crate's gesdd reports info != 0 -> "did not converge" (linalg.rs:115).  Checked on what came back anyway --
-        // means, sums of squares, the spectrum: replicated values, so every rank of a sharded fit raises -- and on the RAW values (the
-        // max(., 0) clamps above turn a NaN into a zero)
-        bool finite = std::isfinite(keep[0]) && std::isfinite(htv);
-        for (int64_t j = 0; j < d; ++j) finite = finite && std::isfinite(hmu[j]) && (!tv_from_sq || tv_direct || std::isfinite(hmu[dp + j]));
-        for (int64_t j = 0; j < k; ++j) finite = finite && std::isfinite(hlam[j]);
-        if (!finite) linalg_error("did not converge");
-    }
-    for (int64_t j = 0; j < k; ++j) {   // the components leave the ring with svd_flip's sign on row j (pca.rs:684)
-        if (dt == F32) {
-            const float* src = static_cast<const float*>(hcomp) + j * d;
-            float* r = static_cast<float*>(components) + j * d;
-            if (sg[j] < 0) for (int64_t i = 0; i < d; ++i) r[i] = -src[i];
-            else std::memcpy(r, src, sizeof(float) * size_t(d));
-        } else {
-            const double* src = static_cast<const double*>(hcomp) + j * d;
-            double* r = static_cast<double*>(components) + j * d;
-            if (sg[j] < 0) for (int64_t i = 0; i < d; ++i) r[i] = -src[i];
-            else std::memcpy(r, src, sizeof(double) * size_t(d));
+        {   // non-finite input: the crate's gesdd reports info != 0 -> "did not converge" (linalg.rs:115).  Checked on what came back anyway --
+            // means, sums of squares, the spectrum: replicated values, so every rank of a sharded fit raises -- and on the RAW values (the
+            // max(., 0) clamps above turn a NaN into a zero)
+            bool finite = std::isfinite(keep[0]) && std::isfinite(htv);
+            for (int64_t j = 0; j < d; ++j) finite = finite && std::isfinite(hmu[j]) && (!tv_from_sq || tv_direct || std::isfinite(hmu[dp + j]));
+            for (int64_t j = 0; j < k; ++j) finite = finite && std::isfinite(hlam[j]);
+            if (!finite) linalg_error("did not converge");
         }
-        put_elem(singular, dt, j, hs[j]);
+        write_pca_outputs(c, out, dt, k, d, hcomp, sg.data(), hs.data(), hmu, htv, Uout, n, LP);
     }
-    if (dt == F32) { float* m = static_cast<float*>(means); for (int64_t i = 0; i < d; ++i) m[i] = float(hmu[i]); }
-    else std::memcpy(means, hmu, sizeof(double) * size_t(d));
-    put_elem(total_variance, dt, 0, htv);
-    if (y_out) {  // fit_transform: U[:, :k] * sigma (transform_with_u, pca.rs:758-779)
-        std::vector<double> sc(LP, 0.0);
-        for (int64_t j = 0; j < k; ++j) sc[j] = sg[j] * hs[j];
-        DBuf dsc(c.dev, sizeof(double) * LP);
-        dev_h2d(c.dev, dsc.p, sc.data(), dsc.bytes);
-        emit(c, dt, Uout, n, k, LP, *y_out, dsc.f64());
+};
+
+}  // namespace
+
+void rpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, int64_t n_oversample, int64_t n_iter, bool centering,
+              const void* omega, void* components, void* means, void* singular, void* total_variance,
+              const petal_matrix* y_out) {
+    const Timer timer = start_fit(c, x);
+    if (k < 0 || n_oversample < 0 || n_iter < 0) invalid_input("negative parameter");
+    const int dt = x.dtype;
+    const int64_t d = x.cols, l_req = k + n_oversample;
+    // (argument errors that every rank sees alike are raised BEFORE the collective, so no rank is left waiting in it)
+    if (sharded(c) && d > 0 && l_req > 0 && omega == nullptr) invalid_input("omega is required");
+    FitInput in = fit_input(c, x, !centering ? 0 : dt == F32 ? 2 : 1, omega, d * l_req);   // (fp32: with the sums of squares, RpcaRun::tv_from_sq)
+    if (in.n_total < k || d < k) invalid_input("every dimension should be at least " + std::to_string(k));  // pca.rs:513-518
+    if (centering && in.n_total == 0) {  // mean_axis -> None (pca.rs:521-525): Ok, model untouched
+        if (y_out && (y_out->rows != 0)) invalid_input("output has the wrong shape");
+        return;
     }
-    (void)t_q; (void)t_s;
-    c.stats.means_folded = tv_direct ? 1 : 0;
+    const int64_t L = std::min(l_req, std::min(in.n_total, d));  // the reference's min(nrows, ncols) slices, pca.rs:710/713
+    if (L > 0 && omega == nullptr) invalid_input("omega is required");
+    if (d == 0 || L == 0) {  // nothing to decompose: k == 0 here
+        if (total_variance) put_elem(total_variance, dt, 0, 0.0);
+        if (y_out) emit(c, dt, nullptr, x.rows, 0, 0, *y_out);
+        return;
+    }
+    if (!sharded(c)) in.X = ingest(c, x);
+    RpcaRun run(c, in, y_out, k, l_req, n_iter, L, centering, omega);
+    Attempt a{false, !run.two_plane_applies || dev_option(c.dev, OPT_TWO_PLANE) == 0, false, run.rebase_sketch};
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        if (!a.jacobi) run.pipeline(a);
+        run.small_stage(a);
+        run.read_back(a);
+        // (a robust run is final: its verdict is not formed -- on a sharded fp64 fit that takes a collective)
+        if (!next_attempt(a, a.robust ? 0.0 : run.verdict(), n_iter, c.stats)) break;
+    }
+    run.write_out({components, means, singular, total_variance, y_out});
+    c.stats.means_folded = run.tv_direct ? 1 : 0;
     finish_stats(c, timer);
 }
 
@@ -974,24 +1040,12 @@ void rpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, int64_t n_oversamp
 // so the thin factorisation is computed: eigen-decomposition of the d x d Gram matrix in fp64.
 void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, void* components, void* means,
              void* singular, void* total_variance, const petal_matrix* y_out) {
-    Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
-    check_matrix(x, "input");
+    const Timer timer = start_fit(c, x);
     if (k < 0) invalid_input("negative parameter");
     const int dt = x.dtype;
     const int64_t d = x.cols;
-    DevMat X;
-    ShardPrologue pro;
-    RankInfo ri;
-    if (sharded(c)) {
-        X = ingest(c, x);
-        pro = shard_prologue(c, X, centering ? X.dp : 0, false, dt, nullptr, 0);
-        ri = pro.ri;
-    } else {
-        ri.n_total = double(x.rows);
-    }
-    const int64_t n_total = int64_t(ri.n_total);
+    FitInput in = fit_input(c, x, centering ? 1 : 0, nullptr, 0);
+    const int64_t n_total = in.n_total;
     if (n_total < k || d < k) invalid_input("every dimension should be at least " + std::to_string(k));  // pca.rs:199-204
     if (centering && n_total == 0) return;  // pca.rs:207-211
     if (d == 0 || n_total == 0) {
@@ -999,11 +1053,12 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
         if (y_out) emit(c, dt, nullptr, x.rows, 0, 0, *y_out);
         return;
     }
-    if (!sharded(c)) X = ingest(c, x);
+    if (!sharded(c)) in.X = ingest(c, x);
+    const DevMat& X = in.X;
     const int64_t n = X.n, dp = X.dp;
     const size_t esz = dtype_size(dt);
     DBuf mu64, muT;
-    column_means(c, X, ri.n_total, centering, mu64, muT, false, sharded(c) && centering ? pro.sums : nullptr);
+    column_means(c, X, in.ri.n_total, centering, mu64, muT, false, sharded(c) && centering ? in.pro.sums : nullptr);
 
     DBuf C(c.dev, sizeof(double) * dp * dp), V(c.dev, sizeof(double) * dp * dp), lam(c.dev, sizeof(double) * dp);
     DBuf sig(c.dev, sizeof(double) * dp), inv(c.dev, sizeof(double) * dp), diag(c.dev, sizeof(double) * dp), r3(c.dev, sizeof(double) * 3);
@@ -1025,10 +1080,8 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
     dev_memset(c.dev, V.p, 0, V.bytes);
     dev_memset(c.dev, lam.p, 0, lam.bytes);
     // only the top-k pairs reach the outputs (components, singular values, the k columns of U that svd_flip signs)
-    DBuf Ckeep;  // (the eigen-solvers may destroy their input; the accurate route of fp64 fits factors the Gram matrix again)
-    if (dt == F64) { Ckeep = DBuf(c.dev, C.bytes); dev_d2d(c.dev, Ckeep.p, C.p, C.bytes); }
-    const double vtol = dt == F32 ? 1e-12 : 3e-14;
-    const bool partial = topk_eigh(c, C.f64(), d, dp, k, V.f64(), lam.f64(), dt == F32 ? 1e-8 : 1e-5, optimistic ? r3.f64() : nullptr, vtol);
+    const GramEigen g = gram_topk_eigh(c, dt, C, d, dp, k, V.f64(), lam.f64(), optimistic ? r3.f64() : nullptr);
+    const bool partial = g.topk;
     // (order d, not the padded dp: the zero padding would only add dp - d exact zero eigenvalues, a cluster that sends the
     // two-stage solver to its Jacobi fallback; V and lam beyond d stay at the zeros set above)
     // (... and the closeness verdict of the two-stage solver covers the k pairs that reach the outputs: the noise-floor
@@ -1041,15 +1094,8 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
     // with the results -- a fit that does need the route, rare, is run again with the check in place; every fp64 fit used to pay
     // a host round trip in the middle of its queue for it)
     bool accurate = false;
-    if (dt == F64 && k > 0 && route_check) {
-        std::vector<double> hl(k);
-        dev_d2h(c.dev, hl.data(), lam.p, sizeof(double) * k);
-        dev_sync(c.dev);
-        // (lam[k-1] <= 0 or fewer samples than features: rank-deficient, the accurate route's Cholesky would only break down --
-        // after allocating a second copy of X and two more passes)
-        const bool low = hl[0] > 0 && hl[k - 1] > 0 && n_total >= d && std::sqrt(hl[k - 1] / hl[0]) < GRAM_ROUTE_FLOOR;
-        if (agree_any(c, low)) accurate = accurate_small_svd(c, X, muT.p, Ckeep.f64(), d, V.f64(), sig.f64());
-    }
+    if (dt == F64 && k > 0 && route_check && lam_below_gram_floor(c, lam.f64(), k, n_total, d))
+        accurate = accurate_small_svd(c, X, muT.p, g.Ckeep.f64(), d, V.f64(), sig.f64());
     if (!accurate) op_sigma_inv(c.dev, lam.f64(), sig.f64(), inv.f64(), dp, dt == F32 ? 1e-6 : 1e-10);
     else op_dvec(c.dev, 1, sig.f64(), inv.f64(), dp, dt == F32 ? 1e-6 : 1e-10);
 
@@ -1064,13 +1110,13 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
         // pca.rs:223: svd_flip's scan comes out of the product kernel's accumulators (no second pass over U; U itself is only
         // stored for fit_transform); decision data queued, decoded below
         fslot = DBuf(c.dev, sizeof(double) * (4 * rp + 1));
-        op_gemm_xp_absmax(c.dev, dt, X.p, n, dp, X.ld, muT.p, Pm.f64(), rp, rp, U.p, rp, ri.row_offset, fslot.f64(), fslot.f64() + rp,
+        op_gemm_xp_absmax(c.dev, dt, X.p, n, dp, X.ld, muT.p, Pm.f64(), rp, rp, U.p, rp, in.ri.row_offset, fslot.f64(), fslot.f64() + rp,
                           fslot.f64() + 2 * rp, /*store_product=*/y_out != nullptr);
-        flip_signs_to_slot(c, dt, U.p, n, rp, rp, ri.row_offset, fslot.f64(), true);
+        flip_signs_to_slot(c, dt, rp, fslot.f64());
         deferred.assign(size_t(4 * rp), 0.0);   // (leaves with the other results below)
     } else {
         op_gemm_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, Pm.f64(), rp, rp, nullptr, U.p, rp, nullptr);
-        sg = flip_signs(c, dt, U.p, n, r, rp, ri.row_offset);
+        sg = flip_signs(c, dt, U.p, n, r, rp, in.ri.row_offset);
     }
     op_transpose_out(c.dev, dt, V.f64(), dp, d, k, compd.p);
 
@@ -1083,37 +1129,19 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
         dev_d2h_multi(c.dev, 6, dsts, srcs, lens);
     }
     dev_sync(c.dev);
-    return !(partial && optimistic) || topk_verdict_ok(h3, vtol);
+    return !(partial && optimistic) || topk_verdict_ok(h3, g.vtol);
     };  // pipeline
     pipeline(false, false);
-    if (dt == F64 && k > 0) {
-        const bool low = hs[0] > 0 && hs[k - 1] > 0 && n_total >= d && hs[k - 1] / hs[0] < GRAM_ROUTE_FLOOR;
-        if (agree_any(c, low)) pipeline(false, true);
-    }
-    if (slot_flip)   // (sharded fp32: the all-reduced keys behind the triple; else the triple itself)
-        sg = flip_slot_keys(c, dt) ? signs_from_triple(std::vector<double>(deferred.begin() + 3 * rp, deferred.begin() + 4 * rp), rp)
-                                   : signs_from_triple(std::vector<double>(deferred.begin(), deferred.begin() + 3 * rp), rp);
+    if (dt == F64 && k > 0 && agree_any(c, below_gram_floor(hs[0], hs[k - 1], hs[k - 1] / hs[0], n_total, d))) pipeline(false, true);
+    if (slot_flip) sg = signs_from_slot(c, dt, deferred.data(), rp);
     double tvar = 0;
     for (int64_t j = 0; j < d; ++j) tvar += hdiag[j];
     // (non-finite input: the crate's gesvd comes back with info != 0 -> "did not converge", linalg.rs:84; the trace is replicated,
     // so every rank of a sharded fit raises)
     if (!std::isfinite(tvar)) linalg_error("did not converge");
-    for (int64_t j = 0; j < k; ++j) {   // svd_flip's sign on row j of the components (already in place)
-        if (sg[j] < 0) {
-            if (dt == F32) { float* row = static_cast<float*>(components) + j * d; for (int64_t i = 0; i < d; ++i) row[i] = -row[i]; }
-            else { double* row = static_cast<double*>(components) + j * d; for (int64_t i = 0; i < d; ++i) row[i] = -row[i]; }
-        }
-        put_elem(singular, dt, j, hs[j]);
-    }
-    for (int64_t i = 0; i < d; ++i) put_elem(means, dt, i, hmu[i]);
-    put_elem(total_variance, dt, 0, tvar);
-    if (y_out) {
-        std::vector<double> sc(rp, 0.0);
-        for (int64_t j = 0; j < k; ++j) sc[j] = sg[j] * hs[j];
-        DBuf dsc(c.dev, sizeof(double) * rp);
-        dev_h2d(c.dev, dsc.p, sc.data(), dsc.bytes);
-        emit(c, dt, U.p, n, k, rp, *y_out, dsc.f64());
-    }
+    // (the components are already in place: svd_flip's sign is applied there)
+    write_pca_outputs(c, {components, means, singular, total_variance, y_out}, dt, k, d, components, sg.data(), hs.data(), hmu.data(), tvar,
+                      U.p, n, rp);
     finish_stats(c, timer);
 }
 
@@ -1247,7 +1275,6 @@ int64_t ica_loop(petal_ctx& c, int dt, const void* X1T, int64_t n, int64_t nc, i
         hp[0] = 0; hp[1] = 0;
         auto t_progress = std::chrono::steady_clock::now();  // when the device last reported a finished iteration
         int last_seen = 0;
-        bool synced = false;
         int64_t it = 0;
         for (; it < max_iter && !hp[0]; ++it) {
             int spins = 0;
@@ -1256,7 +1283,7 @@ int64_t ica_loop(petal_ctx& c, int dt, const void* X1T, int64_t n, int64_t nc, i
                 const auto now = std::chrono::steady_clock::now();
                 if (hp[1] != last_seen) { last_seen = hp[1]; t_progress = now; }
                 // a device that stopped reporting for 30 s (not: a fit that has been running for 30 s): blocking wait
-                if (std::chrono::duration<double>(now - t_progress).count() > 30.0) { dev_sync(c.dev); t_progress = now; synced = true; break; }
+                if (std::chrono::duration<double>(now - t_progress).count() > 30.0) { dev_sync(c.dev); t_progress = now; break; }
             }
             if (hp[0]) break;
             enqueue(it, const_cast<int*>(hp));
@@ -1264,7 +1291,6 @@ int64_t ica_loop(petal_ctx& c, int dt, const void* X1T, int64_t n, int64_t nc, i
         if (hp[0]) {
             n_iter = hp[0];                       // converged: the tail kernel published the iteration it stopped at
         } else {                                  // ran to max_iter (or the progress words failed): the device state decides
-            (void)synced;
             dev_d2h(c.dev, hstate, state.p, sizeof(hstate));
             dev_sync(c.dev);
             n_iter = hstate[0] ? hstate[1] : max_iter;
@@ -1298,34 +1324,23 @@ void check_finite_w(const std::vector<double>& w) {
 // FastIca::inner_fit (ica.rs:167-221)
 void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, double tol, int64_t max_iter, int mode,
                  const void* w_init, void* components, void* means, int64_t* n_iter, const petal_matrix* y_out) {
-    Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
-    check_matrix(x, "input");
+    const Timer timer = start_fit(c, x);
     const int dt = x.dtype;
     const int64_t d = x.cols;
     if (n_iter) *n_iter = 0;
-    DevMat X;
-    ShardPrologue pro;
-    RankInfo ri;
     // sharded: the caller sizes w_init before the row counts are known -- n_components, or the number of features
     const int64_t nc_draw = n_components > 0 ? n_components : d;
-    if (sharded(c)) {
-        if (d > 0 && w_init == nullptr) invalid_input("w_init is required");  // (before the collective: every rank alike)
-        X = ingest(c, x);
-        pro = shard_prologue(c, X, X.dp, false, dt, w_init, nc_draw * nc_draw);
-        ri = pro.ri;
-    } else {
-        ri.n_total = double(x.rows);
-    }
-    const int64_t n_total = int64_t(ri.n_total);
+    if (sharded(c) && d > 0 && w_init == nullptr) invalid_input("w_init is required");  // (before the collective: every rank alike)
+    FitInput in = fit_input(c, x, 1, w_init, nc_draw * nc_draw);
+    const int64_t n_total = in.n_total;
     if (n_total == 0) return;  // ica.rs:174-176
     int64_t nc = n_components > 0 ? n_components : std::min(n_total, d);  // ica.rs:173
     if (nc > std::min(n_total, d)) invalid_input("n_components should be at most min(n_samples, n_features)");
     if (nc == 0 || d == 0) return;
     if (w_init == nullptr) invalid_input("w_init is required");
     if (sharded(c) && nc != nc_draw) invalid_input("a sharded fit with fewer samples than features needs n_components");
-    if (!sharded(c)) X = ingest(c, x);
+    if (!sharded(c)) in.X = ingest(c, x);
+    const DevMat& X = in.X;
     const int64_t n = X.n, dp = X.dp, ncp = round_up(nc, 16);
     const size_t esz = dtype_size(dt);
     DBuf mu64, muT;
@@ -1336,7 +1351,7 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
     const bool fold_means = !sharded(c) && dt == F32 && dp >= 256 && dev_gemm_mode(c.dev) != 1;
     bool means_done = false;
     auto means_pass = [&] {
-        column_means(c, X, ri.n_total, true, mu64, muT, false, sharded(c) ? pro.sums : nullptr);
+        column_means(c, X, in.ri.n_total, true, mu64, muT, false, sharded(c) ? in.pro.sums : nullptr);
         means_done = true;
     };
     if (!fold_means) means_pass();
@@ -1358,7 +1373,7 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
         if (!means_done) {   // (fold_means: the first run of the pipeline)
             mu64 = DBuf(c.dev, sizeof(double) * dp);
             muT = DBuf(c.dev, esz * dp);
-            gram_fast = optimistic && op_gram_split(c.dev, X.p, n, d, dp, X.ld, muT.p, C.f64(), dp, mu64.f64(), ri.n_total);
+            gram_fast = optimistic && op_gram_split(c.dev, X.p, n, d, dp, X.ld, muT.p, C.f64(), dp, mu64.f64(), in.ri.n_total);
             if (gram_fast) means_done = true;
             else means_pass();
         } else {
@@ -1372,7 +1387,7 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
         dev_fork(c.dev, false);   // (nothing of the main stream's queue is needed: the prologue's draw was synchronised with)
         DBuf W(c.dev, sizeof(double) * nc * nc);   // (allocated while forked: a block no main-stream kernel can still be using)
         if (sharded(c)) {  // rank 0's draw, from the prologue's all-reduce
-            dev_d2d(c.dev, W.p, pro.draw, W.bytes);
+            dev_d2d(c.dev, W.p, in.pro.draw, W.bytes);
         } else {
             std::vector<double> h(size_t(nc) * nc);
             for (int64_t i = 0; i < nc * nc; ++i) h[i] = get_elem(w_init, dt, i);
@@ -1380,32 +1395,24 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
         }
         IcaStart start = ica_prepare(c, nc, W, mode);
         dev_fork_end(c.dev);
-        DBuf Ckeep;  // (see pca_fit)
-        if (dt == F64) { Ckeep = DBuf(c.dev, C.bytes); dev_d2d(c.dev, Ckeep.p, C.p, C.bytes); }
-        const double vtol = dt == F32 ? 1e-12 : 3e-14;
-        const bool topk = topk_eigh(c, C.f64(), d, dp, nc, U.f64(), lam.f64(), dt == F32 ? 1e-8 : 1e-5, optimistic ? r3.f64() : nullptr, vtol);  // only the first nc pairs are used below
-        if (!topk) {
+        const GramEigen g = gram_topk_eigh(c, dt, C, d, dp, nc, U.f64(), lam.f64(), optimistic ? r3.f64() : nullptr);  // only the first nc pairs are used below
+        if (!g.topk) {
             dev_memset(c.dev, U.p, 0, U.bytes);
             dev_memset(c.dev, lam.p, 0, lam.bytes);
             op_eigh(c.dev, C.f64(), d, dp, U.f64(), dp, lam.f64(), dt == F32 ? 1e-8 : 1e-15, false, 0, nc);  // (closeness verdict over the nc pairs used)
         }
-        if (dt == F64) {  // the whitening divides by sigma: below the Gram route's floor take the accurate route (see pca_fit)
-            std::vector<double> hl(nc);
-            dev_d2h(c.dev, hl.data(), lam.p, sizeof(double) * nc);
-            dev_sync(c.dev);
-            const bool low = hl[0] > 0 && hl[nc - 1] > 0 && n_total >= d && std::sqrt(hl[nc - 1] / hl[0]) < GRAM_ROUTE_FLOOR;
-            if (agree_any(c, low)) {  // (rank-deficient data stay on the Gram route: see pca_fit)
-                DBuf sg(c.dev, sizeof(double) * dp);
-                if (accurate_small_svd(c, X, muT.p, Ckeep.f64(), d, U.f64(), sg.f64())) op_dvec(c.dev, 2, sg.f64(), lam.f64(), d, 0.0);
-            }
+        // the whitening divides by sigma: below the Gram route's floor take the accurate route (see pca_fit)
+        if (dt == F64 && lam_below_gram_floor(c, lam.f64(), nc, n_total, d)) {
+            DBuf sg(c.dev, sizeof(double) * dp);
+            if (accurate_small_svd(c, X, muT.p, g.Ckeep.f64(), d, U.f64(), sg.f64())) op_dvec(c.dev, 2, sg.f64(), lam.f64(), d, 0.0);
         }
         // K^T = U[:, :nc] / sigma (ica.rs:190-203), zero padded, and K^T sqrt(n) (ica.rs:204-208), one launch
         DBuf KT(c.dev, sizeof(double) * dp * ncp), KTs(c.dev, sizeof(double) * dp * ncp);
-        op_whiten_k(c.dev, U.f64(), dp, lam.f64(), dp, nc, ncp, std::sqrt(ri.n_total), KT.f64(), KTs.f64());
+        op_whiten_k(c.dev, U.f64(), dp, lam.f64(), dp, nc, ncp, std::sqrt(in.ri.n_total), KT.f64(), KTs.f64());
         op_gemm_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, KTs.f64(), ncp, ncp, nullptr, X1T.p, ncp, nullptr);
 
         dev_join(c.dev);   // the decorrelated w_init (side stream) meets the whitened data
-        iters = ica_loop(c, dt, X1T.p, n, nc, ncp, ri.n_total, W, tol, max_iter, mode, &start);  // ica.rs:216
+        iters = ica_loop(c, dt, X1T.p, n, nc, ncp, in.ri.n_total, W, tol, max_iter, mode, &start);  // ica.rs:216
 
         // components = W K (ica.rs:217); everything the host reads comes back behind ONE synchronisation
         DBuf Cm(c.dev, sizeof(double) * nc * dp);
@@ -1414,7 +1421,7 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
         {
             void* dsts[5] = {hC.data(), hmu.data(), h3, &hl2[0], &hl2[1]};
             const void* srcs[5] = {Cm.p, mu64.p, r3.p, lam.p, lam.f64() + (nc - 1)};
-            const size_t lens[5] = {Cm.bytes, sizeof(double) * size_t(dp), (topk && optimistic) ? sizeof(h3) : 0,
+            const size_t lens[5] = {Cm.bytes, sizeof(double) * size_t(dp), (g.topk && optimistic) ? sizeof(h3) : 0,
                                     gram_fast ? sizeof(double) : 0, gram_fast ? sizeof(double) : 0};
             dev_d2h_multi(c.dev, 5, dsts, srcs, lens);
         }
@@ -1424,7 +1431,7 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
         // by -- the level of the crate's own f32 SVD whitening, ica.rs:189-208; the round-5 bound of two decades left 2e-4 there,
         // ADVICE round 5)
         const bool spectrum_ok = !gram_fast || (hl2[0] > 0 && hl2[1] >= 1e-1 * hl2[0]);
-        return !agree_any(c, ((topk && optimistic) && !topk_verdict_ok(h3, vtol)) || !spectrum_ok);   // every rank redoes, or none
+        return !agree_any(c, ((g.topk && optimistic) && !topk_verdict_ok(h3, g.vtol)) || !spectrum_ok);   // every rank redoes, or none
     };
     bool redone = false;
     if (!pipeline(true)) { redone = true; pipeline(false); }
@@ -1451,10 +1458,7 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
 // ica_par (ica.rs:319-361) with the crate's nc x n component-major input
 void ica_par(petal_ctx& c, const petal_matrix& x1, double tol, int64_t max_iter, int mode, const void* w_init,
              void* w_out, int64_t* n_iter) {
-    Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
-    check_matrix(x1, "input");
+    const Timer timer = start_fit(c, x1);
     const int dt = x1.dtype;
     const int64_t nc = x1.rows, n = x1.cols;
     if (nc == 0) { if (n_iter) *n_iter = 0; return; }
@@ -1553,10 +1557,7 @@ void svd_flip(petal_ctx& c, const petal_matrix& u, const petal_matrix& vt) {
 // the two X-streaming GEMMs on their own (parity tests / roofline measurement)
 void gemm_xp(petal_ctx& c, const petal_matrix& x, const void* mu, const void* p, int64_t N, const void* bias,
              const petal_matrix& z_out) {
-    Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
-    check_matrix(x, "input");
+    const Timer timer = start_fit(c, x);
     const int dt = x.dtype;
     if (N < 0) invalid_input("negative parameter");
     if (x.rows == 0 || N == 0) { emit(c, dt, nullptr, x.rows, N, 0, z_out); return; }
@@ -1585,10 +1586,7 @@ void gemm_xp(petal_ctx& c, const petal_matrix& x, const void* mu, const void* p,
 // one power iteration on its own: the fused pass where it exists, K1 + K2 otherwise (parity tests / roofline measurement)
 void power_pass(petal_ctx& c, const petal_matrix& x, const void* mu, const void* p, int64_t N, double* y_out, const petal_matrix* z_out,
                 int* fused_out) {
-    Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
-    check_matrix(x, "input");
+    const Timer timer = start_fit(c, x);
     const int dt = x.dtype;
     if (N < 0) invalid_input("negative parameter");
     if (fused_out) *fused_out = 0;

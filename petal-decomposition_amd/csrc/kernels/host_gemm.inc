@@ -711,8 +711,7 @@ void op_gemm_atb(Dev* d, int dt, const void* A, int64_t lda, int64_t M, const vo
 
 __global__ void k_flip_key(const double* __restrict__ t, double* __restrict__ key, int64_t L, const int* __restrict__ flag) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // (three verdict words: pivot breakdowns -> 3, heavy tail -> 1, else the eigen-solver's closeness verdict -> 2; algo.cpp reads the code)
-    if (j == L && flag) key[L] = flag[0] != 0 ? 3.0 : (flag[1] != 0 ? 1.0 : (flag[2] != 0 ? 2.0 : 0.0));
+    if (j == L && flag) key[L] = verdict_code(flag);   // (the three verdict words' code: ops.h)
     if (j >= L) return;
     const double a = t[j] < 0 ? 0.0 : t[j];
     unsigned long long bits = (unsigned long long)__double_as_longlong(a);

@@ -191,9 +191,17 @@ void op_col_absmax(Dev*, int dtype, const void* U, int64_t n, int64_t L, int64_t
 // svd_flip across ranks, fp32 data: key[j] = the fp64 image of absmax[j] with (2^28 - 1 - row[j], sign[j] < 0) packed into
 // the 29 low mantissa bits an fp32 magnitude leaves zero (absmax < 0, an empty shard, gives key 0); `triple` is
 // op_col_absmax's [absmax | row | sign] (3 L).  A MAX all-reduce of the keys elects the first element of maximal magnitude.
-// flag != nullptr (three ints): key[L] = flag[0] != 0 ? 3 : flag[1] != 0 ? 1 : flag[2] != 0 ? 2 : 0 -- a replicated decision word riding the same MAX
-// all-reduce, so that every rank branches on the agreed value; the stronger redo (2) wins
+// flag != nullptr (three ints): key[L] = verdict_code(flag) -- a replicated decision word riding the same MAX all-reduce, so that
+// every rank branches on the agreed value
 void op_flip_key(Dev*, const double* triple, double* key, int64_t L, const int* flag = nullptr);
+// The redo verdict of an optimistic RandomizedPca run (algo.cpp's attempt loop) from its three verdict words: [0] pivot breakdowns,
+// [1] a heavy tail behind the block, [2] eigenvalues among the wanted ones too close for the two-stage eigen-solver's vectors.  The one
+// definition of the code for the host algorithms, the device's op_flip_key and the host simulation's: a sharded fp32 fit and a
+// single-rank fit must branch alike.  (Words read lazily, in this order.)
+constexpr double VERDICT_TAIL = 1.0, VERDICT_EIG = 2.0, VERDICT_PIVOT = 3.0;
+constexpr double verdict_code(const int* w) {
+    return w[0] != 0 ? VERDICT_PIVOT : (w[1] != 0 ? VERDICT_TAIL : (w[2] != 0 ? VERDICT_EIG : 0.0));
+}
 // A[i][j] *= s[j] (dtype matrix, f64 scale vector), i < n, j < L
 void op_scale_cols(Dev*, int dtype, void* A, int64_t n, int64_t L, int64_t lda, const double* s);
 // G = tanh(X) elementwise (n x c), gp[j]... logcosh KAT helper: rows are components:
