@@ -123,13 +123,15 @@ def lu_pl(a: np.ndarray):
 # --------------------------------------------------------------------------- pca.rs
 def svd_flip(u: np.ndarray, vt: np.ndarray) -> None:
     """svd_flip (pca.rs:815-850): per column of u, the sign of the FIRST element of maximal
-    magnitude (strict '>' update, pca.rs:830) decides; flips u[:, j] and vt[j, :] in place."""
+    magnitude (strict '>' update, pca.rs:830) decides; flips u[:, j] and vt[j, :] in place.
+    The deciding quantity is Rust's ``signum`` (pca.rs:827, 837), which is -1 for -0.0: the SIGN BIT, not ``np.sign``
+    (0 for either zero) -- an all-zero column that starts with -0.0 is flipped."""
     for j in range(min(u.shape[1], vt.shape[0])):
         col = u[:, j]
         if col.shape[0] == 0:
             continue
         i = int(np.argmax(np.abs(col)))  # numpy argmax returns the first maximum
-        if np.sign(col[i]) < 0:
+        if np.signbit(col[i]):
             u[:, j] *= -1
             vt[j, :] *= -1
 

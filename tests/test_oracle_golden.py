@@ -84,6 +84,19 @@ def test_svd_flip(kats):
     assert np.array_equal(v, np.array(c["v_out"], dtype=float))
 
 
+def test_svd_flip_negative_zero_column():
+    """src/pca.rs:827: the first element's `signum` starts the scan, and Rust's signum(-0.0) is -1 -- an all-zero column whose first
+    element is -0.0 IS flipped (every sign bit of the column and of the V^T row changes: `*e *= signum`, pca.rs:842-847); one that
+    starts with +0.0 is not, whatever follows it (|-0.0| is not greater than |+0.0|)."""
+    u = np.array([[-0.0, 0.0, 3.0], [0.0, -0.0, -4.0], [0.0, 0.0, 4.0]])
+    v = np.array([[1.0, -2.0], [1.0, -2.0], [1.0, 0.0]])
+    po.svd_flip(u, v)
+    u_out = np.array([[0.0, 0.0, -3.0], [-0.0, -0.0, 4.0], [-0.0, 0.0, -4.0]])
+    v_out = np.array([[-1.0, 2.0], [1.0, -2.0], [-1.0, -0.0]])
+    assert np.array_equal(u, u_out) and np.array_equal(np.signbit(u), np.signbit(u_out))
+    assert np.array_equal(v, v_out) and np.array_equal(np.signbit(v), np.signbit(v_out))
+
+
 @pytest.mark.parametrize("literal", [False, True])
 def test_ica_par_single_iter(kats, literal):
     c = kats["ica_par_single_iter"]
