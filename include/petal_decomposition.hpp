@@ -320,6 +320,8 @@ class FastIca {  // src/ica.rs:41-221
     const Array2<A>& components() const { return components_; }
     int64_t n_iter() const { return n_iter_; }
     int mode = PETAL_ICA_TEXTBOOK;  // PETAL_ICA_REFERENCE_LITERAL follows src/ica.rs:345-349, 369-380 as written
+    // the contrast function g: PETAL_ICA_CONTRAST_LOGCOSH (the crate's, src/ica.rs:383-398), _EXP or _CUBE (extensions of this library)
+    int contrast = PETAL_ICA_CONTRAST_LOGCOSH;
 
   private:
     Context& context() const { return ctx_ ? *ctx_ : Context::global(); }
@@ -333,7 +335,7 @@ class FastIca {  // src/ica.rs:41-221
         int64_t it = 0;
         petal_matrix mx = input.view(), my{};
         if (y) my = y->view();
-        context().check(petal_fastica_fit(context().get(), &mx, 0, 1e-4, 200, mode, w_init.data(), comp.data.data(), means.data(),
+        context().check(petal_fastica_fit(context().get(), &mx, 0, 1e-4, 200, mode | contrast, w_init.data(), comp.data.data(), means.data(),
                                           &it, y ? &my : nullptr));
         components_ = std::move(comp); means_ = std::move(means); n_iter_ = it;
     }
@@ -352,10 +354,15 @@ class FastIcaBuilder {  // src/ica.rs:244-308
     static FastIcaBuilder with_rng(R rng) { FastIcaBuilder b; b.rng_ = rng; return b; }
     FastIcaBuilder& seed(unsigned __int128 s) { rng_ = R::from_seed_be_bytes(s); return *this; }
     FastIcaBuilder& context(Context* c) { ctx_ = c; return *this; }
-    template <class A> FastIca<A, R> build() const { return FastIca<A, R>(rng_, ctx_); }
+    FastIcaBuilder& contrast(int c) { contrast_ = c; return *this; }  // PETAL_ICA_CONTRAST_*
+    template <class A> FastIca<A, R> build() const {
+        FastIca<A, R> m(rng_, ctx_);
+        m.contrast = contrast_;
+        return m;
+    }
 
   private:
-    R rng_; Context* ctx_ = nullptr;
+    R rng_; Context* ctx_ = nullptr; int contrast_ = PETAL_ICA_CONTRAST_LOGCOSH;
 };
 
 }  // namespace petal_decomposition

@@ -41,6 +41,15 @@ enum { PETAL_SUM = 0, PETAL_MAX = 1, PETAL_MIN = 2 };
 /* FastICA semantics: TEXTBOOK = (W W^T)^(-1/2) W and rows.rows convergence test;
  * REFERENCE_LITERAL = the crate's arithmetic as written (src/ica.rs:345-349, 369-380). */
 enum { PETAL_ICA_TEXTBOOK = 0, PETAL_ICA_REFERENCE_LITERAL = 1 };
+/* The contrast function g of the fixed-point iteration W <- polar(g(W X1) X1^T / n - diag(mean g'(W X1)) W) rides in bits 4-7 of the
+ * same `mode` argument of petal_fastica_fit and petal_ica_par (bits 0-3: the semantics above), OR-ed to it:
+ *   LOGCOSH  g(u) = tanh u              the crate's only one (src/ica.rs:383-398) and the default
+ *   EXP      g(u) = u exp(-u^2 / 2)     robust: heavy-tailed sources, outliers
+ *   CUBE     g(u) = u^3                 kurtosis: cheap, for sub-Gaussian sources
+ * EXP and CUBE are an extension beyond the crate.  Any other value of the field, or a bit above bit 7, is
+ * PETAL_INVALID_INPUT.  petal_symmetric_decorrelation takes the semantics alone. */
+enum { PETAL_ICA_CONTRAST_LOGCOSH = 0, PETAL_ICA_CONTRAST_EXP = 16, PETAL_ICA_CONTRAST_CUBE = 32 };
+enum { PETAL_ICA_SEMANTICS_MASK = 15, PETAL_ICA_CONTRAST_MASK = 240 };
 
 typedef struct petal_matrix {
     void*   data;

@@ -31,6 +31,18 @@ OPTIONS = {"two_plane_operands": 0, "two_plane_omega": 1, "two_plane_iterate": 2
            "fused_pass_min_rows": 5, "verdict_threshold": 6, "means_fold_rows": 7, "gram_split": 8, "gram_split_hook": 9,
            "d2h_kernel": 10, "row_pad": 11, "eigh_jacobi": 12, "poison": 13, "force_collective": 14}
 ICA_TEXTBOOK, ICA_REFERENCE_LITERAL = 0, 1
+# the contrast function of the FastICA iteration: bits 4-7 of the same `mode` argument (include/petal_hip.h); EXP and CUBE are an
+# extension beyond the crate, whose only contrast is logcosh
+ICA_CONTRAST_LOGCOSH, ICA_CONTRAST_EXP, ICA_CONTRAST_CUBE = 0, 16, 32
+ICA_SEMANTICS_MASK, ICA_CONTRAST_MASK = 15, 240
+_ICA_FUN = {"logcosh": ICA_CONTRAST_LOGCOSH, "exp": ICA_CONTRAST_EXP, "cube": ICA_CONTRAST_CUBE}
+
+
+def _ica_contrast(fun) -> int:
+    try:
+        return _ICA_FUN[fun]
+    except (KeyError, TypeError):
+        raise InvalidInput(f"unknown contrast function {fun!r}: one of {sorted(_ICA_FUN)}") from None
 
 
 from .pcg import Pcg  # noqa: E402  (rand_pcg::Mcg128Xsl64 + Ziggurat StandardNormal)
@@ -679,11 +691,16 @@ class FastIca:
 
     TOL, MAX_ITER = 1e-4, 200  # src/ica.rs:216
 
-    def __init__(self, rng=None, ctx=None, n_components: int = 0, mode: int = ICA_TEXTBOOK, tol=None, max_iter=None):
+    def __init__(self, rng=None, ctx=None, n_components: int = 0, mode: int = ICA_TEXTBOOK, tol=None, max_iter=None,
+                 fun: str = "logcosh"):
         self.rng = rng if rng is not None else np.random.default_rng()
         self.ctx = ctx
         self.n_components = int(n_components)  # extension: the crate always uses min(n, d) (src/ica.rs:173)
         self.mode = mode
+        # extension: "logcosh" (the crate's, src/ica.rs:383-398), "exp" or "cube".  `mode` is meant to carry the semantics; contrast bits
+        # in it are passed on as they are with the default fun, and refused beside any other fun (_mode_word)
+        self.fun = fun
+        _ica_contrast(fun)
         self.tol = self.TOL if tol is None else tol
         self.max_iter = self.MAX_ITER if max_iter is None else max_iter
         self.components = np.zeros((0, 0))
@@ -725,10 +742,18 @@ class FastIca:
             self.ctx = default_context()
         return self.ctx
 
+    def _mode_word(self) -> int:
+        """the ABI's `mode`: the semantics with the contrast of `fun` in bits 4-7"""
+        mode, g = int(self.mode), _ica_contrast(self.fun)
+        if g != ICA_CONTRAST_LOGCOSH and mode >= 0 and mode & ICA_CONTRAST_MASK:
+            raise InvalidInput(f"FastICA: mode = {mode} already carries a contrast function; give it either there or as fun = {self.fun!r}")
+        return mode | g
+
     def _inner_fit(self, x, want_y: bool, w_init=None):
         keep = []
         mx = describe(x, keep)
         ctx = self._ctx()
+        word = self._mode_word()
         npdt = _np_dtype(mx.dtype)
         if mx.rows == 0 and ctx.world_size == 1:  # src/ica.rs:174-176
             return _alloc_like(x, 0, mx.cols, mx.dtype) if want_y else None
@@ -744,7 +769,7 @@ class FastIca:
             y = _alloc_like(x, mx.rows, nc, mx.dtype)
             my = describe(y, keep)
         ctx.check(ctx.lib.petal_fastica_fit(ctx._h, C.byref(mx), self.n_components, float(self.tol),
-                                            int(self.max_iter), int(self.mode), w_init.ctypes.data, comp.ctypes.data,
+                                            int(self.max_iter), word, w_init.ctypes.data, comp.ctypes.data,
                                             means.ctypes.data, C.byref(n_iter), C.byref(my) if my is not None else None))
         self.components, self.means, self.n_iter = comp, means, int(n_iter.value)
         return y
@@ -777,7 +802,7 @@ class FastIcaBuilder:
     """``FastIcaBuilder<R>`` (src/ica.rs:244-308)."""
 
     def __init__(self, rng=None):
-        self._rng, self._ctx, self._nc, self._mode = rng, None, 0, ICA_TEXTBOOK
+        self._rng, self._ctx, self._nc, self._mode, self._fun = rng, None, 0, ICA_TEXTBOOK, "logcosh"
 
     @classmethod
     def new(cls):
@@ -804,13 +829,20 @@ class FastIcaBuilder:
         self._mode = mode
         return self
 
+    def fun(self, name: str):
+        """The contrast function: "logcosh" (the crate's), "exp" or "cube" (extensions)."""
+        _ica_contrast(name)
+        self._fun = name
+        return self
+
     def build(self) -> FastIca:
-        return FastIca(self._rng, self._ctx, self._nc, self._mode)
+        return FastIca(self._rng, self._ctx, self._nc, self._mode, fun=self._fun)
 
 
 # ---- crate-private kernels that carry known-answer tests -------------------------------------------
 def ica_par(x1, tol, max_iter, w_init, mode=ICA_TEXTBOOK, ctx: Optional[Context] = None):
-    """``ica_par`` (src/ica.rs:319-361): x1 is nc x n.  Returns (W, n_iter)."""
+    """``ica_par`` (src/ica.rs:319-361): x1 is nc x n.  Returns (W, n_iter).  mode: ICA_TEXTBOOK or ICA_REFERENCE_LITERAL, OR-ed
+    with an ICA_CONTRAST_* (default: logcosh)."""
     ctx = ctx or default_context()
     keep = []
     mx = describe(x1, keep)

@@ -1232,6 +1232,12 @@ void inverse_transform(petal_ctx& c, const petal_matrix& y, const void* componen
 }
 
 // ---------------------------------------------------------------------------------------------
+// The contrasts beyond logcosh are an extension that a device-op layer may lack (the host simulation does): this default stands in
+// wherever no strong definition is linked, and refuses.
+__attribute__((weak)) void op_ica_step_g(Dev*, int, const void*, int64_t, int64_t, int64_t, const double*, double*, const int*, int) {
+    invalid_input("contrast not available in this device-op layer (only logcosh is)");
+}
+
 namespace {
 
 // ica_par (ica.rs:319-361) on a device-resident, sample-major X1T (n x ncp).  W (device f64 nc x nc)
@@ -1240,6 +1246,15 @@ namespace {
 // (ica_prepare between dev_fork and dev_fork_end), ica_par right before its loop.  W: w_init in, the decorrelated iterate out;
 // state: the loop's {converged at, iterations done} words, cleared by the same launch.
 struct IcaStart { DBuf W0, state; };
+// `mode` as the ABI carries it: bits 0-3 the semantics (what op_symdecorr and op_ica_tail understand), bits 4-7 the contrast
+struct IcaMode { int semantics, contrast; };
+IcaMode split_ica_mode(int mode) {
+    if (mode < 0 || (mode & ~(PETAL_ICA_SEMANTICS_MASK | PETAL_ICA_CONTRAST_MASK))) invalid_input("unknown FastICA mode bits");
+    const int g = mode & PETAL_ICA_CONTRAST_MASK;
+    if (g != PETAL_ICA_CONTRAST_LOGCOSH && g != PETAL_ICA_CONTRAST_EXP && g != PETAL_ICA_CONTRAST_CUBE)
+        invalid_input("unknown FastICA contrast function (PETAL_ICA_CONTRAST_LOGCOSH, _EXP or _CUBE)");
+    return {mode & PETAL_ICA_SEMANTICS_MASK, g >> 4};
+}
 IcaStart ica_prepare(petal_ctx& c, int64_t nc, DBuf& W, int mode) {
     // (the caller's buffer holds w_init; the iterate lives in a buffer of this function's and the two are exchanged -- no copy)
     IcaStart s{DBuf(c.dev, W.bytes), DBuf(c.dev, 2 * sizeof(int))};
@@ -1248,7 +1263,7 @@ IcaStart ica_prepare(petal_ctx& c, int64_t nc, DBuf& W, int mode) {
     return s;
 }
 int64_t ica_loop(petal_ctx& c, int dt, const void* X1T, int64_t n, int64_t nc, int64_t ld, double n_total, DBuf& W,
-                 double tol, int64_t max_iter, int mode, IcaStart* prepared = nullptr) {
+                 double tol, int64_t max_iter, int mode, int contrast, IcaStart* prepared = nullptr) {
     IcaStart own;
     if (!prepared) { own = ica_prepare(c, nc, W, mode); prepared = &own; }
     DBuf& state = prepared->state;
@@ -1257,7 +1272,8 @@ int64_t ica_loop(petal_ctx& c, int dt, const void* X1T, int64_t n, int64_t nc, i
     int hstate[2] = {0, 0};
     auto enqueue = [&](int64_t it, int* progress) {
         dev_set_tag(c.dev, TAG_ICA);
-        op_ica_step(c.dev, dt, X1T, n, nc, ld, W.f64(), GX.f64(), state.as<int>());  // ica.rs:332-333
+        if (contrast == 0) op_ica_step(c.dev, dt, X1T, n, nc, ld, W.f64(), GX.f64(), state.as<int>());  // ica.rs:332-333
+        else op_ica_step_g(c.dev, dt, X1T, n, nc, ld, W.f64(), GX.f64(), state.as<int>(), contrast);
         dev_set_tag(c.dev, TAG_NONE);
         allreduce_f64(c, GX.f64(), nc * nc + nc, PETAL_SUM);
         op_ica_tail(c.dev, nc, n_total, W.f64(), GX.f64(), mode, tol, state.as<int>(), int(it), progress);  // ica.rs:334-358
@@ -1322,8 +1338,10 @@ void check_finite_w(const std::vector<double>& w) {
 }  // namespace
 
 // FastIca::inner_fit (ica.rs:167-221)
-void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, double tol, int64_t max_iter, int mode,
+void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, double tol, int64_t max_iter, int mode_bits,
                  const void* w_init, void* components, void* means, int64_t* n_iter, const petal_matrix* y_out) {
+    const IcaMode im = split_ica_mode(mode_bits);
+    const int mode = im.semantics;
     const Timer timer = start_fit(c, x);
     const int dt = x.dtype;
     const int64_t d = x.cols;
@@ -1412,7 +1430,7 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
         op_gemm_xp(c.dev, dt, X.p, n, dp, X.ld, muT.p, KTs.f64(), ncp, ncp, nullptr, X1T.p, ncp, nullptr);
 
         dev_join(c.dev);   // the decorrelated w_init (side stream) meets the whitened data
-        iters = ica_loop(c, dt, X1T.p, n, nc, ncp, in.ri.n_total, W, tol, max_iter, mode, &start);  // ica.rs:216
+        iters = ica_loop(c, dt, X1T.p, n, nc, ncp, in.ri.n_total, W, tol, max_iter, mode, im.contrast, &start);  // ica.rs:216
 
         // components = W K (ica.rs:217); everything the host reads comes back behind ONE synchronisation
         DBuf Cm(c.dev, sizeof(double) * nc * dp);
@@ -1456,8 +1474,10 @@ void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, doub
 }
 
 // ica_par (ica.rs:319-361) with the crate's nc x n component-major input
-void ica_par(petal_ctx& c, const petal_matrix& x1, double tol, int64_t max_iter, int mode, const void* w_init,
+void ica_par(petal_ctx& c, const petal_matrix& x1, double tol, int64_t max_iter, int mode_bits, const void* w_init,
              void* w_out, int64_t* n_iter) {
+    const IcaMode im = split_ica_mode(mode_bits);
+    const int mode = im.semantics;
     const Timer timer = start_fit(c, x1);
     const int dt = x1.dtype;
     const int64_t nc = x1.rows, n = x1.cols;
@@ -1481,7 +1501,7 @@ void ica_par(petal_ctx& c, const petal_matrix& x1, double tol, int64_t max_iter,
         for (int64_t i = 0; i < nc * nc; ++i) h[i] = get_elem(w_init, dt, i);
         dev_h2d(c.dev, W.p, h.data(), W.bytes);
     }
-    const int64_t iters = ica_loop(c, dt, xp, n, nc, X1T.ld, ri.n_total, W, tol, max_iter, mode);
+    const int64_t iters = ica_loop(c, dt, xp, n, nc, X1T.ld, ri.n_total, W, tol, max_iter, mode, im.contrast);
     dev_d2h(c.dev, h.data(), W.p, W.bytes);
     dev_sync(c.dev);
     check_finite_w(h);

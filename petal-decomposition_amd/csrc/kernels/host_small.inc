@@ -19,8 +19,15 @@ void op_ica_prepare(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int6
     launch_check();
     d->ica_x1pl_for = X1T; d->ica_x1pl_n = n; d->ica_x1pl_ld = ld;
 }
-void op_ica_step(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t ld, const double* W, double* GX_gp,
-                 const int* state) {
+// the kernel instantiation of a contrast other than logcosh (g: ICA_G_EXP or ICA_G_CUBE, checked by op_ica_step_g)
+#define ICA_G_DISPATCH(g, CALL)                                          \
+    do {                                                                 \
+        if ((g) == ICA_G_EXP) { constexpr int Gv = ICA_G_EXP; CALL; }    \
+        else { constexpr int Gv = ICA_G_CUBE; CALL; }                    \
+    } while (0)
+// one step of the loop with contrast g (ICA_G_LOGCOSH: the kernels the crate's logcosh has always run on)
+static void ica_step_impl(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t ld, const double* W, double* GX_gp,
+                          const int* state, const int g) {
     const int64_t cnt = nc * nc + nc;
     const bool planes_current = d->ica_wpk3_valid && d->ica_wpk3_for == W && d->ica_wpk3_nc == nc;
     d->ica_ortho_tol2 = dt == F32 ? 1e-14 : 1e-26;
@@ -40,6 +47,20 @@ void op_ica_step(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t
         op_gemm_xp(d, dt, X1T, n, ncp, ld, nullptr, WT, ncp, ncp, nullptr, S, ncp, nullptr);
         const int saved_tag = d->tag;
         d->tag = TAG_NONE;  // (only the first product is bracketed as "the step kernel")
+        if (g != ICA_G_LOGCOSH) {
+            // n - sum g^2 is tanh's identity: here g' is summed explicitly, per 256-row block and then over the blocks in order
+            const int64_t nparts = cdiv(n, 256);
+            double* gp_part = (double*)dev_alloc(d, sizeof(double) * nparts * ncp);
+            ICA_G_DISPATCH(g, DISPATCH_T(dt, hipLaunchKernelGGL((k_contrast_inplace<T, Gv>), dim3((unsigned)nparts), dim3(256), 0, d->stream, (T*)S, n, ncp, gp_part)));
+            launch_check();
+            double* GXp = (double*)dev_alloc(d, sizeof(double) * ncp * ncp);
+            op_gemm_atb(d, dt, S, ncp, ncp, nullptr, X1T, ld, ncp, nullptr, n, GXp, ncp);
+            hipLaunchKernelGGL(k_ica_big_out_g, dim3(cdiv(cnt, 256)), dim3(256), 0, d->stream, GXp, gp_part, nparts, nc, ncp, GX_gp, state);
+            launch_check();
+            d->tag = saved_tag;
+            dev_free(d, GXp); dev_free(d, gp_part); dev_free(d, S); dev_free(d, WT);
+            return;
+        }
         DISPATCH_T(dt, hipLaunchKernelGGL(k_tanh_inplace<T>, dim3(cdiv((int64_t)n * ncp, 256)), dim3(256), 0, d->stream, (T*)S, (int64_t)n * ncp));
         launch_check();
         double* cs = (double*)dev_alloc(d, sizeof(double) * 2 * ncp);
@@ -56,8 +77,16 @@ void op_ica_step(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t
         const int64_t nparts = cdiv(n, 64);
         double* part = (double*)dev_alloc(d, sizeof(double) * nparts * cnt);
         TagScope ts(d);
-        DISPATCH_T(dt, hipLaunchKernelGGL(k_ica_simple<T>, dim3((unsigned)nparts), dim3(256), sizeof(double) * nc * 64, d->stream,
-                                          (const T*)X1T, n, (int)nc, ld, W, part, state));
+        if (g == ICA_G_LOGCOSH) {
+            DISPATCH_T(dt, hipLaunchKernelGGL(k_ica_simple<T>, dim3((unsigned)nparts), dim3(256), sizeof(double) * nc * 64, d->stream,
+                                              (const T*)X1T, n, (int)nc, ld, W, part, state));
+        } else {
+            const size_t lds = 2 * sizeof(double) * nc * 64;   // g and g': 64 KB at 64 components
+            ICA_G_DISPATCH(g, DISPATCH_T(dt, {
+                if (lds >= 64 * 1024) set_max_lds(d, reinterpret_cast<const void*>(k_ica_simple_g<T, Gv>));
+                hipLaunchKernelGGL((k_ica_simple_g<T, Gv>), dim3((unsigned)nparts), dim3(256), lds, d->stream, (const T*)X1T, n, (int)nc, ld, W, part, state);
+            }));
+        }
         launch_check();
         ts.stop();
         hipLaunchKernelGGL(k_sum_parts_state, dim3(cdiv(cnt, 256)), dim3(256), 0, d->stream, part, nparts, cnt, GX_gp, state);
@@ -90,7 +119,24 @@ void op_ica_step(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t
         float* part = (float*)dev_alloc(d, sizeof(float) * blocks * slab);
         TagScope ts(d);
         const bool pre = d->ica_x1pl_for == X1T && d->ica_x1pl_n == n && d->ica_x1pl_ld == ld && (NT == 2 || NT == 4);
-        if (pre) {
+        if (g != ICA_G_LOGCOSH) {
+#define ICA3G_LAUNCH(NTv) hipLaunchKernelGGL((k_ica3g<NTv, Gv>), dim3(blocks), dim3(256), 0, d->stream, (const float*)X1T, n, ld, Wpk3, bpw, part, state)
+            if (pre) {
+                if (NT == 2) ICA_G_DISPATCH(g, hipLaunchKernelGGL((k_ica3pg<2, Gv>), dim3(blocks), dim3(256), 0, d->stream, (const bf16x8*)d->ica_x1pl, n, Wpk3, bpw, part, state));
+                else ICA_G_DISPATCH(g, hipLaunchKernelGGL((k_ica3pg<4, Gv>), dim3(blocks), dim3(256), 0, d->stream, (const bf16x8*)d->ica_x1pl, n, Wpk3, bpw, part, state));
+            } else
+            // (NT = 2 and 4 land here only when the step is called WITHOUT op_ica_prepare, which the op allows (ops.h) and ica_loop never
+            // does: its conditions for those two are this path's own, so every fit and every ica_par takes k_ica3pg there, as the logcosh
+            // step takes k_ica3p (EXPERIMENTS.md).  k_ica3g<2, *> and <4, *> are built and held to their register budgets, not launched
+            // by any caller of the library today; what runs of k_ica3g is NT = 1 and 3.)
+            switch (NT) {
+                case 1: ICA_G_DISPATCH(g, ICA3G_LAUNCH(1)); break;
+                case 2: ICA_G_DISPATCH(g, ICA3G_LAUNCH(2)); break;
+                case 3: ICA_G_DISPATCH(g, ICA3G_LAUNCH(3)); break;
+                default: ICA_G_DISPATCH(g, ICA3G_LAUNCH(4)); break;
+            }
+#undef ICA3G_LAUNCH
+        } else if (pre) {
             if (NT == 2) hipLaunchKernelGGL(k_ica3p<2>, dim3(blocks), dim3(256), 0, d->stream, (const bf16x8*)d->ica_x1pl, n, Wpk3, bpw, part, state);
             else hipLaunchKernelGGL(k_ica3p<4>, dim3(blocks), dim3(256), 0, d->stream, (const bf16x8*)d->ica_x1pl, n, Wpk3, bpw, part, state);
         } else
@@ -118,6 +164,16 @@ void op_ica_step(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t
     const int64_t nparts = (int64_t)blocks;  // one slab per workgroup
     float* part = (float*)dev_alloc(d, sizeof(float) * nparts * slab);
     TagScope ts(d);
+    if (g != ICA_G_LOGCOSH) {
+#define ICAMG_LAUNCH(NTv) hipLaunchKernelGGL((k_ica_mfma_g<NTv, Gv>), dim3(blocks), dim3(256), 0, d->stream, (const float*)X1T, n, ld, Wpk, tpw, part, state)
+        switch (NT) {
+            case 1: ICA_G_DISPATCH(g, ICAMG_LAUNCH(1)); break;
+            case 2: ICA_G_DISPATCH(g, ICAMG_LAUNCH(2)); break;
+            case 3: ICA_G_DISPATCH(g, ICAMG_LAUNCH(3)); break;
+            default: ICA_G_DISPATCH(g, ICAMG_LAUNCH(4)); break;
+        }
+#undef ICAMG_LAUNCH
+    } else
     switch (NT) {
         case 1: hipLaunchKernelGGL(k_ica_mfma<1>, dim3(blocks), dim3(256), 0, d->stream, (const float*)X1T, n, ld, Wpk, tpw, part, state); break;
         case 2: hipLaunchKernelGGL(k_ica_mfma<2>, dim3(blocks), dim3(256), 0, d->stream, (const float*)X1T, n, ld, Wpk, tpw, part, state); break;
@@ -130,6 +186,15 @@ void op_ica_step(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t
     launch_check();
     dev_free(d, part);
     dev_free(d, Wpk);
+}
+void op_ica_step(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t ld, const double* W, double* GX_gp,
+                 const int* state) {
+    ica_step_impl(d, dt, X1T, n, nc, ld, W, GX_gp, state, ICA_G_LOGCOSH);
+}
+void op_ica_step_g(Dev* d, int dt, const void* X1T, int64_t n, int64_t nc, int64_t ld, const double* W, double* GX_gp,
+                   const int* state, int contrast) {
+    if (contrast != ICA_G_LOGCOSH && contrast != ICA_G_EXP && contrast != ICA_G_CUBE) throw std::runtime_error("ica_step: unknown contrast");
+    ica_step_impl(d, dt, X1T, n, nc, ld, W, GX_gp, state, contrast);
 }
 
 

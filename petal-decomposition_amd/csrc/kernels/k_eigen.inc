@@ -1593,6 +1593,34 @@ __global__ void k_tanh_inplace(T* __restrict__ x, int64_t count) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < count) x[e] = (T)tanh((double)x[e]);
 }
+// the other contrasts (k_ica_step.inc: ica_contrast): S <- g(S) in place, and the column sums of g'(S) over this block's 256 rows to
+// gp_part[block][ncp] -- one thread per column walks the rows in order, so the sums are the same bits on every run
+template <class T, int G>
+__global__ __launch_bounds__(256) void k_contrast_inplace(T* __restrict__ S, int64_t n, int64_t ncp, double* __restrict__ gp_part) {
+    const int64_t r0 = (int64_t)blockIdx.x * 256, r1 = min(n, r0 + 256);
+    for (int64_t c = threadIdx.x; c < ncp; c += 256) {
+        double acc = 0;
+        for (int64_t r = r0; r < r1; ++r) {
+            T g, gp;
+            ica_contrast<G>(S[r * ncp + c], g, gp);
+            S[r * ncp + c] = g;
+            acc += (double)gp;
+        }
+        gp_part[(int64_t)blockIdx.x * ncp + c] = acc;
+    }
+}
+// GX_gp = [ GXp[:nc, :nc] | sum over the row blocks of gp_part, in block order ]
+__global__ void k_ica_big_out_g(const double* __restrict__ GXp, const double* __restrict__ gp_part, int64_t nparts, int64_t nc, int64_t ncp,
+                                double* __restrict__ GX_gp, const int* __restrict__ state) {
+    if (state && state[0]) return;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < nc * nc) GX_gp[e] = GXp[(e / nc) * ncp + (e % nc)];
+    else if (e < nc * nc + nc) {
+        double s = 0;
+        for (int64_t p = 0; p < nparts; ++p) s += gp_part[p * ncp + (e - nc * nc)];
+        GX_gp[e] = s;
+    }
+}
 // GX_gp = [ GXp[:nc, :nc] | n - sum_s g_si^2 ]   (sum_s (1 - g^2) = n - sum g^2, fp64)
 __global__ void k_ica_big_out(const double* __restrict__ GXp, const double* __restrict__ sumsq, double n, int64_t nc, int64_t ncp,
                               double* __restrict__ GX_gp, const int* __restrict__ state) {

@@ -1,4 +1,4 @@
-// k_ica_step.inc -- part of the ONE translation unit hip_ops.hip (textually included there, inside namespace petal): K7: the fused FastICA step (k_ica_mfma, k_ica3, k_ica3p, k_ica_reduce).
+// k_ica_step.inc -- part of the ONE translation unit hip_ops.hip (textually included there, inside namespace petal): K7: the fused FastICA step (k_ica_mfma, k_ica3, k_ica3p, k_ica_reduce; k_ica_mfma_g, k_ica3g, k_ica3pg: the same bodies, k_ica*_body.inc, with the exp / cube contrast).
 // ================================================================================================
 // K7: fused FastICA step (ica.rs:332-333) -- per 16-sample tile: S = X1 . W^T (MFMA) -> tanh ->
 // D += G^T . X1 (MFMA) and gp += sum(1 - g^2); partial D / gp per wave, combined in fp64.
@@ -9,6 +9,44 @@ __device__ __forceinline__ float tanh_fast(float x) {
     const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
     return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
+// The contrast functions of the fixed-point iteration beyond the crate's logcosh (DESIGN.md section 7): g and g' of
+//   ICA_G_LOGCOSH  tanh u,  1 - g^2       ICA_G_EXP  u exp(-u^2/2),  (1 - u^2) exp(-u^2/2)       ICA_G_CUBE  u^3,  3 u^2
+// exp: e = exp2(-u^2 log2(e)/2) is ONE v_exp_f32 and no reciprocal (underflows to 0 for |u| > 14.4: g = g' = 0, the limit);
+// g' = e - u g.  g(0) = 0 for all three, so zero rows add nothing to D; g'(0) is 1, 1, 0: see ica_gp_pad.
+enum { ICA_G_LOGCOSH = 0, ICA_G_EXP = 1, ICA_G_CUBE = 2 };
+template <int G>
+__device__ __forceinline__ void ica_contrast(float u, float& g, float& gp) {
+    static_assert(G == ICA_G_LOGCOSH || G == ICA_G_EXP || G == ICA_G_CUBE, "unknown contrast");
+    if constexpr (G == ICA_G_LOGCOSH) {
+        g = tanh_fast(u);
+        gp = fmaf(-g, g, 1.0f);
+    } else if constexpr (G == ICA_G_EXP) {
+        const float e = __builtin_amdgcn_exp2f(u * u * -0.72134752044448170f);
+        g = u * e;
+        gp = fmaf(-u, g, e);
+    } else {
+        const float u2 = u * u;
+        g = u2 * u;
+        gp = 3.0f * u2;
+    }
+}
+template <int G>
+__device__ __forceinline__ void ica_contrast(double u, double& g, double& gp) {
+    if constexpr (G == ICA_G_LOGCOSH) {
+        g = tanh(u);
+        gp = 1.0 - g * g;
+    } else if constexpr (G == ICA_G_EXP) {
+        const double e = exp(-0.5 * u * u);
+        g = u * e;
+        gp = e - u * g;
+    } else {
+        g = u * u * u;
+        gp = 3.0 * u * u;
+    }
+}
+// what the `pad` zero rows of a ragged last block (S = 0 there) put into an UNMASKED sum of g': g'(0) each
+template <int G>
+__device__ __forceinline__ float ica_gp_pad(float pad) { return G == ICA_G_CUBE ? 0.f : pad; }
 // Wpk[((kc * NT + nt) * 64 + lane) * 4 + s] = W[16 nt + (lane&15)][16 kc + 4 (lane>>4) + s]   (B = W^T)
 __global__ void k_pack_w(const double* __restrict__ W, int nc, float* __restrict__ Wpk, int NT) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,75 +101,14 @@ template <int NT>
 __global__ __launch_bounds__(256) void k_ica_mfma(const float* __restrict__ X1T, int64_t n, int64_t ld,
                                                   const float* __restrict__ Wpk, int64_t tiles_per_wave,
                                                   float* __restrict__ part, const int* __restrict__ state) {
-    if (state && state[0]) return;
-    constexpr int NCP = 16 * NT;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 15, q = lane >> 4;
-    const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-    f32x4 wf[NT][NT];  // [kc][nt]
-#pragma unroll
-    for (int kc = 0; kc < NT; ++kc)
-#pragma unroll
-        for (int u = 0; u < NT; ++u) wf[kc][u] = reinterpret_cast<const f32x4*>(Wpk)[(kc * NT + u) * 64 + lane];
-    f32x4 dacc[NT][NT];  // [component tile][x tile]
-    float gpa[NT];
-#pragma unroll
-    for (int a = 0; a < NT; ++a) {
-        gpa[a] = 0.f;
-#pragma unroll
-        for (int b = 0; b < NT; ++b) dacc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const int64_t t0 = wid * tiles_per_wave, t1 = min((n + 15) / 16, t0 + tiles_per_wave);
-    for (int64_t tile = t0; tile < t1; ++tile) {
-        const int64_t r0 = tile * 16;
-        // A layout: lane (i, q) <- X1[r0 + i][16 kc + 4 q .. +3]
-        const int64_t ra = r0 + i;
-        const bool va = ra < n;
-        f32x4 xa[NT];
-#pragma unroll
-        for (int kc = 0; kc < NT; ++kc)
-            xa[kc] = va ? *reinterpret_cast<const f32x4*>(X1T + ra * ld + 16 * kc + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-        // B layout for the second product: lane (j = i, q), k-step s <- X1[r0 + 4 q + s][16 b + j]
-        float xb[4][NT];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int64_t rb = r0 + 4 * q + s;
-            const bool vb = rb < n;
-#pragma unroll
-            for (int b = 0; b < NT; ++b) xb[s][b] = vb ? X1T[rb * ld + 16 * b + i] : 0.f;
-        }
-        f32x4 sacc[NT];
-#pragma unroll
-        for (int u = 0; u < NT; ++u) sacc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kc = 0; kc < NT; ++kc)
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int u = 0; u < NT; ++u)
-                    sacc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[kc][s], wf[kc][u][s], sacc[u], 0, 0, 0);
-        // sacc[u][r] = S[sample r0 + 4 q + r][component 16 u + i]
-#pragma unroll
-        for (int u = 0; u < NT; ++u)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float g = tanh_fast(sacc[u][r]);
-                const bool v = (r0 + 4 * q + r) < n;
-                sacc[u][r] = v ? g : 0.f;
-                gpa[u] += v ? (1.0f - g * g) : 0.f;
-            }
-        // D[component][x] += sum_samples G[sample][component] X1[sample][x]:
-        // A operand (i = component, k = q) of k-step s is G[r0 + 4 q + s][16 a + i] = sacc[a][s]
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int a = 0; a < NT; ++a)
-#pragma unroll
-                for (int b = 0; b < NT; ++b)
-                    dacc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(sacc[a][s], xb[s][b], dacc[a][b], 0, 0, 0);
-    }
-    __shared__ float s_slab[2 * (NCP * NCP + NCP)];
-    ica_write_slab<NT>(dacc, gpa, s_slab, part);
+    constexpr int G = ICA_G_LOGCOSH;
+#include "k_ica_mfma_body.inc"
+}
+template <int NT, int G>
+__global__ __launch_bounds__(256) void k_ica_mfma_g(const float* __restrict__ X1T, int64_t n, int64_t ld,
+                                                    const float* __restrict__ Wpk, int64_t tiles_per_wave,
+                                                    float* __restrict__ part, const int* __restrict__ state) {
+#include "k_ica_mfma_body.inc"
 }
 // K7, split-product form: both products of the step on the bf16 matrix cores (six piece products each, see K1).  One
 // wave handles 32 samples per pass.  The first product is laid out so that its OUTPUT is already the second product's
@@ -160,162 +137,14 @@ template <int NT>
 __global__ __launch_bounds__(256, 2) void k_ica3(const float* __restrict__ X1T, int64_t n, int64_t ld,
                                                  const bf16x8* __restrict__ Wpk3, int64_t blocks_per_wave,
                                                  float* __restrict__ part, const int* __restrict__ state) {
-    if (state && state[0]) return;
-    constexpr int NCP = 16 * NT, KCH = (NCP + 31) / 32, WITEMS = KCH * NT * 192;
-    constexpr int XP = NCP + 4;  // row pitch of the transposition buffer: 4 XP = 16 (mod 32) banks
-    constexpr int XT_FLOATS = 4 * 32 * XP, SLAB = 2 * (NCP * NCP + NCP);
-    __shared__ bf16x8 sW[WITEMS];
-    __shared__ __attribute__((aligned(16))) float sX[XT_FLOATS > SLAB ? XT_FLOATS : SLAB];  // per wave [32 samples][XP]; the slab at the end
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 15, q = lane >> 4;
-    for (int e = threadIdx.x; e < WITEMS; e += 256) sW[e] = Wpk3[e];
-    __syncthreads();
-    const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-    float* xt = sX + wave * 32 * XP;
-    f32x4 dacc[NT][NT];  // [component tile][x tile]
-    float gpa[NT];
-#pragma unroll
-    for (int a = 0; a < NT; ++a) {
-        gpa[a] = 0.f;
-#pragma unroll
-        for (int b = 0; b < NT; ++b) dacc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const int64_t b0 = wid * blocks_per_wave, b1 = min((n + 31) / 32, b0 + blocks_per_wave);
-    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    // A operand of the first product: lane (i, q) <- X1[r0 + 16 t + i][32 kc + 8 q .. + 7]
-    f32x4 xa[2][KCH][2];
-    auto load_a = [&](int64_t blk) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int64_t ra = blk * 32 + 16 * t + i;
-#pragma unroll
-            for (int kc = 0; kc < KCH; ++kc) {
-                const bool v = ra < n && (32 * kc + 8 * q) < NCP;
-                const float* src = X1T + ra * ld + 32 * kc + 8 * q;
-                xa[t][kc][0] = v ? *reinterpret_cast<const f32x4*>(src) : z4;
-                xa[t][kc][1] = v ? *reinterpret_cast<const f32x4*>(src + 4) : z4;
-            }
-        }
-    };
-    if (b0 < b1) load_a(b0);
-    // Each group of MFMAs is written next to independent VALU work (chunk kc's MFMAs beside the split of chunk kc + 1 or
-    // of the transposed rows; component tile a's MFMAs beside tanh + split of tile a + 1).  Measured (dev/micro_coissue.hip):
-    // on a SIMD holding two such waves MFMA time and VALU time ADD rather than overlap, so the pass costs
-    // ~3070 (192 MFMAs) + ~3600 (730 VALU, 64 of them quarter-rate transcendentals) cycles; the kernel runs within 25 % of that.
-    for (int64_t blk = b0; blk < b1; ++blk) {
-        const int64_t r0 = blk * 32;
-        bf16x8 ah[2], am[2], al[2];
-        auto split_a = [&](int kc) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const f32x8 x = {xa[t][kc][0][0], xa[t][kc][0][1], xa[t][kc][0][2], xa[t][kc][0][3],
-                                 xa[t][kc][1][0], xa[t][kc][1][1], xa[t][kc][1][2], xa[t][kc][1][3]};
-                split3(x, ah[t], am[t], al[t]);
-            }
-        };
-        // the raw rows also go to the wave's LDS buffer, from which the second product reads them transposed
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int kc = 0; kc < KCH; ++kc)
-                if ((32 * kc + 8 * q) < NCP) {
-                    float* dst = xt + (16 * t + i) * XP + 32 * kc + 8 * q;
-                    *reinterpret_cast<f32x4*>(dst) = xa[t][kc][0];
-                    *reinterpret_cast<f32x4*>(dst + 4) = xa[t][kc][1];
-                }
-        bf16x8 nwh = sW[lane], nwm = sW[64 + lane], nwl = sW[128 + lane];
-        split_a(0);
-        __builtin_amdgcn_wave_barrier();
-        f32x4 sacc[2][NT];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int u = 0; u < NT; ++u) sacc[t][u] = z4;
-        bf16x8 bh[NT], bm[NT], bl[NT];
-#pragma unroll
-        for (int kc = 0; kc < KCH; ++kc) {
-            __builtin_amdgcn_sched_barrier(0);
-            bf16x8 ch[2], cm[2], cl[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) { ch[t] = ah[t]; cm[t] = am[t]; cl[t] = al[t]; }
-            if (kc + 1 < KCH) {
-                split_a(kc + 1);
-            } else {
-                // B operand: lane (j = i, q), slot e <- X1[r0 + (e < 4 ? 4 q + e : 16 + 4 q + e - 4)][16 b + j]
-#pragma unroll
-                for (int b = 0; b < NT; ++b) {
-                    f32x8 xb;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) xb[e] = xt[((e < 4 ? 4 * q + e : 12 + 4 * q + e)) * XP + 16 * b + i];
-                    split3(xb, bh[b], bm[b], bl[b]);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < NT; ++u) {
-                const bf16x8 wh = nwh, wm = nwm, wl = nwl;
-                if (kc * NT + u + 1 < KCH * NT) {  // W's pieces are read one tile ahead (LDS latency off the MFMA path)
-                    const bf16x8* sw = sW + (kc * NT + u + 1) * 192 + lane;
-                    nwh = sw[0], nwm = sw[64], nwl = sw[128];
-                }
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    f32x4 c4 = sacc[t][u];
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cl[t], wh, c4, 0, 0, 0);  // smallest terms first
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cm[t], wm, c4, 0, 0, 0);
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ch[t], wl, c4, 0, 0, 0);
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cm[t], wh, c4, 0, 0, 0);
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ch[t], wm, c4, 0, 0, 0);
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ch[t], wh, c4, 0, 0, 0);
-                    sacc[t][u] = c4;
-                }
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (blk + 1 < b1) load_a(blk + 1);  // next pass's rows land behind tanh and the second product
-        // sacc[t][u][r] = S[sample r0 + 16 t + 4 q + r][component 16 u + i].  Rows past n were loaded as zeros: S = 0
-        // and tanh(0) = 0 exactly, so only the g' sum needs masking (last pass).
-        const bool tail = r0 + 32 > n;
-        const float nvalid = tail ? (float)((n > r0 + 4 * q ? (int)min((int64_t)4, n - r0 - 4 * q) : 0) +
-                                            (n > r0 + 16 + 4 * q ? (int)min((int64_t)4, n - r0 - 16 - 4 * q) : 0))
-                                  : 8.0f;
-        bf16x8 gh, gm, gl;
-        auto make_g = [&](int u) {
-            f32x8 g8;
-            float gs = 0.f;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float g = tanh_fast(sacc[t][u][r]);
-                    g8[4 * t + r] = g;
-                    gs = fmaf(-g, g, gs);
-                }
-            gpa[u] += gs + nvalid;
-            split3(g8, gh, gm, gl);
-        };
-        make_g(0);
-        // D[component][x] += sum_samples G[sample][component] X1[sample][x]
-#pragma unroll
-        for (int a = 0; a < NT; ++a) {
-            __builtin_amdgcn_sched_barrier(0);
-            const bf16x8 fh = gh, fm = gm, fl = gl;
-            if (a + 1 < NT) make_g(a + 1);
-#pragma unroll
-            for (int b = 0; b < NT; ++b) {
-                f32x4 c4 = dacc[a][b];
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl, bh[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm, bm[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh, bl[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm, bh[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh, bm[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh, bh[b], c4, 0, 0, 0);
-                dacc[a][b] = c4;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();  // the slab aliases the transposition buffers
-    ica_write_slab<NT>(dacc, gpa, sX, part);
+    constexpr int G = ICA_G_LOGCOSH;
+#include "k_ica3_body.inc"
+}
+template <int NT, int G>
+__global__ __launch_bounds__(256, 2) void k_ica3g(const float* __restrict__ X1T, int64_t n, int64_t ld,
+                                                  const bf16x8* __restrict__ Wpk3, int64_t blocks_per_wave,
+                                                  float* __restrict__ part, const int* __restrict__ state) {
+#include "k_ica3_body.inc"
 }
 // K7 on PRE-SPLIT whitened data (round 5).  X1 is constant over the 10 .. 200 iterations of a fit, and k_ica3 split it into bf16
 // planes twice per iteration (row fragments for the first product, transposed fragments for the second): a third or more of the
@@ -354,136 +183,13 @@ __device__ __forceinline__ int ica_xoff(int row, int ch) {
 template <int NT>
 __global__ __launch_bounds__(256, 2) void k_ica3p(const bf16x8* __restrict__ X1pl, int64_t n, const bf16x8* __restrict__ Wpk3,
                                                   int64_t blocks_per_wave, float* __restrict__ part, const int* __restrict__ state) {
-    static_assert(NT == 2 || NT == 4, "whole 32-component chunks only");
-    if (state && state[0]) return;
-    constexpr int NCP = 16 * NT, KCH = NCP / 32, WITEMS = KCH * NT * 192;
-    constexpr int ROWB = NCP * 2, PLANE = 32 * ROWB, IMG = 3 * PLANE, SLAB = 2 * (NCP * NCP + NCP);
-    constexpr int SX = 4 * IMG > SLAB * 4 ? 4 * IMG : SLAB * 4;
-    __shared__ bf16x8 sW[WITEMS];
-    __shared__ __attribute__((aligned(16))) unsigned char sXb[SX];  // per wave [3 planes][32 samples][NCP bf16]; the slab at the end
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 15, q = lane >> 4;
-    for (int e = threadIdx.x; e < WITEMS; e += 256) sW[e] = Wpk3[e];
-    __syncthreads();
-    const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-    unsigned char* const img = sXb + wave * IMG;
-    f32x4 dacc[NT][NT];  // [component tile][x tile]
-    float gpa[NT];
-#pragma unroll
-    for (int a = 0; a < NT; ++a) {
-        gpa[a] = 0.f;
-#pragma unroll
-        for (int b = 0; b < NT; ++b) dacc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const int64_t b0 = wid * blocks_per_wave, b1 = min((n + 31) / 32, b0 + blocks_per_wave);
-    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    bf16x8 xa[2][KCH][3];
-    auto load_a = [&](int64_t blk) {
-        const bf16x8* src = X1pl + (blk * 2 * KCH * 3) * 64 + lane;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int kc = 0; kc < KCH; ++kc)
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) xa[t][kc][pl] = src[((t * KCH + kc) * 3 + pl) * 64];
-    };
-    if (b0 < b1) load_a(b0);
-    const int trq = (lane >> 2) & 3, trp = lane & 3;
-    for (int64_t blk = b0; blk < b1; ++blk) {
-        const int64_t r0 = blk * 32;
-        // the planes go to the wave's image (row 16 t + i, chunk 4 kc + q), from which the second product reads them transposed
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int kc = 0; kc < KCH; ++kc) {
-                unsigned char* a = img + ica_xoff<NT>(16 * t + i, 4 * kc + q);
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<bf16x8*>(a + pl * PLANE) = xa[t][kc][pl];
-            }
-        bf16x8 nwh = sW[lane], nwm = sW[64 + lane], nwl = sW[128 + lane];
-        f32x4 sacc[2][NT];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int u = 0; u < NT; ++u) sacc[t][u] = z4;
-#pragma unroll
-        for (int kc = 0; kc < KCH; ++kc) {
-#pragma unroll
-            for (int u = 0; u < NT; ++u) {
-                const bf16x8 wh = nwh, wm = nwm, wl = nwl;
-                if (kc * NT + u + 1 < KCH * NT) {  // W's pieces are read one tile ahead (LDS latency off the MFMA path)
-                    const bf16x8* sw = sW + (kc * NT + u + 1) * 192 + lane;
-                    nwh = sw[0], nwm = sw[64], nwl = sw[128];
-                }
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    f32x4 c4 = sacc[t][u];
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[t][kc][2], wh, c4, 0, 0, 0);  // smallest terms first
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[t][kc][1], wm, c4, 0, 0, 0);
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[t][kc][0], wl, c4, 0, 0, 0);
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[t][kc][1], wh, c4, 0, 0, 0);
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[t][kc][0], wm, c4, 0, 0, 0);
-                    c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[t][kc][0], wh, c4, 0, 0, 0);
-                    sacc[t][u] = c4;
-                }
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (blk + 1 < b1) load_a(blk + 1);  // next pass's planes land behind tanh and the second product
-        // B operand of the second product: lane (j = i, q), slot e <- X1[r0 + (e < 4 ? 4 q + e : 16 + 4 q + e - 4)][16 b + j], transposed
-        // reads of the image (T10: lane 16 g + 4 q' + p supplies block row q', columns 4 p .. 4 p + 3)
-        bf16x8 bh[NT], bm[NT], bl[NT];
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            const unsigned char* a0 = img + ica_xoff<NT>(4 * q + trq, 2 * b + (trp >> 1)) + 8 * (trp & 1);   // (row + 16: + 16 rows, same swizzle)
-            bh[b] = lds_tr2(a0, a0 + 16 * ROWB);
-            bm[b] = lds_tr2(a0 + PLANE, a0 + PLANE + 16 * ROWB);
-            bl[b] = lds_tr2(a0 + 2 * PLANE, a0 + 2 * PLANE + 16 * ROWB);
-        }
-        // sacc[t][u][r] = S[sample r0 + 16 t + 4 q + r][component 16 u + i].  Rows past n were stored as zero planes: S = 0
-        // and tanh(0) = 0 exactly, so only the g' sum needs masking (last pass).
-        const bool tail = r0 + 32 > n;
-        const float nvalid = tail ? (float)((n > r0 + 4 * q ? (int)min((int64_t)4, n - r0 - 4 * q) : 0) +
-                                            (n > r0 + 16 + 4 * q ? (int)min((int64_t)4, n - r0 - 16 - 4 * q) : 0))
-                                  : 8.0f;
-        bf16x8 gh, gm, gl;
-        auto make_g = [&](int u) {
-            f32x8 g8;
-            float gs = 0.f;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float g = tanh_fast(sacc[t][u][r]);
-                    g8[4 * t + r] = g;
-                    gs = fmaf(-g, g, gs);
-                }
-            gpa[u] += gs + nvalid;
-            split3(g8, gh, gm, gl);
-        };
-        make_g(0);
-        // D[component][x] += sum_samples G[sample][component] X1[sample][x]
-#pragma unroll
-        for (int a = 0; a < NT; ++a) {
-            __builtin_amdgcn_sched_barrier(0);
-            const bf16x8 fh = gh, fm = gm, fl = gl;
-            if (a + 1 < NT) make_g(a + 1);
-#pragma unroll
-            for (int b = 0; b < NT; ++b) {
-                f32x4 c4 = dacc[a][b];
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl, bh[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm, bm[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh, bl[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm, bh[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh, bm[b], c4, 0, 0, 0);
-                c4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh, bh[b], c4, 0, 0, 0);
-                dacc[a][b] = c4;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();  // the slab aliases the images
-    ica_write_slab<NT>(dacc, gpa, reinterpret_cast<float*>(sXb), part);
+    constexpr int G = ICA_G_LOGCOSH;
+#include "k_ica3p_body.inc"
+}
+template <int NT, int G>
+__global__ __launch_bounds__(256, 2) void k_ica3pg(const bf16x8* __restrict__ X1pl, int64_t n, const bf16x8* __restrict__ Wpk3,
+                                                   int64_t blocks_per_wave, float* __restrict__ part, const int* __restrict__ state) {
+#include "k_ica3p_body.inc"
 }
 // combine the per-workgroup slabs in fp64 (fixed order) and drop the padding: GX_gp = [nc*nc | nc].
 // block = 32 outputs x 32 part-lanes (the reduction is latency-bound: many short independent load chains).
@@ -510,23 +216,27 @@ __global__ __launch_bounds__(1024) void k_ica_reduce(const float* __restrict__ p
 }
 
 // generic FastICA step: one block per chunk of 64 samples, fp64
-template <class T>
-__global__ void k_ica_simple(const T* __restrict__ X1T, int64_t n, int nc, int64_t ld, const double* __restrict__ W,
-                             double* __restrict__ part, const int* __restrict__ state) {
+// (the other contrasts keep g' beside g in shared memory: [nc][64] each)
+template <class T, int G>
+__device__ __forceinline__ void ica_simple_body(const T* __restrict__ X1T, int64_t n, int nc, int64_t ld, const double* __restrict__ W,
+                                                double* __restrict__ part, const int* __restrict__ state) {
     if (state && state[0]) return;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* g = reinterpret_cast<double*>(smem_raw);  // [nc][64]
+    double* gd = g + (G == ICA_G_LOGCOSH ? 0 : nc * 64);
     const int64_t s0 = (int64_t)blockIdx.x * 64;
     const int ns = (int)min((int64_t)64, n - s0);
     for (int e = threadIdx.x; e < nc * 64; e += blockDim.x) {
         const int c = e / 64, s = e % 64;
-        double v = 0;
+        double v = 0, vd = 0;
         if (s < ns) {
             double wx = 0;
             for (int j = 0; j < nc; ++j) wx += (sizeof(T) == 4 ? (double)(float)W[c * nc + j] : W[c * nc + j]) * (double)X1T[(s0 + s) * ld + j];
-            v = tanh(wx);
+            if constexpr (G == ICA_G_LOGCOSH) v = tanh(wx);
+            else ica_contrast<G>(wx, v, vd);
         }
         g[e] = v;
+        if constexpr (G != ICA_G_LOGCOSH) gd[e] = vd;
     }
     __syncthreads();
     double* out = part + (int64_t)blockIdx.x * (nc * nc + nc);
@@ -537,10 +247,24 @@ __global__ void k_ica_simple(const T* __restrict__ X1T, int64_t n, int nc, int64
             for (int t = 0; t < ns; ++t) s += g[c * 64 + t] * (double)X1T[(s0 + t) * ld + j];
         } else {
             const int c = e - nc * nc;
-            for (int t = 0; t < ns; ++t) s += 1.0 - g[c * 64 + t] * g[c * 64 + t];
+            if constexpr (G == ICA_G_LOGCOSH) {
+                for (int t = 0; t < ns; ++t) s += 1.0 - g[c * 64 + t] * g[c * 64 + t];
+            } else {
+                for (int t = 0; t < ns; ++t) s += gd[c * 64 + t];
+            }
         }
         out[e] = s;
     }
+}
+template <class T>
+__global__ void k_ica_simple(const T* __restrict__ X1T, int64_t n, int nc, int64_t ld, const double* __restrict__ W,
+                             double* __restrict__ part, const int* __restrict__ state) {
+    ica_simple_body<T, ICA_G_LOGCOSH>(X1T, n, nc, ld, W, part, state);
+}
+template <class T, int G>
+__global__ void k_ica_simple_g(const T* __restrict__ X1T, int64_t n, int nc, int64_t ld, const double* __restrict__ W,
+                               double* __restrict__ part, const int* __restrict__ state) {
+    ica_simple_body<T, G>(X1T, n, nc, ld, W, part, state);
 }
 __global__ void k_sum_parts_state(const double* __restrict__ part, int64_t nparts, int64_t count, double* __restrict__ out,
                                   const int* __restrict__ state) {

@@ -217,6 +217,12 @@ void op_logcosh_rows(Dev*, int dtype, const void* X, int64_t r, int64_t c, int64
 void op_ica_prepare(Dev*, int dtype, const void* X1T, int64_t n, int64_t nc, int64_t ld);
 void op_ica_step(Dev*, int dtype, const void* X1T, int64_t n, int64_t nc, int64_t ld,
                  const double* W, double* GX_gp /* nc*nc + nc contiguous */, const int* state);
+// The same step with another contrast function g in tanh's place: GX[i][j] = sum_s g(w_i . x_s) x_s[j];  gp[i] = sum_s g'(w_i . x_s).
+// contrast = PETAL_ICA_CONTRAST_* >> 4:  1  g(u) = u exp(-u^2/2)   2  g(u) = u^3   (0: what op_ica_step computes).
+// An extension beyond the crate: a device-op layer that does not define it gets algo.cpp's weak default,
+// which refuses the contrast (PETAL_INVALID_INPUT) -- never a silent tanh fit.
+void op_ica_step_g(Dev*, int dtype, const void* X1T, int64_t n, int64_t nc, int64_t ld,
+                   const double* W, double* GX_gp /* nc*nc + nc contiguous */, const int* state, int contrast);
 // ica.rs:334-358 on one workgroup: D = GX/n_total - gp/n_total (.) W; W1 = symdecorr(D); lim; update.
 // state = {done, n_iter}; iter is the 0-based index of this iteration.  W is replaced by W1 unless done.
 // progress (nullable): dev_host_progress()'s array; the kernel publishes {n_iter if converged else 0, iter + 1} there when it

@@ -21,6 +21,12 @@ pub struct PetalMatrix {
 pub const PETAL_OK: c_int = 0;
 pub const PETAL_INVALID_INPUT: c_int = 1;
 pub const PETAL_LINALG_ERROR: c_int = 2;
+/// FastICA contrast function, OR-ed into the `mode` argument of `petal_fastica_fit` (bits 4-7; bits 0-3: the semantics)
+pub const PETAL_ICA_CONTRAST_LOGCOSH: c_int = 0;
+pub const PETAL_ICA_CONTRAST_EXP: c_int = 16;
+pub const PETAL_ICA_CONTRAST_CUBE: c_int = 32;
+pub const PETAL_ICA_SEMANTICS_MASK: c_int = 15;
+pub const PETAL_ICA_CONTRAST_MASK: c_int = 240;
 
 extern "C" {
     pub fn petal_ctx_create(device: c_int, stream: *mut c_void, out: *mut *mut PetalCtx) -> c_int;

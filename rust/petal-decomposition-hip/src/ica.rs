@@ -11,9 +11,31 @@ const MAX_ITER: i64 = 200; // src/ica.rs:216
 /// 0 = textbook (W W^T)^(-1/2) W, 1 = the reference's literal arithmetic.
 const MODE: i32 = 0;
 
+/// The contrast function g of the fixed-point iteration.  `Logcosh` (g = tanh) is the reference's only one (src/ica.rs:383-398);
+/// `Exp` (g(u) = u exp(-u^2/2)) and `Cube` (g(u) = u^3) are an extension of this library.
+#[derive(Debug, Clone, Copy, PartialEq, Eq, Default)]
+pub enum Contrast {
+    #[default]
+    Logcosh,
+    Exp,
+    Cube,
+}
+impl Contrast {
+    fn bits(self) -> i32 {
+        match self {
+            Contrast::Logcosh => ffi::PETAL_ICA_CONTRAST_LOGCOSH,
+            Contrast::Exp => ffi::PETAL_ICA_CONTRAST_EXP,
+            Contrast::Cube => ffi::PETAL_ICA_CONTRAST_CUBE,
+        }
+    }
+}
+
 #[cfg_attr(feature = "serde", derive(serde::Serialize, serde::Deserialize))]
 #[derive(Debug, Clone)]
 pub struct FastIca<A: HipScalar, R = Pcg> {
+    /// not part of the reference's struct, and `transform` does not need it: the serde form stays the crate's
+    #[cfg_attr(feature = "serde", serde(skip))]
+    contrast: Contrast,
     rng: R,
     components: Array2<A>,
     means: Array1<A>,
@@ -60,10 +82,11 @@ impl<A: HipScalar, R: Rng> FastIca<A, R> {
         let mut means = Array1::<A>::default(d);
         let mut n_iter: i64 = 0;
         let x = view(input);
+        let contrast = self.contrast.bits();
         let yv = y.as_ref().map(|y| view(&**y));
         with_ctx(
             |ctx| unsafe {
-                ffi::petal_fastica_fit(ctx, &x, 0, TOL, MAX_ITER, MODE, w_init.as_ptr() as *const c_void,
+                ffi::petal_fastica_fit(ctx, &x, 0, TOL, MAX_ITER, MODE | contrast, w_init.as_ptr() as *const c_void,
                     comps.as_mut_ptr() as *mut c_void, means.as_mut_ptr() as *mut c_void, &mut n_iter,
                     yv.as_ref().map_or(std::ptr::null(), |v| v as *const _))
             },
@@ -78,13 +101,14 @@ impl<A: HipScalar, R: Rng> FastIca<A, R> {
 
 pub struct FastIcaBuilder<R> {
     rng: R,
+    contrast: Contrast,
 }
 impl FastIcaBuilder<Pcg> {
     /// Randomly seeded PCG, like the reference (src/ica.rs:255-260).
     pub fn new() -> Self {
         use rand::SeedableRng;
         let seed: u128 = rand::rng().random();
-        Self { rng: Pcg::from_seed(seed.to_be_bytes()) }
+        Self { rng: Pcg::from_seed(seed.to_be_bytes()), contrast: Contrast::default() }
     }
     pub fn seed(mut self, seed: u128) -> Self {
         use rand::SeedableRng;
@@ -96,8 +120,13 @@ impl Default for FastIcaBuilder<Pcg> {
     fn default() -> Self { Self::new() }
 }
 impl<R: Rng> FastIcaBuilder<R> {
-    pub fn with_rng(rng: R) -> Self { Self { rng } }
+    pub fn with_rng(rng: R) -> Self { Self { rng, contrast: Contrast::default() } }
+    /// The contrast function of the fit (extension: the reference has logcosh only).
+    pub fn contrast(mut self, contrast: Contrast) -> Self {
+        self.contrast = contrast;
+        self
+    }
     pub fn build<A: HipScalar>(self) -> FastIca<A, R> {
-        FastIca { rng: self.rng, components: Array2::default((0, 0)), means: Array1::default(0), n_iter: 0 }
+        FastIca { contrast: self.contrast, rng: self.rng, components: Array2::default((0, 0)), means: Array1::default(0), n_iter: 0 }
     }
 }

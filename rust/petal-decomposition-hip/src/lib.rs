@@ -6,7 +6,7 @@ mod ffi;
 mod ica;
 mod pca;
 
-pub use ica::{FastIca, FastIcaBuilder};
+pub use ica::{Contrast, FastIca, FastIcaBuilder};
 pub use pca::{Pca, PcaBuilder, RandomizedPca, RandomizedPcaBuilder};
 
 use ndarray::{ArrayBase, Data, Ix2};
