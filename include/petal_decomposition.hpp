@@ -11,6 +11,7 @@
 // `Mcg128Xsl64` (rand_pcg) with a Ziggurat StandardNormal -- a restatement of un-vendored third-party code whose
 // exact stream is NOT pinned by any reference test ("stream parity unpinned").
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "petal_hip.h"
+#include "petal_hip_score.h"
 
 namespace petal_decomposition {
 
@@ -175,6 +177,61 @@ struct PcaState {  // src/pca.rs:41-51 / 317-329
         for (size_t i = 0; i < r.size(); ++i) r[i] = singular[i] * singular[i] / total_variance;
         return r;
     }
+    // ---- scores of rows against the fitted model: an extension beyond the crate (petal_hip_score.h) ----
+    std::vector<A> explained_variance() const {  // lambda_j = sigma_j^2 / (n_samples - 1)
+        std::vector<A> r(singular.size());
+        for (size_t i = 0; i < r.size(); ++i) r[i] = singular[i] * singular[i] / A(n_samples - 1);
+        return r;
+    }
+    A noise_variance() const {  // mean variance of the min(n_samples, d) - k discarded directions (scikit-learn's definition)
+        const int64_t rest = std::min<int64_t>(n_samples, int64_t(means.size())) - k;
+        if (rest <= 0) return A(0);
+        double kept = 0;
+        for (const A s : singular) kept += double(s) * double(s);
+        return A((double(total_variance) - kept) / double(n_samples - 1) / double(rest));
+    }
+    // n x 2: [residual, weighted] (weights: k values or empty = all ones), one pass over the input
+    Array2<A> score_rows(const Array2<A>& input, const std::vector<A>& weights) const {
+        const int64_t d = int64_t(means.size());
+        if (input.ncols() != d) throw DecompositionError(DecompositionError::InvalidInput, "# of columns should be " + std::to_string(d));
+        Array2<A> out(input.nrows(), 2);
+        petal_matrix mx = input.view(), mo = out.view();
+        context().check(petal_score_rows(context().get(), &mx, components.data.data(), means.data(), k, d, centering,
+                                         weights.empty() ? nullptr : weights.data(), &mo, nullptr));
+        return out;
+    }
+    std::vector<A> inverse_variances() const {
+        std::vector<A> w = explained_variance();
+        for (A& v : w) {
+            if (!(v > A(0))) throw DecompositionError(DecompositionError::InvalidInput, "a kept component has zero variance");
+            v = A(1) / v;
+        }
+        return w;
+    }
+    std::vector<A> reconstruction_error(const Array2<A>& input) const {  // |xc|^2 - |xc V^T|^2: rounding noise below ~1e-5 |xc|^2 in float
+        const Array2<A> sc = score_rows(input, {});
+        std::vector<A> r(size_t(sc.nrows()));
+        for (int64_t i = 0; i < sc.nrows(); ++i) r[size_t(i)] = sc(i, 0);
+        return r;
+    }
+    std::vector<A> hotelling_t2(const Array2<A>& input) const {
+        const Array2<A> sc = score_rows(input, inverse_variances());
+        std::vector<A> r(size_t(sc.nrows()));
+        for (int64_t i = 0; i < sc.nrows(); ++i) r[size_t(i)] = sc(i, 1);
+        return r;
+    }
+    std::vector<A> score_samples(const Array2<A>& input) const {  // probabilistic-PCA log-likelihood per row (scikit-learn's score_samples)
+        const double s2 = double(noise_variance());
+        if (!(s2 > 0)) throw DecompositionError(DecompositionError::InvalidInput, "the noise variance is not positive (no discarded direction, or an exactly low-rank fit)");
+        const std::vector<A> w = inverse_variances();
+        const int64_t d = int64_t(means.size());
+        double c = double(d) * std::log(2.0 * 3.14159265358979323846) + double(d - k) * std::log(s2);
+        for (const A v : w) c -= std::log(double(v));
+        const Array2<A> sc = score_rows(input, w);
+        std::vector<A> r(size_t(sc.nrows()));
+        for (int64_t i = 0; i < sc.nrows(); ++i) r[size_t(i)] = A(-0.5 * (c + double(sc(i, 0)) / s2 + double(sc(i, 1))));
+        return r;
+    }
 };
 }  // namespace detail
 
@@ -199,6 +256,12 @@ class Pca {  // src/pca.rs:41-232
     }
     Array2<A> transform(const Array2<A>& input) const { return st_.transform(input); }
     Array2<A> inverse_transform(const Array2<A>& input) const { return st_.inverse_transform(input); }
+    // extension beyond the crate (petal_hip_score.h): scores of rows against the fitted model, one pass over the input each
+    std::vector<A> explained_variance() const { return st_.explained_variance(); }
+    A noise_variance() const { return st_.noise_variance(); }
+    std::vector<A> reconstruction_error(const Array2<A>& input) const { return st_.reconstruction_error(input); }
+    std::vector<A> hotelling_t2(const Array2<A>& input) const { return st_.hotelling_t2(input); }
+    std::vector<A> score_samples(const Array2<A>& input) const { return st_.score_samples(input); }
 
   private:
     void inner_fit(const Array2<A>& input, Array2<A>* y) {
@@ -251,6 +314,12 @@ class RandomizedPca {  // src/pca.rs:317-551
     }
     Array2<A> transform(const Array2<A>& input) const { return st_.transform(input); }
     Array2<A> inverse_transform(const Array2<A>& input) const { return st_.inverse_transform(input); }
+    // extension beyond the crate (petal_hip_score.h): scores of rows against the fitted model, one pass over the input each
+    std::vector<A> explained_variance() const { return st_.explained_variance(); }
+    A noise_variance() const { return st_.noise_variance(); }
+    std::vector<A> reconstruction_error(const Array2<A>& input) const { return st_.reconstruction_error(input); }
+    std::vector<A> hotelling_t2(const Array2<A>& input) const { return st_.hotelling_t2(input); }
+    std::vector<A> score_samples(const Array2<A>& input) const { return st_.score_samples(input); }
     static constexpr int64_t N_OVERSAMPLE = 10, N_ITER = 7;  // src/pca.rs:679-680
 
   private:

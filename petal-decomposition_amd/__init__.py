@@ -124,6 +124,11 @@ ABI = [
     ("petal_gemm_atb", C.c_int, [_P, _M, _P, _M, _P, C.POINTER(C.c_double)]),
 ]
 
+# every symbol include/petal_hip_score.h declares (row scores: an extension beyond the crate, kept apart from the mirrored set above)
+ABI_SCORE = [
+    ("petal_score_rows", C.c_int, [_P, _M, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _M, _M]),
+]
+
 
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
@@ -141,7 +146,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h and include/petal_hip_score.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -150,7 +155,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI:
+    for name, res, args in ABI + ABI_SCORE:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -443,6 +448,48 @@ class _PcaModel:
 
     def explained_variance_ratio(self):
         return self._singular * self._singular / self._total_variance
+
+    # scores of rows against the fitted model: an extension beyond the crate (include/petal_hip_score.h)
+    def explained_variance(self):
+        """lambda_j = sigma_j^2 / (n_samples - 1), the variance along each kept component."""
+        return self._singular * self._singular / (self.n_samples - 1)
+
+    def noise_variance(self):
+        """The mean variance of the min(n_samples, d) - k discarded directions, as scikit-learn defines it (0 when none is discarded)."""
+        rest = min(self.n_samples, self._means.shape[0]) - self._k
+        if rest <= 0:
+            return np.asarray(0.0, dtype=self._singular.dtype)[()]
+        s = self._singular.astype(np.float64)
+        return np.asarray((float(self._total_variance) - float(np.sum(s * s))) / (self.n_samples - 1) / rest, dtype=self._singular.dtype)[()]
+
+    def _score(self, x, weights):
+        return score_rows(x, self._components, self._means, weights=weights, centering=self.centering, ctx=self._ctx())[0]
+
+    def reconstruction_error(self, x):
+        """|xc - (xc V^T) V|^2 per row (the Q / SPE statistic), as |xc|^2 - |xc V^T|^2 from one pass over x.  A difference: below about
+        1e-5 |xc|^2 it is rounding noise for float32 input (float64 input: 1e-14)."""
+        return self._score(x, None)[:, 0]
+
+    def hotelling_t2(self, x):
+        """sum_j y_j^2 / lambda_j per row, y = transform(x)."""
+        lam = np.asarray(self.explained_variance(), dtype=np.float64)
+        if not np.all(lam > 0):
+            raise InvalidInput("a kept component has zero variance")
+        return self._score(x, 1.0 / lam)[:, 1]
+
+    def score_samples(self, x):
+        """Log-likelihood of each row under the probabilistic-PCA model (scikit-learn's score_samples), from one pass over x:
+        -1/2 [d log 2 pi + sum_j log lambda_j + (d - k) log s2 + residual / s2 + T^2], s2 = noise_variance()."""
+        lam = np.asarray(self.explained_variance(), dtype=np.float64)
+        s2 = float(self.noise_variance())
+        if not s2 > 0:
+            raise InvalidInput("the noise variance is not positive (no discarded direction, or an exactly low-rank fit)")
+        if not np.all(lam > 0):
+            raise InvalidInput("a kept component has zero variance")
+        d = self._means.shape[0]
+        sc = self._score(x, 1.0 / lam)
+        const = d * np.log(2.0 * np.pi) + float(np.sum(np.log(lam))) + (d - self._k) * np.log(s2)
+        return -0.5 * (const + sc[:, 0] / s2 + sc[:, 1])
 
     def _serde_fields(self) -> dict:
         dt = self._components.dtype if self._components.size or self._means.size else np.dtype(_np_dtype(self._dt))
@@ -903,6 +950,28 @@ def gemm_xp(x, p, mu=None, bias=None, ctx: Optional[Context] = None):
     ctx.check(ctx.lib.petal_gemm_xp(ctx._h, C.byref(mx), muh.ctypes.data if muh is not None else None, ph.ctypes.data, N,
                                     bh.ctypes.data if bh is not None else None, C.byref(mz)))
     return z
+
+
+def score_rows(x, components, means, weights=None, centering=True, want_y=False, ctx: Optional[Context] = None):
+    """(scores, y): scores[:, 0] = max(|xc|^2 - sum_j y_j^2, 0) and scores[:, 1] = sum_j weights_j y_j^2 per row, with xc = x - means
+    (when centering) and y = xc . components^T (k x d components) -- one pass over x (petal_score_rows, include/petal_hip_score.h);
+    y = the projections as transform writes them if wanted, else None.  weights=None means all ones."""
+    ctx = ctx or default_context()
+    keep = []
+    mx = describe(x, keep)
+    comp = _host(components, mx.dtype)
+    if comp.ndim != 2:
+        raise InvalidInput("components should be a k x d matrix")
+    k, d = comp.shape
+    mu = _host(means, mx.dtype, (d,)) if means is not None else np.zeros(d, dtype=_np_dtype(mx.dtype))
+    wh = _host(weights, mx.dtype, (k,)) if weights is not None else None
+    out = _alloc_like(x, mx.rows, 2, mx.dtype)
+    mo = describe(out, keep)
+    y = _alloc_like(x, mx.rows, k, mx.dtype) if want_y else None
+    my = describe(y, keep) if want_y else None
+    ctx.check(ctx.lib.petal_score_rows(ctx._h, C.byref(mx), comp.ctypes.data, mu.ctypes.data, k, d, int(bool(centering)),
+                                       wh.ctypes.data if wh is not None else None, C.byref(mo), C.byref(my) if want_y else None))
+    return out, y
 
 
 def power_pass(x, p, mu=None, want_z=False, ctx: Optional[Context] = None):

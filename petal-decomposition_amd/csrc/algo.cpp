@@ -1147,6 +1147,19 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
 
 // ---------------------------------------------------------------------------------------------
 // free fn transform (pca.rs:726-750) / FastIca::transform (ica.rs:120-131)
+// do two device matrices share bytes?
+static bool device_spans_overlap(const petal_matrix& a, const petal_matrix& b) {
+    if (a.space != PETAL_DEVICE || b.space != PETAL_DEVICE || a.rows <= 0 || a.cols <= 0 || b.rows <= 0 || b.cols <= 0) return false;
+    const auto span = [&](const petal_matrix& m, uintptr_t& lo, uintptr_t& hi) {
+        const int64_t last = (m.rows - 1) * std::abs(m.row_stride) + (m.cols - 1) * std::abs(m.col_stride) + 1;
+        const uintptr_t p0 = reinterpret_cast<uintptr_t>(m.data), ext = size_t(last) * dtype_size(m.dtype);
+        lo = (m.row_stride < 0 || m.col_stride < 0) ? p0 - std::min<uintptr_t>(p0, ext) : p0;   // (a reversed view reaches below its base)
+        hi = p0 + ext;
+    };
+    uintptr_t alo, ahi, blo, bhi;
+    span(a, alo, ahi); span(b, blo, bhi);
+    return alo < bhi && blo < ahi;
+}
 // May the product kernel write its n x cols result straight into the caller's matrix?  A device matrix of the same type with unit
 // column stride, no padding columns to drop (cols a multiple of 16) and 16-byte aligned rows: then there is no staging buffer and
 // no copy-out pass (1e6 x 64 floats: 0.15 ms of a 0.9 ms transform).  The shape / type checks of emit() are made here as well.
@@ -1159,18 +1172,7 @@ static bool writes_in_place(const petal_matrix& out, int dtype, int64_t n, int64
           (size_t(out.row_stride) * esz) % 16 == 0 && (reinterpret_cast<uintptr_t>(out.data) & 15) == 0))
         return false;
     // (an output that overlaps the input keeps the staged form: the product would read rows it has already overwritten)
-    if (in.space == PETAL_DEVICE && in.rows > 0 && in.cols > 0) {
-        const auto span = [&](const petal_matrix& m, uintptr_t& lo, uintptr_t& hi) {
-            const int64_t last = (m.rows - 1) * std::abs(m.row_stride) + (m.cols - 1) * std::abs(m.col_stride) + 1;
-            const uintptr_t p0 = reinterpret_cast<uintptr_t>(m.data), ext = size_t(last) * dtype_size(m.dtype);
-            lo = (m.row_stride < 0 || m.col_stride < 0) ? p0 - std::min<uintptr_t>(p0, ext) : p0;   // (a reversed view reaches below its base)
-            hi = p0 + ext;
-        };
-        uintptr_t alo, ahi, blo, bhi;
-        span(in, alo, ahi); span(out, blo, bhi);
-        if (alo < bhi && blo < ahi) return false;
-    }
-    return true;
+    return !device_spans_overlap(in, out);
 }
 // k x d components (the caller's type, row-major) -> the fp64 operand the product kernels take: P[i][j] = comp[j][i] (transposed = true,
 // dp x kp) or P[j][i] = comp[j][i] (kp x dp), zero padded
@@ -1228,6 +1230,75 @@ void inverse_transform(petal_ctx& c, const petal_matrix& y, const void* componen
     op_gemm_xp(c.dev, dt, Y.p, Y.n, kp, Y.ld, nullptr, P.f64(), dp, dp, centering ? muT.p : nullptr, in_place ? x_out.data : Xo.p,
                in_place ? x_out.row_stride : dp, nullptr);
     if (!in_place) emit(c, dt, Xo.p, Y.n, d, dp, x_out);
+    dev_sync(c.dev);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row scores against a fitted projection (include/petal_hip_score.h; an extension beyond the crate): residual and weighted energy of
+// every row from the one pass of the product kernel.  A device-op layer may lack the op (the host simulation does): this default stands
+// in wherever no strong definition is linked, and refuses -- after every check of the arguments has been made.
+__attribute__((weak)) void op_gemm_xp_scores(Dev*, int, const void*, int64_t, int64_t, int64_t, const void*, const double*, int64_t, int64_t,
+                                             const void*, void*, int64_t, void*, int64_t) {
+    invalid_input("row scores not available in this device-op layer");
+}
+void score_rows(petal_ctx& c, const petal_matrix& x, const void* components, const void* means, int64_t k, int64_t d, bool centering,
+                const void* weights, const petal_matrix& out, const petal_matrix* y_out) {
+    check_matrix(x, "input");
+    if (x.cols != d) invalid_input("# of columns should be " + std::to_string(d));  // as transform
+    if (k < 0) invalid_input("negative parameter");
+    const int dt = x.dtype;
+    const int64_t n = x.rows;
+    check_matrix(out, "output");
+    if (out.dtype != dt) invalid_input("output dtype differs from input dtype");
+    if (out.rows != n || out.cols != 2) invalid_input("output has the wrong shape");
+    if (y_out) {
+        check_matrix(*y_out, "output");
+        if (y_out->dtype != dt) invalid_input("output dtype differs from input dtype");
+        if (y_out->rows != n || y_out->cols != k) invalid_input("output has the wrong shape");
+    }
+    if (k > 0 && d > 0 && !components) invalid_input("components must not be null");
+    if (centering && d > 0 && !means) invalid_input("means must not be null");
+    if (weights)
+        for (int64_t j = 0; j < k; ++j)
+            if (!std::isfinite(get_elem(weights, dt, j))) invalid_input("weights should be finite");
+    if (n == 0) return;
+    const size_t esz = dtype_size(dt);
+    if (d == 0) {   // no columns: every projection and every score is zero
+        const int64_t w = std::max<int64_t>(k, 2);
+        DBuf Zr(c.dev, esz * size_t(n) * w);
+        dev_memset(c.dev, Zr.p, 0, Zr.bytes);
+        emit(c, dt, Zr.p, n, 2, w, out);
+        if (y_out) emit(c, dt, Zr.p, n, k, w, *y_out);
+        dev_sync(c.dev);
+        return;
+    }
+    DevMat X = ingest(c, x);
+    const int64_t dp = X.dp, kp = round_up(k, 16);
+    const bool y_in_place = y_out && k > 0 && writes_in_place(*y_out, dt, n, k, x) && !device_spans_overlap(*y_out, out);
+    const bool st_in_place = out.space == PETAL_DEVICE && out.col_stride == 1 && out.row_stride >= 2 && !device_spans_overlap(x, out);
+    DBuf P, W, muT(c.dev, esz * dp);
+    if (k > 0) {
+        const std::vector<double> hP = components_operand(components, dt, k, d, dp, kp, true);
+        P = DBuf(c.dev, sizeof(double) * dp * kp);
+        dev_h2d_async(c.dev, P.p, hP.data(), P.bytes);
+        if (weights) {
+            std::vector<char> hw(esz * kp, 0);
+            std::memcpy(hw.data(), weights, esz * k);
+            W = DBuf(c.dev, hw.size());
+            dev_h2d_async(c.dev, W.p, hw.data(), W.bytes);
+        }
+    }
+    std::vector<char> hmu(esz * dp, 0);
+    if (centering) std::memcpy(hmu.data(), means, esz * d);
+    dev_h2d_async(c.dev, muT.p, hmu.data(), muT.bytes);
+    DBuf Y, S;
+    if (y_out && k > 0 && !y_in_place) Y = DBuf(c.dev, esz * size_t(n) * kp);
+    if (!st_in_place) S = DBuf(c.dev, esz * size_t(n) * 2);
+    void* Z = !(y_out && k > 0) ? nullptr : (y_in_place ? y_out->data : Y.p);
+    op_gemm_xp_scores(c.dev, dt, X.p, n, dp, X.ld, centering ? muT.p : nullptr, P.f64(), kp, kp, weights && k > 0 ? W.p : nullptr, Z,
+                      y_in_place ? y_out->row_stride : kp, st_in_place ? out.data : S.p, st_in_place ? out.row_stride : 2);
+    if (!st_in_place) emit(c, dt, S.p, n, 2, 2, out);
+    if (y_out && k > 0 && !y_in_place) emit(c, dt, Y.p, n, k, kp, *y_out);
     dev_sync(c.dev);
 }
 

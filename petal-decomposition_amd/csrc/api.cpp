@@ -5,6 +5,7 @@
 #include <new>
 
 #include "ctx.h"
+#include "../../include/petal_hip_score.h"
 
 using namespace petal;
 
@@ -187,6 +188,15 @@ int petal_inverse_transform(petal_ctx* ctx, const petal_matrix* y, const void* c
         need(y, "y");
         need(x_out, "x_out");
         inverse_transform(*ctx, *y, components, means, k, d, centering != 0, *x_out);
+    });
+}
+
+int petal_score_rows(petal_ctx* ctx, const petal_matrix* x, const void* components, const void* means, int64_t k, int64_t d,
+                     int centering, const void* weights, const petal_matrix* out, const petal_matrix* y_out) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(out, "out");
+        score_rows(*ctx, *x, components, means, k, d, centering != 0, weights, *out, y_out);
     });
 }
 

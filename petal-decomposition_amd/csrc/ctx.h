@@ -92,6 +92,8 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
              void* singular, void* total_variance, const petal_matrix* y_out);
 void transform(petal_ctx& c, const petal_matrix& x, const void* components, const void* means, int64_t k, int64_t d,
                bool centering, const petal_matrix& y_out);
+void score_rows(petal_ctx& c, const petal_matrix& x, const void* components, const void* means, int64_t k, int64_t d, bool centering,
+                const void* weights, const petal_matrix& out, const petal_matrix* y_out);
 void inverse_transform(petal_ctx& c, const petal_matrix& y, const void* components, const void* means, int64_t k,
                        int64_t d, bool centering, const petal_matrix& x_out);
 void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, double tol, int64_t max_iter, int mode,

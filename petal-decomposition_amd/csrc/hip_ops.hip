@@ -569,6 +569,7 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #include "kernels/k_gemm_k2.inc"   // K2: k_atb_mfma (fp32 MFMA), k_atb3 (split-product)
 #include "kernels/k_pow3.inc"   // K3: the fused power-iteration pass (k_pow3, k_pow3f)
 #include "kernels/k_gemm_f64.inc"   // the fp64-MFMA products (k_atb_f64, k_xp_f64)
+#include "kernels/k_gemm_scores.inc"   // K1 with the row-score epilogue (k_xp3s, k_xp_mfma_s, k_xp_f64s, k_xp_simple_s)
 #include "kernels/k_ica_step.inc"   // K7: the fused FastICA step (k_ica_mfma, k_ica3, k_ica3p, k_ica_reduce) and its exp / cube forms (k_ica*_g; bodies in k_ica*_body.inc)
 #include "kernels/k_smallmat.inc"   // fp64 small-matrix kernels: k_dgemm, k_trsm_pack, k_trsm_left_pack, k_chol_inv2, k_chol_rt4, Jacobi solvers
 #include "kernels/k_eigen.inc"   // the two-stage symmetric eigen-solver, the polar iteration / FastICA tail, result kernels

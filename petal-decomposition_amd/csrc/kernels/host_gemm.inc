@@ -475,6 +475,118 @@ static void gemm_xp_impl(Dev* d, int dt, const void* X, int64_t n, int64_t K, in
     }
 }
 
+// Row scores from the product kernels' accumulators (k_gemm_scores.inc); dispatched like gemm_xp_impl.  Column panels are launched in
+// order on the one stream and each updates the per-row state st: a fixed order, no atomics.
+void op_gemm_xp_scores(Dev* d, int dt, const void* X, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* P, int64_t N,
+                       int64_t ldp, const void* wts, void* Z, int64_t ldz, void* st, int64_t ldst) {
+    if (n == 0) return;
+    const bool mfma = dt == F32 && K % 16 == 0 && K > 0 && ldx % 4 == 0 && aligned16(X) && (!mu || aligned16(mu)) && n >= 64 &&
+                      K < (1 << 24) && N < (1 << 24) && N % 16 == 0 && N > 0 && ldz % 4 == 0 && aligned16(Z) && (!wts || aligned16(wts));
+    const bool mfma64 = dt == F64 && K % 8 == 0 && K > 0 && ldx % 2 == 0 && aligned16(X) && (!mu || aligned16(mu)) && n >= 64 &&
+                        K < (1 << 24) && N < (1 << 24) && N % 16 == 0 && N > 0;
+    const int NTtot = cdiv(N, 16);
+    const int npass = cdiv(NTtot, 5);   // panels of <= 5 tiles, the tiles spread evenly over them
+    TagScope ts(d);   // (the product launches, bracketed when the caller tagged them: as gemm_xp_impl)
+    if (mfma64) {
+        const int64_t total = (K / 8) * (int64_t)NTtot * 64;
+        f64x2* Ppk = (f64x2*)dev_alloc(d, sizeof(f64x2) * total);
+        hipLaunchKernelGGL(k_pack_p64, dim3(cdiv(total, 256)), dim3(256), 0, d->stream, P, K, N, ldp, Ppk, NTtot, total);
+        launch_check();
+        const int blocks = cdiv(n, 128);
+        for (int nt0 = 0, pass = 0; nt0 < NTtot; ++pass) {
+            const int w = (NTtot - nt0 + (npass - pass) - 1) / (npass - pass);
+#define XPS_LAUNCH(NTv)                                                                                                                   \
+            do {                                                                                                                            \
+                if (mu) hipLaunchKernelGGL((k_xp_f64s<NTv, true>), dim3(blocks), dim3(256), 0, d->stream, (const double*)X, n, (int)K, ldx, (const double*)mu, Ppk, NTtot, nt0, (int)N, (double*)Z, ldz, (const double*)wts, (double*)st, ldst); \
+                else hipLaunchKernelGGL((k_xp_f64s<NTv, false>), dim3(blocks), dim3(256), 0, d->stream, (const double*)X, n, (int)K, ldx, (const double*)mu, Ppk, NTtot, nt0, (int)N, (double*)Z, ldz, (const double*)wts, (double*)st, ldst); \
+            } while (0)
+            switch (w) {
+                case 5: XPS_LAUNCH(5); break;
+                case 4: XPS_LAUNCH(4); break;
+                case 3: XPS_LAUNCH(3); break;
+                case 2: XPS_LAUNCH(2); break;
+                default: XPS_LAUNCH(1); break;
+            }
+#undef XPS_LAUNCH
+            launch_check();
+            nt0 += w;
+        }
+        ts.stop();
+        dev_free(d, Ppk);
+        return;
+    }
+    if (!mfma) {
+        DISPATCH_T(dt, hipLaunchKernelGGL(k_xp_simple_s<T>, dim3((unsigned)n), dim3(64), 0, d->stream, (const T*)X, n, K, ldx, (const T*)mu, P, N,
+                                          ldp, (T*)Z, ldz, (const T*)wts, (T*)st, ldst));
+        launch_check();
+        ts.stop();
+        return;
+    }
+    const float* Xf = (const float*)X; const float* muf = (const float*)mu; const float* wf = (const float*)wts;
+    float* Zf = (float*)Z; float* stf = (float*)st;
+    const int blocks = cdiv(n, 256);
+    if (gemm_split_product(d)) {   // (three-plane operands in every mode: these scores are results, not steering)
+        const int64_t nch = (K + 31) / 32, total = nch * NTtot * 64;
+        bf16x8* Ppk3 = (bf16x8*)dev_alloc(d, sizeof(bf16x8) * total * 3);
+        hipLaunchKernelGGL(k_pack_p3, dim3(cdiv(total, 256)), dim3(256), 0, d->stream, P, K, N, ldp, Ppk3, NTtot, total);
+        launch_check();
+        for (int nt0 = 0, pass = 0; nt0 < NTtot; ++pass) {
+            const int w = (NTtot - nt0 + (npass - pass) - 1) / (npass - pass);
+            const size_t lds = sizeof(bf16x8) * 2 * w * 64 * 3 + sizeof(float) * 32 * nch;
+#define XPS_LAUNCH(NTv)                                                                                                                   \
+            do {                                                                                                                            \
+                if (lds > 64 * 1024) set_max_lds(d, muf ? reinterpret_cast<const void*>(k_xp3s<NTv, true>) : reinterpret_cast<const void*>(k_xp3s<NTv, false>)); \
+                if (muf) hipLaunchKernelGGL((k_xp3s<NTv, true>), dim3(blocks), dim3(256), lds, d->stream, Xf, n, (int)K, ldx, muf, Ppk3, NTtot, nt0, (int)N, Zf, ldz, wf, stf, ldst); \
+                else hipLaunchKernelGGL((k_xp3s<NTv, false>), dim3(blocks), dim3(256), lds, d->stream, Xf, n, (int)K, ldx, muf, Ppk3, NTtot, nt0, (int)N, Zf, ldz, wf, stf, ldst); \
+            } while (0)
+            switch (w) {
+                case 5: XPS_LAUNCH(5); break;
+                case 4: XPS_LAUNCH(4); break;
+                case 3: XPS_LAUNCH(3); break;
+                case 2: XPS_LAUNCH(2); break;
+                default: XPS_LAUNCH(1); break;
+            }
+#undef XPS_LAUNCH
+            launch_check();
+            nt0 += w;
+        }
+        ts.stop();
+        dev_free(d, Ppk3);
+        return;
+    }
+    float* Ppk = (float*)dev_alloc(d, sizeof(float) * (K / 16) * NTtot * 64 * 4);
+    hipLaunchKernelGGL(k_pack_p, dim3(cdiv((K / 16) * (int64_t)NTtot * 64, 256)), dim3(256), 0, d->stream, P, K, N, ldp, Ppk, NTtot);
+    launch_check();
+    // Panels of <= 4 tiles (k_xp_mfma_s), spread evenly when centring.  Without centring a 3-tile panel is not launched: that form takes
+    // 194 registers, two waves per SIMD where k_xp_mfma<4, 3, false, false> runs three -- the panels are then 4, 2 and 1 tiles wide.
+    const int npass4 = cdiv(NTtot, 4);
+    for (int nt0 = 0, pass = 0; nt0 < NTtot; ++pass) {
+        const int rem = NTtot - nt0;
+        const int w = muf ? (rem + (npass4 - pass) - 1) / (npass4 - pass) : (rem >= 4 ? 4 : rem >= 2 ? 2 : 1);
+#define XPS_LAUNCH(NTv)                                                                                                                   \
+        do {                                                                                                                                \
+            if (muf) hipLaunchKernelGGL((k_xp_mfma_s<NTv, true>), dim3(blocks), dim3(256), 0, d->stream, Xf, n, (int)K, ldx, muf, Ppk, NTtot, nt0, (int)N, Zf, ldz, wf, stf, ldst); \
+            else hipLaunchKernelGGL((k_xp_mfma_s<NTv, false>), dim3(blocks), dim3(256), 0, d->stream, Xf, n, (int)K, ldx, muf, Ppk, NTtot, nt0, (int)N, Zf, ldz, wf, stf, ldst); \
+        } while (0)
+        switch (w) {
+            case 4: XPS_LAUNCH(4); break;
+            case 3: hipLaunchKernelGGL((k_xp_mfma_s<3, true>), dim3(blocks), dim3(256), 0, d->stream, Xf, n, (int)K, ldx, muf, Ppk, NTtot, nt0, (int)N, Zf, ldz, wf, stf, ldst); break;   // (centring only, see above)
+            case 2: XPS_LAUNCH(2); break;
+            default: {   // one tile: 32-row wave tiles (k_xp_mfma_s)
+                const int blocks2 = cdiv(n, 128);
+                if (muf) hipLaunchKernelGGL((k_xp_mfma_s<1, true, 2>), dim3(blocks2), dim3(256), 0, d->stream, Xf, n, (int)K, ldx, muf, Ppk, NTtot, nt0, (int)N, Zf, ldz, wf, stf, ldst);
+                else hipLaunchKernelGGL((k_xp_mfma_s<1, false, 2>), dim3(blocks2), dim3(256), 0, d->stream, Xf, n, (int)K, ldx, muf, Ppk, NTtot, nt0, (int)N, Zf, ldz, wf, stf, ldst);
+                break;
+            }
+        }
+#undef XPS_LAUNCH
+        launch_check();
+        nt0 += w;
+    }
+    ts.stop();
+    dev_free(d, Ppk);
+}
+
 template <int NT>
 static void launch_atb(Dev* d, const float* A, int64_t lda, int M, const float* muA, const float* B, int64_t ldb, int N,
                        int n0col, const float* muB, int64_t n, int64_t chunk, float* part, int nsplit) {

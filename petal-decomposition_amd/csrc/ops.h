@@ -133,6 +133,13 @@ void op_gemm_xp_prod_absmax(Dev*, int dtype, const void* X, int64_t n, int64_t K
 void op_gemm_xp_absmax(Dev*, int dtype, const void* X, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* P, int64_t N,
                        int64_t ldp, void* Z, int64_t ldz, int64_t row_offset, double* absmax, double* idx, double* sign,
                        bool store_product = true);
+// Row scores of the projection Y = (X - mu) . P, from the product kernel's accumulators in its one pass over X (an extension beyond the
+// crate; a device-op layer may lack it -- algo.cpp holds a weak default that refuses):
+//   st[i][0] = max(|xc_i|^2 - sum_j Y_ij^2, 0),  st[i][1] = sum_j wts[j] Y_ij^2      (st: device, n x 2 in dtype, leading dimension ldst)
+// wts (nullable = all ones): device, N values in dtype.  Z (nullable, ldz): also receives Y, bit for bit op_gemm_xp's.  N == 0 is legal (q only; it takes the
+// any-shape kernel, one wave per row: the slow path).
+void op_gemm_xp_scores(Dev*, int dtype, const void* X, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* P, int64_t N,
+                       int64_t ldp, const void* wts, void* Z, int64_t ldz, void* st, int64_t ldst);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.

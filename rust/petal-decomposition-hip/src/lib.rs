@@ -3,6 +3,7 @@
 //! image) -- see Cargo.toml.  Model state lives in these structs exactly as in the reference
 //! (`src/pca.rs:41-51, 317-329`, `src/ica.rs:41-50`), so serde persistence keeps its field names.
 mod ffi;
+mod ffi_score;
 mod ica;
 mod pca;
 

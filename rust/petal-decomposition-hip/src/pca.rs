@@ -1,5 +1,5 @@
 //! `Pca` (`src/pca.rs:41-231` of the reference) and `RandomizedPca` (`src/pca.rs:317-663`) over the C ABI.
-use crate::{ffi, view, with_ctx, DecompositionError, HipScalar};
+use crate::{ffi, ffi_score, view, with_ctx, DecompositionError, HipScalar};
 use ndarray::{Array1, Array2, ArrayBase, Data, Ix2};
 use rand::Rng;
 use rand_distr::StandardNormal;
@@ -46,6 +46,25 @@ impl<A: HipScalar> Pca<A> {
     }
     pub fn inverse_transform<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array2<A>, DecompositionError> {
         inverse_transform(input, &self.components, &self.means, self.centering)
+    }
+
+    // ---- scores of rows against the fitted model: an extension beyond the crate (include/petal_hip_score.h) ----
+    /// lambda_j = sigma_j^2 / (n_samples - 1).
+    pub fn explained_variance(&self) -> Array1<A> { explained_variance(&self.singular, self.n_samples) }
+    /// Mean variance of the min(n_samples, d) - k discarded directions, as scikit-learn defines it.
+    pub fn noise_variance(&self) -> A { noise_variance(&self.singular, self.total_variance, self.n_samples, self.means.len()) }
+    /// |xc|^2 - |xc V^T|^2 per row from one pass over the input (rounding noise below about 1e-5 |xc|^2 for f32).
+    pub fn reconstruction_error<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array1<A>, DecompositionError> {
+        Ok(score_rows(input, &self.components, &self.means, self.centering, None)?.column(0).to_owned())
+    }
+    /// Hotelling's T^2: sum_j y_j^2 / lambda_j per row.
+    pub fn hotelling_t2<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array1<A>, DecompositionError> {
+        let w = inverse_variances(&self.explained_variance())?;
+        Ok(score_rows(input, &self.components, &self.means, self.centering, Some(&w))?.column(1).to_owned())
+    }
+    /// Log-likelihood of each row under the probabilistic-PCA model (scikit-learn's `score_samples`).
+    pub fn score_samples<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array1<A>, DecompositionError> {
+        score_samples(input, &self.components, &self.means, self.centering, &self.explained_variance(), self.noise_variance())
     }
 
     fn inner_fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, y: Option<&mut Array2<A>>) -> Result<(), DecompositionError> {
@@ -136,6 +155,25 @@ impl<A: HipScalar, R: Rng> RandomizedPca<A, R> {
     }
     pub fn inverse_transform<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array2<A>, DecompositionError> {
         inverse_transform(input, &self.components, &self.means, self.centering)
+    }
+
+    // ---- scores of rows against the fitted model: an extension beyond the crate (include/petal_hip_score.h) ----
+    /// lambda_j = sigma_j^2 / (n_samples - 1).
+    pub fn explained_variance(&self) -> Array1<A> { explained_variance(&self.singular, self.n_samples) }
+    /// Mean variance of the min(n_samples, d) - k discarded directions, as scikit-learn defines it.
+    pub fn noise_variance(&self) -> A { noise_variance(&self.singular, self.total_variance, self.n_samples, self.means.len()) }
+    /// |xc|^2 - |xc V^T|^2 per row from one pass over the input (rounding noise below about 1e-5 |xc|^2 for f32).
+    pub fn reconstruction_error<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array1<A>, DecompositionError> {
+        Ok(score_rows(input, &self.components, &self.means, self.centering, None)?.column(0).to_owned())
+    }
+    /// Hotelling's T^2: sum_j y_j^2 / lambda_j per row.
+    pub fn hotelling_t2<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array1<A>, DecompositionError> {
+        let w = inverse_variances(&self.explained_variance())?;
+        Ok(score_rows(input, &self.components, &self.means, self.centering, Some(&w))?.column(1).to_owned())
+    }
+    /// Log-likelihood of each row under the probabilistic-PCA model (scikit-learn's `score_samples`).
+    pub fn score_samples<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array1<A>, DecompositionError> {
+        score_samples(input, &self.components, &self.means, self.centering, &self.explained_variance(), self.noise_variance())
     }
 
     fn inner_fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, y: Option<&mut Array2<A>>) -> Result<(), DecompositionError> {
@@ -243,4 +281,62 @@ pub(crate) fn inverse_transform<A: HipScalar, S: Data<Elem = A>>(
     )?;
     let _ = &mut x_out;
     Ok(x_out)
+}
+
+fn explained_variance<A: HipScalar>(singular: &Array1<A>, n_samples: usize) -> Array1<A> {
+    let nm1 = n_samples as f64 - 1.0;
+    singular.mapv(|s| A::from_f64(s.to_f64() * s.to_f64() / nm1))
+}
+
+fn noise_variance<A: HipScalar>(singular: &Array1<A>, total_variance: A, n_samples: usize, d: usize) -> A {
+    let rest = n_samples.min(d) as i64 - singular.len() as i64;
+    if rest <= 0 {
+        return A::from_f64(0.0);
+    }
+    let kept: f64 = singular.iter().map(|s| s.to_f64() * s.to_f64()).sum();
+    A::from_f64((total_variance.to_f64() - kept) / (n_samples as f64 - 1.0) / rest as f64)
+}
+
+fn inverse_variances<A: HipScalar>(lambda: &Array1<A>) -> Result<Array1<A>, DecompositionError> {
+    if lambda.iter().any(|l| !(l.to_f64() > 0.0)) {
+        return Err(DecompositionError::InvalidInput("a kept component has zero variance".into()));
+    }
+    Ok(lambda.mapv(|l| A::from_f64(1.0 / l.to_f64())))
+}
+
+/// n x 2 = [residual, weighted] (include/petal_hip_score.h)
+pub(crate) fn score_rows<A: HipScalar, S: Data<Elem = A>>(
+    input: &ArrayBase<S, Ix2>, components: &Array2<A>, means: &Array1<A>, centering: bool, weights: Option<&Array1<A>>,
+) -> Result<Array2<A>, DecompositionError> {
+    let (k, d) = components.dim();
+    let mut out = Array2::<A>::default((input.nrows(), 2));
+    let (x, ov) = (view(input), view(&out));
+    with_ctx(
+        |ctx| unsafe {
+            ffi_score::petal_score_rows(ctx, &x, components.as_ptr() as *const c_void, means.as_ptr() as *const c_void,
+                k as i64, d as i64, centering as i32, weights.map_or(std::ptr::null(), |w| w.as_ptr() as *const c_void), &ov,
+                std::ptr::null())
+        },
+        || (),
+    )?;
+    let _ = &mut out; // written through ov
+    Ok(out)
+}
+
+fn score_samples<A: HipScalar, S: Data<Elem = A>>(
+    input: &ArrayBase<S, Ix2>, components: &Array2<A>, means: &Array1<A>, centering: bool, lambda: &Array1<A>, noise: A,
+) -> Result<Array1<A>, DecompositionError> {
+    let s2 = noise.to_f64();
+    if !(s2 > 0.0) {
+        return Err(DecompositionError::InvalidInput(
+            "the noise variance is not positive (no discarded direction, or an exactly low-rank fit)".into(),
+        ));
+    }
+    let w = inverse_variances(lambda)?;
+    let (k, d) = components.dim();
+    let c = d as f64 * (2.0 * std::f64::consts::PI).ln()
+        + lambda.iter().map(|l| l.to_f64().ln()).sum::<f64>()
+        + (d - k) as f64 * s2.ln();
+    let sc = score_rows(input, components, means, centering, Some(&w))?;
+    Ok(Array1::from_iter(sc.rows().into_iter().map(|r| A::from_f64(-0.5 * (c + r[0].to_f64() / s2 + r[1].to_f64())))))
 }
