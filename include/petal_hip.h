@@ -155,7 +155,7 @@ int         petal_ctx_set_profiling(petal_ctx* ctx, int profiling);
 int         petal_ctx_set_gemm_mode(petal_ctx* ctx, int mode);
 /* Options of a ctx.  Every switch that selects WHICH arithmetic or kernel form a fit runs is an option of the ctx: its default comes
  * from the environment variable named with it, read ONCE at petal_ctx_create; afterwards only petal_ctx_set_option changes it (no
- * library call reads the environment).  Options 0 - 8 change numerics within the documented parity bar; 9 - 13 are test / tooling aids.
+ * library call reads the environment).  Options 0 - 8 change numerics within the documented parity bar; 9 - 15 are test / tooling aids.
  * Unknown option: PETAL_INVALID_INPUT. */
 #define PETAL_OPT_TWO_PLANE_OPERANDS 0   /* (1) optimistic first run of an fp32 RandomizedPca fit: sketch matrix and re-based iterates on two bf16
                                             planes behind the spectrum verdict; 0 = three planes throughout            PETAL_NO_P2=1 -> 0 */
@@ -178,6 +178,10 @@ int         petal_ctx_set_gemm_mode(petal_ctx* ctx, int mode);
 #define PETAL_OPT_POISON 13              /* (0) every workspace block is filled with NaN patterns when handed out          PETAL_POISON=1 */
 #define PETAL_OPT_FORCE_COLLECTIVE 14    /* (0) a one-rank ctx with a collective installed still takes the sharded code path
                                                                                                                          PETAL_FORCE_COLLECTIVE=1 */
+#define PETAL_OPT_STEERING_HOOK 15       /* (0) test hook: petal_gemm_xp, petal_gemm_atb and petal_power_pass (without z) ask for the STEERING forms
+                                            of their kernels -- operands rounded to two bf16 planes, four piece products -- which only a fit
+                                            reaches otherwise; a no-op outside the split-product modes and under PETAL_OPT_STEERING_PASSES = 0.
+                                            No environment variable. */
 int         petal_ctx_set_option(petal_ctx* ctx, int option, double value);
 int         petal_ctx_get_option(const petal_ctx* ctx, int option, double* value);
 int         petal_get_stats(const petal_ctx* ctx, petal_stats* out);

@@ -39,6 +39,7 @@ Dev* dev_create(int, void*, char*, size_t) {
     d->opt[OPT_ROW_PAD] = on("PETAL_NO_ROW_PAD") ? 0 : 1;
     d->opt[OPT_EIGH_JACOBI] = on("PETAL_EIGH_JACOBI") ? 1 : 0;
     d->opt[OPT_POISON] = 0;
+    d->opt[OPT_STEERING_HOOK] = 0;
     return d;
 }
 void dev_set_option(Dev* d, int opt, double value) {

@@ -1668,7 +1668,11 @@ void gemm_xp(petal_ctx& c, const petal_matrix& x, const void* mu, const void* p,
     c.stats.pass_flops = 2.0 * double(X.n) * double(x.cols) * double(N);
     c.stats.pass_bytes = double(dtype_size(dt)) * (double(X.n) * x.cols + double(X.n) * N + double(x.cols) * N);
     dev_set_tag(c.dev, TAG_XP);
-    op_gemm_xp(c.dev, dt, X.p, X.n, K, X.ld, mu ? muT.p : nullptr, P.f64(), NP, NP, bias ? bT.p : nullptr, Z.p, NP, nullptr);
+    // (test hook PETAL_OPT_STEERING_HOOK: the product as a steering pass of a fit asks for it -- P on two planes, and X too in the wide form)
+    if (dev_option(c.dev, OPT_STEERING_HOOK) != 0)
+        op_gemm_xp(c.dev, dt, X.p, X.n, K, X.ld, mu ? muT.p : nullptr, P.f64(), NP, NP, bias ? bT.p : nullptr, Z.p, NP, nullptr, /*p_planes=*/2, /*steering=*/true);
+    else
+        op_gemm_xp(c.dev, dt, X.p, X.n, K, X.ld, mu ? muT.p : nullptr, P.f64(), NP, NP, bias ? bT.p : nullptr, Z.p, NP, nullptr);
     dev_set_tag(c.dev, TAG_NONE);
     emit(c, dt, Z.p, X.n, N, NP, z_out);
     finish_stats(c, timer);
@@ -1698,7 +1702,9 @@ void power_pass(petal_ctx& c, const petal_matrix& x, const void* mu, const void*
     c.stats.pass_bytes = double(dtype_size(dt)) * (double(X.n) * x.cols + 2.0 * double(x.cols) * N);
     const void* mup = mu ? muT.p : nullptr;
     dev_set_tag(c.dev, TAG_POW);
-    const bool fused = op_power_pass(c.dev, dt, X.p, X.n, K, X.ld, mup, P.f64(), NP, NP, z_out ? Z.p : nullptr, NP, Y.f64(), NP);
+    // (test hook PETAL_OPT_STEERING_HOOK: without z the pass is asked for as a steering pass -- k_pow3f where that kernel exists)
+    const bool steer = !z_out && dev_option(c.dev, OPT_STEERING_HOOK) != 0;
+    const bool fused = op_power_pass(c.dev, dt, X.p, X.n, K, X.ld, mup, P.f64(), NP, NP, z_out ? Z.p : nullptr, NP, Y.f64(), NP, steer);
     dev_set_tag(c.dev, TAG_NONE);
     if (!fused) {
         dev_set_tag(c.dev, TAG_XP);
@@ -1749,7 +1755,8 @@ void gemm_atb(petal_ctx& c, const petal_matrix& a, const void* mu_a, const petal
     const bool gram_hook = !b && dt == F32 && ((mu_a == nullptr) == (mu_b == nullptr)) && dev_option(c.dev, OPT_GRAM_SPLIT_HOOK) != 0 &&
                            (!mu_a || std::memcmp(ha.data(), hb.data(), ha.size()) == 0);
     if (!(gram_hook && op_gram_split(c.dev, A.p, A.n, M, A.dp, A.ld, mu_a ? muA.p : nullptr, C.f64(), A.dp)))
-        op_gemm_atb(c.dev, dt, A.p, A.ld, A.dp, mu_a ? muA.p : nullptr, Bm.p, Bm.ld, Bm.dp, mu_b ? muB.p : nullptr, A.n, C.f64(), Bm.dp);
+        op_gemm_atb(c.dev, dt, A.p, A.ld, A.dp, mu_a ? muA.p : nullptr, Bm.p, Bm.ld, Bm.dp, mu_b ? muB.p : nullptr, A.n, C.f64(), Bm.dp,
+                    /*precise=*/false, /*steering=*/dev_option(c.dev, OPT_STEERING_HOOK) != 0);   // (test hook: the steering form)
     dev_set_tag(c.dev, TAG_NONE);
     std::vector<double> h(size_t(A.dp) * Bm.dp);
     dev_d2h(c.dev, h.data(), C.p, C.bytes);

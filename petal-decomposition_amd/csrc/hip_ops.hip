@@ -152,6 +152,7 @@ static void dev_defaults_from_env(Dev* d) {
     d->opt[OPT_ROW_PAD] = on("PETAL_NO_ROW_PAD") ? 0 : 1;
     d->opt[OPT_EIGH_JACOBI] = on("PETAL_EIGH_JACOBI") ? 1 : 0;
     d->opt[OPT_POISON] = on("PETAL_POISON") ? 1 : 0;
+    d->opt[OPT_STEERING_HOOK] = 0;   // (a test aid without an environment default)
     d->d2h_kernel = d->opt[OPT_D2H_KERNEL] != 0;
 }
 void dev_set_option(Dev* d, int opt, double value) {

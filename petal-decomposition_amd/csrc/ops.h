@@ -66,7 +66,9 @@ enum PetalOpt {
     OPT_ROW_PAD = 11,          // (1) copied inputs land with 128 B of row padding when the natural pitch is a multiple of 1 KiB  env PETAL_NO_ROW_PAD=1 -> 0
     OPT_EIGH_JACOBI = 12,      // (0) symmetric eigenproblems go straight to the Jacobi solvers                        env PETAL_EIGH_JACOBI=1
     OPT_POISON = 13,           // (0) every workspace block is filled with NaN patterns when handed out (tests)         env PETAL_POISON=1
-    OPT_COUNT = 14
+    // (14 is PETAL_OPT_FORCE_COLLECTIVE: it lives in the ctx, not in the device layer)
+    OPT_STEERING_HOOK = 15,    // (0) test hook: petal_gemm_xp / petal_gemm_atb / petal_power_pass (without z) ask for the steering forms   no env
+    OPT_COUNT = 16
 };
 void   dev_set_option(Dev*, int opt, double value);
 double dev_option(const Dev*, int opt);
