@@ -1,0 +1,52 @@
+/* petal_hip_probe.h -- TEST AIDS: the fp64 small-matrix operations every fit rests on (Cholesky / triangular solves, the fp64 GEMM
+ * forms, the symmetric eigen-solvers, the one-sided Jacobi SVD), each through an entry of its own, so that a test can hold one
+ * kernel to a long-double reference instead of a whole fit to 1e-5.  Declared beside petal_hip.h, whose set of entry points mirrors
+ * the crate's public interface one to one; nothing here is part of that interface, and there is no Rust binding.
+ *
+ * Every matrix argument is HOST memory, fp64, row-major, with an explicit leading dimension.  Each entry stages its inputs on the
+ * device, fills every output buffer with NaN (whatever PETAL_OPT_POISON says), calls the device operation the way the fit drivers do
+ * and copies the result back.  A shape the operation would refuse or that no kernel takes is PETAL_INVALID_INPUT and launches nothing.
+ */
+#ifndef PETAL_HIP_PROBE_H
+#define PETAL_HIP_PROBE_H
+
+#include "petal_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* G (L x L, ldg; upper triangle read) = R^T R with the dependence rule r_jj^2 <= rel_tol G_jj -> column j dropped.
+ * Lz (0 = L): the padded extent of the result.  ndead_cols: as op_chol_inv.  *ndead: in / out, the device word the operation takes
+ * the maximum into (pass 0 for the plain count).  *rt: 1 when the factor came back in RT form.
+ *   route 0  op_chol_inv:                         out (Lz x Lz, ldo) = T = R^-1
+ *   route 1  op_chol_rt, then op_trsm_right (RT form) or op_dgemm with the explicit inverse:
+ *                                                 out (b_rows x Lz, ldo) = B R^-1;  B (b_rows x Lz, ldb), NULL = the Lz x Lz identity
+ *   route 2  op_chol_rt, then the left solve inside op_gemm_xp_prod_absmax(a_rt) (RT form) or op_dgemm with the explicit inverse:
+ *                                                 out (Lz x b_cols, ldo) = R^-1 B;  B (Lz x b_cols, ldb), not NULL
+ * Where the RT form can come back (L <= 140, Lz a multiple of 16 <= 144) route 1 needs b_rows % 16 == 0 and route 2 b_cols % 16 == 0. */
+int petal_probe_chol(petal_ctx* ctx, const double* G, int64_t L, int64_t ldg, double rel_tol, int64_t Lz, int64_t ndead_cols, int route,
+                     const double* B, int64_t b_rows, int64_t b_cols, int64_t ldb, double* out, int64_t ldo, int* ndead, int* rt);
+
+/* op_eigh on a copy of A (L x L, lda): w (L, descending), V (Lm x Lm, ldv, Lm = max(L, Lz)): eigenvectors in the columns, rows /
+ * columns L .. Lz - 1 zero.  verdict_mode 0: no verdict word (*verdict_out = -1);  1: the word starts at verdict_in and is accumulated
+ * into;  2: the word starts at verdict_in and the operation is told to clear it first (verdict_fresh).  L <= 2048. */
+int petal_probe_eigh(petal_ctx* ctx, const double* A, int64_t L, int64_t lda, double tol_rel, int clustered, int64_t Lz, int64_t ncheck,
+                     int verdict_mode, int verdict_in, double gap_tol_override, double* w, double* V, int64_t ldv, int* verdict_out);
+
+/* op_jacobi_svd_rows on a copy of A (L x L, lda): U (L x L, ldu), s_inv (L), *nonconv (starts at 0).  L <= 1024. */
+int petal_probe_jacobi_svd_rows(petal_ctx* ctx, const double* A, int64_t L, int64_t lda, double* U, int64_t ldu, double* s_inv,
+                                int* nonconv);
+
+/* op_dgemm: C (M x N, ldc; in / out) = alpha op(A) op(B) [* colscale_j] + beta C.  op(A): M x K (A is K x M when ta), op(B): K x N.
+ * B == A with ldb == lda: the operation sees ONE device buffer (the symmetric rank-k form).  colscale (nullable, N values; beta
+ * must be 0).  With beta == 0 the device C is NaN when the operation starts; the words between the rows of C (ldc > N) come back
+ * as they went in. */
+int petal_probe_dgemm(petal_ctx* ctx, int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
+                      const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const double* colscale);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* PETAL_HIP_PROBE_H */

@@ -129,6 +129,20 @@ ABI_SCORE = [
     ("petal_score_rows", C.c_int, [_P, _M, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _M, _M]),
 ]
 
+# every symbol include/petal_hip_probe.h declares (TEST AIDS: the fp64 small-matrix operations through entries of their own; not part
+# of the mirrored interface, no Rust binding)
+_D = C.POINTER(C.c_double)
+_I = C.POINTER(C.c_int)
+ABI_PROBE = [
+    ("petal_probe_chol", C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_int64, C.c_int, _D, C.c_int64, C.c_int64,
+                                   C.c_int64, _D, C.c_int64, _I, _I]),
+    ("petal_probe_eigh", C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double,
+                                   _D, _D, C.c_int64, _I]),
+    ("petal_probe_jacobi_svd_rows", C.c_int, [_P, _D, C.c_int64, C.c_int64, _D, C.c_int64, _D, _I]),
+    ("petal_probe_dgemm", C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _D, C.c_int64, _D, C.c_int64,
+                                    C.c_double, _D, C.c_int64, _D]),
+]
+
 
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
@@ -146,7 +160,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h and include/petal_hip_score.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -155,7 +169,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE:
+    for name, res, args in ABI + ABI_SCORE + ABI_PROBE:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -1010,3 +1024,75 @@ def gemm_atb(a, b=None, mu_a=None, mu_b=None, ctx: Optional[Context] = None):
                                      mbh.ctypes.data if mbh is not None else None,
                                      out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
+
+
+# ---- include/petal_hip_probe.h: thin numpy wrappers (test aids) ---------------------------------------------------------------------
+def _f64_2d(a):
+    """a 2-D float64 array with unit column stride as it is (a row-sliced view keeps its leading dimension), else a contiguous copy"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2:
+        raise InvalidInput("expected a 2-D array")
+    if a.shape[1] > 1 and a.strides[1] != 8 or a.strides[0] % 8 or a.strides[0] < 8 * a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a, (a.strides[0] // 8 if a.shape[0] > 1 else max(a.shape[1], 1))
+
+
+def _dp(a):
+    return a.ctypes.data_as(_D)
+
+
+def probe_chol(g, rel_tol, Lz=0, ndead_cols=0, route=0, b=None, ndead_in=0, ctx: Optional[Context] = None):
+    """(out, ndead, rt) of petal_probe_chol: route 0 out = T (Lz x Lz); 1 out = b R^-1 (b: rows x Lz, None = identity); 2 out = R^-1 b"""
+    ctx = ctx or default_context()
+    g, ldg = _f64_2d(g)
+    L = g.shape[0]
+    lz = Lz or L
+    bb, ldb, br, bc = None, 0, 0, 0
+    if b is not None:
+        bb, ldb = _f64_2d(b)
+        br, bc = bb.shape
+    shape = (lz, lz) if route == 0 else ((br if bb is not None else lz, lz) if route == 1 else (lz, bc))
+    out = np.full(shape, np.nan)
+    nd, rt = C.c_int(int(ndead_in)), C.c_int(-1)
+    ctx.check(ctx.lib.petal_probe_chol(ctx._h, _dp(g), L, ldg, float(rel_tol), int(Lz), int(ndead_cols), int(route),
+                                       _dp(bb) if bb is not None else None, br, bc, ldb, _dp(out), shape[1], C.byref(nd), C.byref(rt)))
+    return out, nd.value, rt.value
+
+
+def probe_eigh(a, tol_rel=1e-15, clustered=False, Lz=0, ncheck=0, verdict_mode=0, verdict_in=0, gap_tol_override=0.0,
+               ctx: Optional[Context] = None):
+    """(w, V, verdict) of petal_probe_eigh; V is max(L, Lz) square"""
+    ctx = ctx or default_context()
+    a, lda = _f64_2d(a)
+    L = a.shape[0]
+    lm = max(L, int(Lz))
+    w, v = np.full(L, np.nan), np.full((lm, lm), np.nan)
+    vo = C.c_int(-2)
+    ctx.check(ctx.lib.petal_probe_eigh(ctx._h, _dp(a), L, lda, float(tol_rel), int(bool(clustered)), int(Lz), int(ncheck), int(verdict_mode),
+                                       int(verdict_in), float(gap_tol_override), _dp(w), _dp(v), lm, C.byref(vo)))
+    return w, v, vo.value
+
+
+def probe_jacobi_svd_rows(a, ctx: Optional[Context] = None):
+    """(U, s_inv, nonconv) of petal_probe_jacobi_svd_rows"""
+    ctx = ctx or default_context()
+    a, lda = _f64_2d(a)
+    L = a.shape[0]
+    u, s = np.full((L, L), np.nan), np.full(L, np.nan)
+    nc = C.c_int(-1)
+    ctx.check(ctx.lib.petal_probe_jacobi_svd_rows(ctx._h, _dp(a), L, lda, _dp(u), L, _dp(s), C.byref(nc)))
+    return u, s, nc.value
+
+
+def probe_dgemm(ta, tb, M, N, K, alpha, a, b, beta, c, colscale=None, ctx: Optional[Context] = None):
+    """petal_probe_dgemm in place on c (float64, unit column stride; a row-sliced view keeps its leading dimension); b is a: one buffer"""
+    ctx = ctx or default_context()
+    aa, lda = _f64_2d(a)
+    bb, ldb = (aa, lda) if b is a else _f64_2d(b)
+    if not (isinstance(c, np.ndarray) and c.dtype == np.float64 and c.ndim == 2 and c.shape == (M, N) and (N == 1 or c.strides[1] == 8)):
+        raise InvalidInput("c should be an M x N float64 array with unit column stride")
+    ldc = c.strides[0] // 8 if M > 1 else N
+    cs = np.ascontiguousarray(colscale, dtype=np.float64) if colscale is not None else None
+    ctx.check(ctx.lib.petal_probe_dgemm(ctx._h, int(bool(ta)), int(bool(tb)), M, N, K, float(alpha), _dp(aa), lda, _dp(bb), ldb, float(beta),
+                                        _dp(c), ldc, _dp(cs) if cs is not None else None))
+    return c

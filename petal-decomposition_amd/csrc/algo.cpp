@@ -1766,4 +1766,152 @@ void gemm_atb(petal_ctx& c, const petal_matrix& a, const void* mu_a, const petal
     finish_stats(c, timer);
 }
 
+
+// ---- probe entries (include/petal_hip_probe.h): TEST AIDS, one fp64 small-matrix operation per call, written against ops.h only ------
+namespace {
+
+constexpr int64_t PROBE_RT_MAXL = 140, PROBE_RT_MAXM = 144;   // where op_chol_rt may hand back the RT form (ops.h)
+
+// rows x cols of a host matrix (leading dimension ldh) on the device with leading dimension ldd, the words between the rows = fill
+DBuf probe_stage(petal_ctx& c, const double* h, int64_t rows, int64_t cols, int64_t ldh, int64_t ldd, double fill) {
+    std::vector<double> s(size_t(rows) * ldd, fill);
+    if (h)
+        for (int64_t i = 0; i < rows; ++i)
+            for (int64_t j = 0; j < cols; ++j) s[size_t(i) * ldd + j] = h[i * ldh + j];
+    DBuf d(c.dev, sizeof(double) * s.size());
+    dev_h2d(c.dev, d.p, s.data(), d.bytes);
+    return d;
+}
+DBuf probe_nan(petal_ctx& c, size_t count) { return probe_stage(c, nullptr, 1, 0, 0, int64_t(count), std::numeric_limits<double>::quiet_NaN()); }
+void probe_fetch(petal_ctx& c, const DBuf& d, int64_t rows, int64_t cols, int64_t ldd, double* h, int64_t ldh) {
+    std::vector<double> s(size_t(rows) * ldd);
+    dev_d2h(c.dev, s.data(), d.p, sizeof(double) * s.size());
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < rows; ++i)
+        for (int64_t j = 0; j < cols; ++j) h[i * ldh + j] = s[size_t(i) * ldd + j];
+}
+DBuf probe_int(petal_ctx& c, int v) {
+    DBuf d(c.dev, sizeof(int));
+    dev_h2d(c.dev, d.p, &v, sizeof(int));
+    return d;
+}
+int probe_int_back(petal_ctx& c, const DBuf& d) {
+    int v = 0;
+    dev_d2h(c.dev, &v, d.p, sizeof(int));
+    dev_sync(c.dev);
+    return v;
+}
+
+}  // namespace
+
+void probe_chol(petal_ctx& c, const double* G, int64_t L, int64_t ldg, double rel_tol, int64_t Lz, int64_t ndead_cols, int route,
+                const double* B, int64_t b_rows, int64_t b_cols, int64_t ldb, double* out, int64_t ldo, int* ndead, int* rt) {
+    if (Lz == 0) Lz = L;
+    if (L < 1 || L > 2048 || Lz < L || Lz > 2048 || ldg < L || route < 0 || route > 2 || ndead_cols < 0 || !(rel_tol >= 0))
+        invalid_input("probe_chol: bad order, padding, leading dimension, route or tolerance");
+    const bool may_rt = L <= PROBE_RT_MAXL && Lz % 16 == 0 && Lz <= PROBE_RT_MAXM;
+    if (route == 0) { b_rows = Lz; b_cols = Lz; }
+    if (route == 1) {
+        if (!B) { b_rows = Lz; ldb = Lz; }
+        b_cols = Lz;
+        if (b_rows < 1 || b_rows > 65536 || ldb < Lz || (may_rt && b_rows % 16 != 0)) invalid_input("probe_chol: B should be rows x Lz, rows a multiple of 16");
+    }
+    if (route == 2) {
+        if (!B || b_rows != Lz || b_cols < 1 || b_cols > 2048 || ldb < b_cols || (may_rt && b_cols % 16 != 0))
+            invalid_input("probe_chol: B should be Lz x cols, cols a multiple of 16");
+    }
+    const int64_t orow = route == 2 ? Lz : b_rows, ocol = route == 2 ? b_cols : Lz;
+    if (ldo < ocol) invalid_input("probe_chol: ldo too small");
+    DBuf Gd = probe_stage(c, G, L, L, ldg, ldg, std::numeric_limits<double>::quiet_NaN());   // (the words between the rows are not the operation's to read)
+    DBuf T = probe_nan(c, size_t(Lz) * Lz);
+    DBuf nd = probe_int(c, *ndead);
+    bool is_rt = false;
+    if (route == 0) {
+        op_chol_inv(c.dev, Gd.f64(), L, ldg, T.f64(), Lz, rel_tol, nd.as<int>(), Lz, ndead_cols);
+        probe_fetch(c, T, Lz, Lz, Lz, out, ldo);
+    } else {
+        is_rt = op_chol_rt(c.dev, F32, 64, Gd.f64(), L, ldg, T.f64(), Lz, rel_tol, nd.as<int>(), Lz, ndead_cols);
+        DBuf Bd;
+        if (B) Bd = probe_stage(c, B, b_rows, b_cols, ldb, b_cols, 0.0);
+        else {
+            std::vector<double> eye(size_t(Lz) * Lz, 0.0);
+            for (int64_t i = 0; i < Lz; ++i) eye[size_t(i) * Lz + i] = 1.0;
+            Bd = probe_stage(c, eye.data(), Lz, Lz, Lz, Lz, 0.0);
+        }
+        DBuf O = probe_nan(c, size_t(orow) * ocol);
+        if (route == 1) {
+            if (is_rt) op_trsm_right(c.dev, Bd.f64(), b_rows, Lz, T.f64(), Lz, Lz, O.f64(), Lz);
+            else op_dgemm(c.dev, false, false, b_rows, Lz, Lz, 1.0, Bd.f64(), Lz, T.f64(), Lz, 0.0, O.f64(), Lz);
+        } else if (is_rt) {
+            // the left solve lives in the product launcher: a 64-row fp32 X of small integers rides along, its product is not read
+            std::vector<float> xh(size_t(64) * Lz);
+            for (size_t i = 0; i < xh.size(); ++i) xh[i] = float(int(i % 7) - 3);
+            DBuf X(c.dev, sizeof(float) * xh.size()), Z(c.dev, sizeof(float) * 64 * size_t(b_cols));
+            dev_h2d(c.dev, X.p, xh.data(), X.bytes);
+            dev_memset(c.dev, Z.p, 0xFF, Z.bytes);
+            DBuf am = probe_nan(c, size_t(3) * b_cols);
+            op_gemm_xp_prod_absmax(c.dev, F32, X.p, 64, Lz, Lz, nullptr, T.f64(), Lz, Lz, Bd.f64(), b_cols, b_cols, O.f64(), b_cols, Z.p, b_cols,
+                                   0, am.f64(), am.f64() + b_cols, am.f64() + 2 * b_cols, true, /*a_rt=*/true);
+        } else {
+            op_dgemm(c.dev, false, false, Lz, b_cols, Lz, 1.0, T.f64(), Lz, Bd.f64(), b_cols, 0.0, O.f64(), b_cols);
+        }
+        probe_fetch(c, O, orow, ocol, ocol, out, ldo);
+    }
+    *ndead = probe_int_back(c, nd);
+    *rt = is_rt ? 1 : 0;
+}
+
+void probe_eigh(petal_ctx& c, const double* A, int64_t L, int64_t lda, double tol_rel, bool clustered, int64_t Lz, int64_t ncheck,
+                int verdict_mode, int verdict_in, double gap_tol_override, double* w, double* V, int64_t ldv, int* verdict_out) {
+    const int64_t Lm = std::max(L, Lz);
+    if (L < 1 || L > 2048 || Lz < 0 || Lz > 2048 || lda < L || ldv < Lm || ncheck < 0 || verdict_mode < 0 || verdict_mode > 2 ||
+        !(tol_rel > 0) || !(gap_tol_override >= 0))
+        invalid_input("probe_eigh: bad order, padding, leading dimension, verdict mode or tolerance");
+    DBuf Ad = probe_stage(c, A, L, L, lda, Lm, 0.0);
+    DBuf Vd = probe_nan(c, size_t(Lm) * Lm), wd = probe_nan(c, size_t(L));
+    DBuf vd = probe_int(c, verdict_in);
+    op_eigh(c.dev, Ad.f64(), L, Lm, Vd.f64(), Lm, wd.f64(), tol_rel, clustered, Lz, ncheck, verdict_mode ? vd.as<int>() : nullptr,
+            verdict_mode == 2, gap_tol_override);
+    probe_fetch(c, Vd, Lm, Lm, Lm, V, ldv);
+    probe_fetch(c, wd, 1, L, L, w, L);
+    *verdict_out = verdict_mode ? probe_int_back(c, vd) : -1;
+}
+
+void probe_jacobi_svd_rows(petal_ctx& c, const double* A, int64_t L, int64_t lda, double* U, int64_t ldu, double* s_inv, int* nonconv) {
+    if (L < 1 || L > 1024 || lda < L || ldu < L) invalid_input("probe_jacobi_svd_rows: bad order or leading dimension");
+    DBuf Ad = probe_stage(c, A, L, L, lda, lda, std::numeric_limits<double>::quiet_NaN());   // (the words between the rows are not the operation's to read)
+    DBuf Ud = probe_nan(c, size_t(L) * L), sd = probe_nan(c, size_t(L));
+    DBuf nc = probe_int(c, 0);
+    op_jacobi_svd_rows(c.dev, Ad.f64(), L, lda, Ud.f64(), L, sd.f64(), nc.as<int>());
+    probe_fetch(c, Ud, L, L, L, U, ldu);
+    probe_fetch(c, sd, 1, L, L, s_inv, L);
+    *nonconv = probe_int_back(c, nc);
+}
+
+void probe_dgemm(petal_ctx& c, bool ta, bool tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
+                 const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const double* colscale) {
+    const int64_t ar = ta ? K : M, ac = ta ? M : K, br = tb ? N : K, bc = tb ? K : N;
+    if (M < 1 || N < 1 || K < 1 || M > 65536 || N > 65536 || K > (int64_t(1) << 20) || lda < ac || ldb < bc || ldc < N ||
+        (colscale && beta != 0.0))
+        invalid_input("probe_dgemm: bad shape or leading dimension, or colscale with beta != 0");
+    const bool alias = A == B && lda == ldb && ar == br && ac == bc;
+    DBuf Ad = probe_stage(c, A, ar, ac, lda, lda, std::numeric_limits<double>::quiet_NaN());   // (the words between the rows are not the operation's to read)
+    DBuf Bd;
+    if (!alias) Bd = probe_stage(c, B, br, bc, ldb, ldb, std::numeric_limits<double>::quiet_NaN());   // (the words between the rows are not the operation's to read)
+    // C with its gaps as they came in; the M x N entries themselves are NaN when beta == 0 (nothing may read them)
+    std::vector<double> ch(size_t(M) * ldc);
+    for (int64_t i = 0; i < M; ++i)
+        for (int64_t j = 0; j < ldc; ++j)
+            ch[size_t(i) * ldc + j] = (j < N && beta == 0.0) ? std::numeric_limits<double>::quiet_NaN() : ((i < M - 1 || j < N) ? C[i * ldc + j] : 0.0);
+    DBuf Cd(c.dev, sizeof(double) * ch.size());
+    dev_h2d(c.dev, Cd.p, ch.data(), Cd.bytes);
+    DBuf sc;
+    if (colscale) sc = probe_stage(c, colscale, 1, N, N, N, 0.0);
+    op_dgemm(c.dev, ta, tb, M, N, K, alpha, Ad.f64(), lda, alias ? Ad.f64() : Bd.f64(), ldb, beta, Cd.f64(), ldc, colscale ? sc.f64() : nullptr);
+    dev_d2h(c.dev, ch.data(), Cd.p, Cd.bytes);
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < M; ++i)
+        for (int64_t j = 0; j < (i < M - 1 ? ldc : N); ++j) C[i * ldc + j] = ch[size_t(i) * ldc + j];
+}
+
 }  // namespace petal

@@ -6,6 +6,7 @@
 
 #include "ctx.h"
 #include "../../include/petal_hip_score.h"
+#include "../../include/petal_hip_probe.h"
 
 using namespace petal;
 
@@ -270,6 +271,50 @@ int petal_gemm_atb(petal_ctx* ctx, const petal_matrix* a, const void* mu_a, cons
         need(a, "a");
         need(c_out, "c_out");
         gemm_atb(*ctx, *a, mu_a, b, mu_b, c_out);
+    });
+}
+
+// ---- include/petal_hip_probe.h: test aids ---------------------------------------------------------------------------------------
+int petal_probe_chol(petal_ctx* ctx, const double* G, int64_t L, int64_t ldg, double rel_tol, int64_t Lz, int64_t ndead_cols, int route,
+                     const double* B, int64_t b_rows, int64_t b_cols, int64_t ldb, double* out, int64_t ldo, int* ndead, int* rt) {
+    return guarded(ctx, [&] {
+        need(G, "G");
+        need(out, "out");
+        need(ndead, "ndead");
+        need(rt, "rt");
+        probe_chol(*ctx, G, L, ldg, rel_tol, Lz, ndead_cols, route, B, b_rows, b_cols, ldb, out, ldo, ndead, rt);
+    });
+}
+
+int petal_probe_eigh(petal_ctx* ctx, const double* A, int64_t L, int64_t lda, double tol_rel, int clustered, int64_t Lz, int64_t ncheck,
+                     int verdict_mode, int verdict_in, double gap_tol_override, double* w, double* V, int64_t ldv, int* verdict_out) {
+    return guarded(ctx, [&] {
+        need(A, "A");
+        need(w, "w");
+        need(V, "V");
+        need(verdict_out, "verdict_out");
+        probe_eigh(*ctx, A, L, lda, tol_rel, clustered != 0, Lz, ncheck, verdict_mode, verdict_in, gap_tol_override, w, V, ldv, verdict_out);
+    });
+}
+
+int petal_probe_jacobi_svd_rows(petal_ctx* ctx, const double* A, int64_t L, int64_t lda, double* U, int64_t ldu, double* s_inv,
+                                int* nonconv) {
+    return guarded(ctx, [&] {
+        need(A, "A");
+        need(U, "U");
+        need(s_inv, "s_inv");
+        need(nonconv, "nonconv");
+        probe_jacobi_svd_rows(*ctx, A, L, lda, U, ldu, s_inv, nonconv);
+    });
+}
+
+int petal_probe_dgemm(petal_ctx* ctx, int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
+                      const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const double* colscale) {
+    return guarded(ctx, [&] {
+        need(A, "A");
+        need(B, "B");
+        need(C, "C");
+        probe_dgemm(*ctx, ta != 0, tb != 0, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, colscale);
     });
 }
 

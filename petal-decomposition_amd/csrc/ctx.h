@@ -108,5 +108,13 @@ void gemm_xp(petal_ctx& c, const petal_matrix& x, const void* mu, const void* p,
 void gemm_atb(petal_ctx& c, const petal_matrix& a, const void* mu_a, const petal_matrix* b, const void* mu_b, double* c_out);
 void power_pass(petal_ctx& c, const petal_matrix& x, const void* mu, const void* p, int64_t N, double* y_out, const petal_matrix* z_out,
                 int* fused_out);
+// the probe entries of include/petal_hip_probe.h (test aids: one fp64 small-matrix operation per call)
+void probe_chol(petal_ctx& c, const double* G, int64_t L, int64_t ldg, double rel_tol, int64_t Lz, int64_t ndead_cols, int route,
+                const double* B, int64_t b_rows, int64_t b_cols, int64_t ldb, double* out, int64_t ldo, int* ndead, int* rt);
+void probe_eigh(petal_ctx& c, const double* A, int64_t L, int64_t lda, double tol_rel, bool clustered, int64_t Lz, int64_t ncheck,
+                int verdict_mode, int verdict_in, double gap_tol_override, double* w, double* V, int64_t ldv, int* verdict_out);
+void probe_jacobi_svd_rows(petal_ctx& c, const double* A, int64_t L, int64_t lda, double* U, int64_t ldu, double* s_inv, int* nonconv);
+void probe_dgemm(petal_ctx& c, bool ta, bool tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
+                 const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const double* colscale);
 
 }  // namespace petal

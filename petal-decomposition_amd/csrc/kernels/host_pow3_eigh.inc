@@ -384,6 +384,8 @@ void op_eigh(Dev* d, double* A, int64_t L, int64_t lda, double* V, int64_t ldv, 
         set_max_lds(d, reinterpret_cast<const void*>(k_jacobi_a<M, G>));                        \
         hipLaunchKernelGGL((k_jacobi_a<M, G>), dim3(1), dim3(threads), lds, d->stream, A, (int)L, lda, log_cs, nrounds, w, rank, pw, tol_rel, (const int*)flag); \
     } break;
+        // (of the eight instantiations only (1, 32), (2, 32), (4, 16) and (5, 16) are ever taken: 16-lane groups need more than 60
+        // row pairs, which is mb2 >= 4, and 32-lane groups at most 60, which is mb2 <= 2 -- tests/smallmat_cases.py::jacobi_form)
         switch (10 * std::min(mb2, 5) + (gw == 32 ? 1 : 0)) {
             JACA_CASE(1, 16) JACA_CASE(2, 16) JACA_CASE(3, 16) JACA_CASE(4, 16) JACA_CASE(5, 16)
             JACA_CASE(1, 32) JACA_CASE(2, 32) JACA_CASE(3, 32)
@@ -411,7 +413,7 @@ void op_eigh(Dev* d, double* A, int64_t L, int64_t lda, double* V, int64_t ldv, 
 }
 // One-sided (Hestenes) Jacobi on the ROWS of M (L x L), G accumulates the rotations from the identity: one workgroup, 32 lanes
 // per row pair, the L / 2 disjoint pairs of a round-robin round in flight together; a round ends with one barrier.  M and G live in
-// LDS when both fit (L <= 96), else in global memory (L2-resident).  Built for accuracy, not speed: it only runs for fp64
+// LDS when both fit (L <= 97: the launcher's 150 KiB test), else in global memory (L2-resident).  Built for accuracy, not speed: it only runs for fp64
 // data whose wanted singular values fall below the Gram route's 10^-3.5 sigma_1 accuracy floor.
 constexpr int HJ_THREADS = 1024, HJ_GROUP = 32;
 template <bool INLDS>

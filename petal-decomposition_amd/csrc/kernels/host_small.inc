@@ -365,6 +365,13 @@ __global__ void k_copy_diag(const double* __restrict__ G, int64_t ldg, int64_t L
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < L) out[j] = G[j * ldg + j];
 }
+// *ndead = max(*ndead, sum of the per-block counts): the dependent columns of the WHOLE matrix, as ops.h promises
+__global__ void k_ndead_total(const int* __restrict__ cnt, int nb, int* __restrict__ ndead) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int tot = 0;
+    for (int b = 0; b < nb; ++b) tot += cnt[b];
+    if (tot > *ndead) *ndead = tot;
+}
 // L beyond the one-workgroup kernels (k + n_oversample > 200): blocked right-looking factorisation on the chip-wide fp64
 // GEMM kernel, 128-wide diagonal blocks by k_chol_inv2 (which hands back T_JJ = R_JJ^-1 directly):
 //   G_J,J.. -= sum_{K<J} R_KJ^T R_K,J..;  T_JJ = chol_inv(G_JJ);  R_J,rest = T_JJ^T G_J,rest;
@@ -381,13 +388,17 @@ static void chol_inv_blocked(Dev* d, const double* G, int64_t L, int64_t ldg, do
     hipLaunchKernelGGL(k_copy_diag, dim3(cdiv(L, 256)), dim3(256), 0, d->stream, G, ldg, L, gd);
     launch_check();
     HIP_CHECK(hipMemset2DAsync(T, ldt * sizeof(double), 0, Lz * sizeof(double), Lz, d->stream));
+    // every diagonal block counts its own dependent columns; their SUM goes to the caller's word (each block once took the maximum
+    // into it directly: dead columns in two blocks were reported as the larger of the two counts)
+    int* cnt = ndead ? (int*)dev_alloc(d, sizeof(int) * nb) : nullptr;
+    if (cnt) HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * nb, d->stream));
     set_max_lds(d, reinterpret_cast<const void*>(k_chol_inv2));
     for (int64_t J = 0; J < nb; ++J) {
         const int64_t j0 = J * B, bj = std::min(B, L - j0), rest = L - j0 - bj;
         if (j0 > 0)  // block row J of the Schur complement (its diagonal block and everything right of it)
             op_dgemm(d, true, false, bj, L - j0, j0, -1.0, R + j0, L, R + j0, L, 1.0, W + j0 * L + j0, L);
         hipLaunchKernelGGL(k_chol_inv2, dim3(1), dim3(CHOL_THREADS), chol2_lds_bytes((int)bj), d->stream, W + j0 * L + j0, (int)bj, L,
-                           T + j0 * ldt + j0, ldt, rel_tol, ndead, (int)bj, (const double*)(gd + j0), 0, (int)bj);
+                           T + j0 * ldt + j0, ldt, rel_tol, cnt ? cnt + J : nullptr, (int)bj, (const double*)(gd + j0), 0, (int)bj);
         launch_check();
         if (rest > 0)
             op_dgemm(d, true, false, bj, rest, bj, 1.0, T + j0 * ldt + j0, ldt, W + j0 * L + j0 + bj, L, 0.0, R + j0 * L + j0 + bj, L);
@@ -399,6 +410,11 @@ static void chol_inv_blocked(Dev* d, const double* G, int64_t L, int64_t ldg, do
             op_dgemm(d, false, false, bi, bj, kk, 1.0, R + i0 * L + k0, L, T + k0 * ldt + j0, ldt, 0.0, tmp, bj);
             op_dgemm(d, false, false, bi, bj, bi, -1.0, T + i0 * ldt + i0, ldt, tmp, bj, 0.0, T + i0 * ldt + j0, ldt);
         }
+    if (cnt) {
+        hipLaunchKernelGGL(k_ndead_total, dim3(1), dim3(1), 0, d->stream, (const int*)cnt, (int)nb, ndead);
+        launch_check();
+        dev_free(d, cnt);
+    }
     dev_free(d, tmp); dev_free(d, gd); dev_free(d, R); dev_free(d, W);
 }
 

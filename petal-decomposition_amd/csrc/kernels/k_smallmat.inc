@@ -786,6 +786,17 @@ __global__ __launch_bounds__(256) void k_chol_rt4(const double* __restrict__ G, 
 //                                          Jacobi its high relative accuracy on positive definite matrices), or
 //     a_pq^2 <= (1e-16 ||diag||_F)^2      (below the rounding noise of the matrix itself: exact zeros / rank deficiency).
 // Returns the largest a_pq^2 / limit over the upper triangle: <= 1 means converged.  Reads r <= c only (the split solver keeps the upper triangle).
+// The second limit alone would end the iteration on a GRADED positive definite matrix (A = D H D, entries accurate to their own
+// size) while the rows of its eigenvalues below 1e-16 ||A|| are still coupled: cyclic sweeps rotate those rows along with the rest,
+// so they are nearly done when the large ones finish, but the last quadratic step is missing -- measured 2.6e-12 relative
+// error in the small eigenvalues of a 48 x 48 matrix graded over 24 decades, where a float64 Hestenes iteration has 1.2e-14; with the
+// rule below 2.8e-15 (eig-graded-L48-jacobi in profiles/smallmat_errors.txt; tests/smallmat_cases.py, EXPERIMENTS.md).
+// s_red[63] (set by the caller before the first sweep: +inf, or 0 to switch this off; in LDS because the value is uniform and the split
+// solver has no register to spare) holds the first criterion's violation of the previous call: once the limits above are met, the sweeps go on while the FIRST
+// criterion alone is still violated AND the last sweep reduced that violation at least fourfold -- quadratic convergence on a
+// graded matrix; on rounding noise (exact zeros, rank deficiency: no progress, or a zero diagonal product) the iteration ends as before.
+// Only for tol_rel <= 1e-15 (fp64 callers).  The cost: a solve whose matrix has eigenvalues at its noise level runs one more sweep
+// before the no-progress exit (EXPERIMENTS.md).
 // Collective over the workgroup; s_red needs 64 doubles.
 __device__ double wg_jacobi_violation(const double* A, int64_t ld, int L, double tol_rel, double* s_red) {
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = (nt + 63) >> 6;
@@ -799,7 +810,7 @@ __device__ double wg_jacobi_violation(const double* A, int64_t ld, int L, double
     __syncthreads();
     if (!(tdg > 0.0) || !(tdg < 1e300)) return 0.0;  // zero or non-finite matrix: nothing a rotation could improve
     const double floor2 = 1e-32 * tdg, tol2 = tol_rel * tol_rel;
-    double viol = 0;
+    double viol = 0, vrel = 0;
     {
         int r = tid / L, c = tid - r * L;
         const int dr = nt / L, dc = nt - dr * L;
@@ -807,20 +818,25 @@ __device__ double wg_jacobi_violation(const double* A, int64_t ld, int L, double
             if (c > r) {
                 const double v = A[r * ld + c];
                 if (v != 0.0) {
-                    const double lim = fmax(tol2 * fabs(A[r * ld + r] * A[c * ld + c]), floor2);
-                    viol = fmax(viol, v * v / lim);
+                    const double rel = tol2 * fabs(A[r * ld + r] * A[c * ld + c]);
+                    viol = fmax(viol, v * v / fmax(rel, floor2));
+                    vrel = fmax(vrel, v * v / rel);   // (+inf on a zero diagonal product)
                 }
             }
             r += dr; c += dc;
             if (c >= L) { c -= L; ++r; }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) viol = fmax(viol, __shfl_down(viol, off, 64));
-    if (lane == 0) s_red[wv] = viol;
+    for (int off = 32; off > 0; off >>= 1) { viol = fmax(viol, __shfl_down(viol, off, 64)); vrel = fmax(vrel, __shfl_down(vrel, off, 64)); }
+    if (lane == 0) { s_red[wv] = viol; s_red[32 + wv] = vrel; }
     __syncthreads();
-    double tv = 0;
-    for (int x = 0; x < nw; ++x) tv = fmax(tv, s_red[x]);
+    double tv = 0, tr = 0;
+    for (int x = 0; x < nw; ++x) { tv = fmax(tv, s_red[x]); tr = fmax(tr, s_red[32 + x]); }
+    const double prev = s_red[63];
+    const bool progress = prev != 0.0 && tr < 0.25 * prev;
     __syncthreads();
+    if (tid == 0 && prev != 0.0) s_red[63] = tr;   // (read again behind the barriers of the next call; a 0 stays: switched off for good)
+    if (!(tv > 1.0) && tr > 1.0 && progress) return tr;
     return tv;
 }
 
@@ -828,12 +844,14 @@ __device__ double wg_jacobi_violation(const double* A, int64_t ld, int L, double
 // A (L x L, lda) symmetric, destroyed; V (L x L, ldv) <- eigenvectors in columns.  Parallel ordering:
 // round-robin tournament, L/2 disjoint rotations per round, three barriers per round.
 __device__ void wg_jacobi(double* A, int64_t lda, double* V, int64_t ldv, int L, double* s_c, double* s_s, int* s_p, int* s_q,
-                          double* s_red, double tol_rel) {
+                          double* s_red, double tol_rel, bool graded = false) {
     const int tid = threadIdx.x, nt = blockDim.x;
     for (int e = tid; e < L * L; e += nt) V[(int64_t)(e / L) * ldv + (e % L)] = (e / L == e % L) ? 1.0 : 0.0;
     __syncthreads();
     if (L < 2) return;
     const int Le = (L + 1) & ~1, half = Le / 2, rounds = Le - 1;
+    if (tid == 0) s_red[63] = (graded && tol_rel <= 1e-15) ? INFINITY : 0.0;   // (0: the continuation of wg_jacobi_violation never starts)
+    __syncthreads();
     for (int sweep = 0; sweep < 40; ++sweep) {
         const double viol = wg_jacobi_violation(A, lda, L, tol_rel, s_red);
         // (no "nearly there: one more sweep" shortcut: with clustered or tiny eigenvalues the step after |a_pq| ~ sqrt(tol) is
@@ -893,7 +911,7 @@ __device__ void wg_jacobi(double* A, int64_t lda, double* V, int64_t ldv, int L,
 // instead of serialising behind possibly-aliasing stores; (c, s) and (p, q) are packed for 16-B / 8-B loads.
 template <int MB>
 __device__ void wg_jacobi_fast(double* A, double* V, int L, double* s_c, double* s_s, int* s_p, int* s_q, double* s_red,
-                               double tol_rel) {
+                               double tol_rel, bool graded = false) {
     constexpr int MB2 = (MB + 1) / 2;  // 16-wide groups of pairs: half <= 8 MB
     const int LD = L | 1;  // odd leading dimension: column accesses (stride LD doubles) spread over all LDS banks
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = nt >> 6;
@@ -908,6 +926,8 @@ __device__ void wg_jacobi_fast(double* A, double* V, int L, double* s_c, double*
     __syncthreads();
     if (L < 2) return;
     const int Le = (L + 1) & ~1, half = Le / 2, rounds = Le - 1;
+    if (tid == 0) s_red[63] = (graded && tol_rel <= 1e-15) ? INFINITY : 0.0;   // (0: the continuation of wg_jacobi_violation never starts)
+    __syncthreads();
     for (int sweep = 0; sweep < 40; ++sweep) {
         const double viol = wg_jacobi_violation(A, LD, L, tol_rel, s_red);
 #ifdef PETAL_DEBUG_COUNTERS
@@ -1007,9 +1027,9 @@ __device__ void wg_jacobi_fast(double* A, double* V, int L, double* s_c, double*
 // MB == 0: matrices in global memory (any L), generic loops; MB > 0: LDS-resident fast path for L <= 16 MB
 template <int MB>
 __device__ __forceinline__ void wg_jacobi_any(double* A, int64_t lda, double* V, int64_t ldv, int L, double* s_c, double* s_s,
-                                              int* s_p, int* s_q, double* s_red, double tol_rel = 1e-15) {
-    if constexpr (MB == 0) wg_jacobi(A, lda, V, ldv, L, s_c, s_s, s_p, s_q, s_red, tol_rel);
-    else wg_jacobi_fast<MB>(A, V, L, s_c, s_s, s_p, s_q, s_red, tol_rel);
+                                              int* s_p, int* s_q, double* s_red, double tol_rel = 1e-15, bool graded = false) {
+    if constexpr (MB == 0) wg_jacobi(A, lda, V, ldv, L, s_c, s_s, s_p, s_q, s_red, tol_rel, graded);
+    else wg_jacobi_fast<MB>(A, V, L, s_c, s_s, s_p, s_q, s_red, tol_rel, graded);
 }
 // sort eigenpairs descending: Vout[:, rank] = V[:, j], w[rank] = A[j][j]
 __device__ void wg_sort_eig(const double* A, int64_t lda, const double* V, int64_t ldv, int L, double* Vout, int64_t ldo,
@@ -1061,7 +1081,7 @@ __global__ __launch_bounds__(MB > 0 ? 768 : 1024) void k_eigh(double* A, int L, 
         for (int e = tid; e < L * L; e += nt) Aw[(e / L) * la + (e % L)] = A[(int64_t)(e / L) * lda + (e % L)];
         __syncthreads();
     }
-    wg_jacobi_any<MB>(Aw, la, Vw, la, L, ws.c, ws.s, ws.p, ws.q, ws.red, tol_rel);
+    wg_jacobi_any<MB>(Aw, la, Vw, la, L, ws.c, ws.s, ws.p, ws.q, ws.red, tol_rel, /*graded=*/true);   // (op_eigh: small eigenvalues to their own size)
     wg_sort_eig(Aw, la, Vw, la, L, V, ldv, w, ws.rank);
 }
 
@@ -1169,6 +1189,8 @@ __global__ __launch_bounds__(1024) void k_jacobi_a(const double* __restrict__ Ai
     const int gb = half - 1 - g, n1 = half - 1 - g;
     const int nslots = (bt < 0) ? 0 : ((g < gb) ? half - 1 : (g == gb ? n1 : 0));
     int R = 0;  // rounds logged so far
+    if (tid == 0) s_red[63] = tol_rel <= 1e-15 ? INFINITY : 0.0;   // (fp64 callers only: a matrix formed from fp32 data has no digits down there)
+    __syncthreads();
     for (int sweep = 0; sweep < JACA_MAX_SWEEPS && L >= 2; ++sweep) {
         const double viol = wg_jacobi_violation(A, LD, L, tol_rel, s_red);
         // (no "nearly there: one more sweep" shortcut: with clustered or tiny eigenvalues the step after |a_pq| ~ sqrt(tol) is

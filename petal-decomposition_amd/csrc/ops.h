@@ -279,7 +279,9 @@ void op_chol_inv(Dev*, const double* G, int64_t L, int64_t ldg, double* T, int64
 // symmetric PSD A (L x L) -> eigenvalues w (descending) and eigenvectors in the COLUMNS of V.  A may be destroyed.
 // tol_rel: off-diagonal elements are annihilated down to |a_pq| <= tol_rel sqrt(a_pp a_qq) (graded matrices keep the
 // relative accuracy of their small eigenvalues) or to the 1e-16 ||diag|| rounding floor; 1e-15 for fp64 data, 1e-8 is
-// ample when the matrix was formed from fp32 data.
+// ample when the matrix was formed from fp32 data.  (Behind the floor the Jacobi solvers go on while the first criterion
+// still makes quadratic progress: a graded matrix keeps its eigenvalues BELOW 1e-16 ||A|| too, rounding noise ends as before.)
+// The two-stage solver computes each eigenvector on its own: v_i . v_j carries up to 2 eps ||A|| / |lam_i - lam_j|.
 // clustered = true: the caller expects eigenvalues closer than the two-stage solver's gap tolerance (the Ritz values of a
 // subspace iteration: a block of noise-level eigenvalues) -- go to the Jacobi solver directly instead of paying for both
 // Lz > L: V is an Lz x Lz matrix (leading dimension ldv) whose rows / columns L .. Lz - 1 must come out zero (padding for the
