@@ -22,6 +22,7 @@
 
 #include "petal_hip.h"
 #include "petal_hip_score.h"
+#include "petal_hip_segments.h"
 
 namespace petal_decomposition {
 
@@ -278,6 +279,83 @@ class Pca {  // src/pca.rs:41-232
         st_.total_variance = tv; st_.n_samples = input.nrows();
     }
     detail::PcaState<A> st_;
+};
+
+// One exact Pca per row segment of a row-sorted matrix, in one call (petal_hip_segments.h: an extension beyond the crate).  Segment b is
+// rows offsets[b] .. offsets[b + 1] - 1 and gets what Pca::fit gives on those rows alone; for d <= 64 the batch is one launch, a
+// workgroup per segment (a very long segment is correct and not fast: fit it with Pca).
+template <class A>
+class SegmentedPca {
+  public:
+    explicit SegmentedPca(int64_t n_components, bool centering = true, Context* ctx = nullptr)
+        : k_(n_components), centering_(centering), ctx_(ctx) {}
+    int64_t n_components() const { return k_; }
+    int64_t n_segments() const { return nseg_; }
+    const std::vector<A>& components() const { return comp_; }           // n_segments x k x d, row-major, svd_flip's sign applied
+    const std::vector<A>& mean() const { return means_; }                // n_segments x d
+    const std::vector<A>& singular_values() const { return sing_; }      // n_segments x k
+    const std::vector<A>& total_variance() const { return tv_; }         // n_segments
+    const std::vector<int32_t>& status() const { return status_; }       // 0: fitted; 1: the segment held a NaN or an infinity (results NaN)
+    int64_t kernel_segments() const { return kernel_segments_; }         // how many segments of the last fit the segment kernel fitted
+    std::vector<A> explained_variance_ratio() const {
+        std::vector<A> r(sing_.size());
+        for (int64_t b = 0; b < nseg_; ++b)
+            for (int64_t j = 0; j < k_; ++j) r[b * k_ + j] = sing_[b * k_ + j] * sing_[b * k_ + j] / tv_[b];
+        return r;
+    }
+    void fit(const Array2<A>& input, const std::vector<int64_t>& offsets) { inner_fit(input, offsets, nullptr); }
+    Array2<A> fit_transform(const Array2<A>& input, const std::vector<int64_t>& offsets) {
+        Array2<A> y(input.nrows(), k_);
+        inner_fit(input, offsets, &y);
+        return y;
+    }
+    Array2<A> transform(const Array2<A>& input, const std::vector<int64_t>& offsets) const {
+        if (input.ncols() != d_) throw DecompositionError(DecompositionError::InvalidInput, "# of columns should be " + std::to_string(d_));
+        Array2<A> y(input.nrows(), k_);
+        petal_matrix mx = input.view(), my = y.view();
+        context().check(petal_transform_segments(context().get(), &mx, offsets_of(offsets), n_of(offsets), comp_.data(), means_.data(), k_, d_,
+                                                 centering_, &my));
+        return y;
+    }
+    Array2<A> inverse_transform(const Array2<A>& input, const std::vector<int64_t>& offsets) const {
+        if (input.ncols() != k_) throw DecompositionError(DecompositionError::InvalidInput, "# of columns should be " + std::to_string(k_));
+        Array2<A> x(input.nrows(), d_);
+        petal_matrix my = input.view(), mx = x.view();
+        context().check(petal_inverse_transform_segments(context().get(), &my, offsets_of(offsets), n_of(offsets), comp_.data(), means_.data(),
+                                                         k_, d_, centering_, &mx));
+        return x;
+    }
+    static std::vector<int64_t> offsets_from_lengths(const std::vector<int64_t>& lengths) {
+        std::vector<int64_t> off(lengths.size() + 1, 0);
+        for (size_t b = 0; b < lengths.size(); ++b) off[b + 1] = off[b] + lengths[b];
+        return off;
+    }
+
+  private:
+    Context& context() const { return ctx_ ? *ctx_ : Context::global(); }
+    static const int64_t* offsets_of(const std::vector<int64_t>& offsets) {
+        if (offsets.empty()) throw DecompositionError(DecompositionError::InvalidInput, "offsets needs n_segments + 1 values");
+        return offsets.data();
+    }
+    static int64_t n_of(const std::vector<int64_t>& offsets) { return int64_t(offsets.size()) - 1; }
+    void inner_fit(const Array2<A>& input, const std::vector<int64_t>& offsets, Array2<A>* y) {
+        const int64_t* off = offsets_of(offsets);
+        const int64_t nseg = n_of(offsets), d = input.ncols();
+        std::vector<A> comp(size_t(nseg * k_ * d)), means(size_t(nseg * d)), sing(size_t(nseg * k_)), tv(size_t(nseg), A(0));
+        std::vector<int32_t> status(size_t(nseg), 0);
+        int64_t ks = 0;
+        petal_matrix mx = input.view(), my{};
+        if (y) my = y->view();
+        context().check(petal_pca_fit_segments(context().get(), &mx, off, nseg, k_, centering_, comp.data(), means.data(), sing.data(), tv.data(),
+                                               status.data(), y ? &my : nullptr, &ks));
+        comp_ = std::move(comp); means_ = std::move(means); sing_ = std::move(sing); tv_ = std::move(tv); status_ = std::move(status);
+        nseg_ = nseg; d_ = d; kernel_segments_ = ks;
+    }
+    int64_t k_, nseg_ = 0, d_ = 0, kernel_segments_ = 0;
+    bool centering_;
+    Context* ctx_;
+    std::vector<A> comp_, means_, sing_, tv_;
+    std::vector<int32_t> status_;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

@@ -129,6 +129,14 @@ ABI_SCORE = [
     ("petal_score_rows", C.c_int, [_P, _M, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _M, _M]),
 ]
 
+# every symbol include/petal_hip_segments.h declares (segmented Pca: an extension beyond the crate, kept apart from the mirrored set above)
+_L = C.POINTER(C.c_int64)
+ABI_SEGMENTS = [
+    ("petal_pca_fit_segments", C.c_int, [_P, _M, _L, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int32), _M, _L]),
+    ("petal_transform_segments", C.c_int, [_P, _M, _L, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int, _M]),
+    ("petal_inverse_transform_segments", C.c_int, [_P, _M, _L, C.c_int64, _P, _P, C.c_int64, C.c_int64, C.c_int, _M]),
+]
+
 # every symbol include/petal_hip_probe.h declares (TEST AIDS: the fp64 small-matrix operations through entries of their own; not part
 # of the mirrored interface, no Rust binding)
 _D = C.POINTER(C.c_double)
@@ -160,7 +168,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -169,7 +177,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_PROBE:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -608,6 +616,122 @@ class Pca(_PcaModel):
 
     def fit_transform(self, x):
         return self._inner_fit(x, True)
+
+
+class SegmentedPca:
+    """One exact Pca per row segment of a row-sorted matrix, in one call (include/petal_hip_segments.h; an extension beyond the crate,
+    DESIGN.md section 7).  Segment b is rows offsets[b] .. offsets[b + 1] - 1; it gets what ``Pca.fit`` gives on those rows alone.  For
+    d <= 64 the batch is one launch, a workgroup per segment; a very long segment is correct and not fast (fit it with ``Pca``)."""
+
+    def __init__(self, n_components: int, centering: bool = True, ctx: Optional[Context] = None):
+        self._k = int(n_components)
+        self.centering = bool(centering)
+        self.ctx = ctx
+        self._dt = PETAL_F64
+        self._components = np.zeros((0, self._k, 0))
+        self._means = np.zeros((0, 0))
+        self._singular = np.zeros((0, self._k))
+        self._total_variance = np.zeros(0)
+        self._status = np.zeros(0, dtype=np.int32)
+        self._kernel_segments = 0
+
+    def _ctx(self) -> Context:
+        if self.ctx is None:
+            self.ctx = default_context()
+        return self.ctx
+
+    components = property(lambda self: self._components, doc="(B, k, d), svd_flip's sign applied")
+    mean = property(lambda self: self._means, doc="(B, d)")
+    singular_values = property(lambda self: self._singular, doc="(B, k)")
+    status = property(lambda self: self._status, doc="(B) 0: fitted; 1: the segment held a NaN or an infinity, its results are NaN")
+    kernel_segments = property(lambda self: self._kernel_segments, doc="how many segments of the last fit the segment kernel fitted")
+    total_variance = property(lambda self: self._total_variance, doc="(B)")
+
+    @property
+    def explained_variance_ratio(self):
+        return self._singular * self._singular / self._total_variance[:, None]
+
+    @staticmethod
+    def _rows(x, offsets, lengths):
+        """(the 2-D matrix of all rows, offsets as int64[B + 1], the leading (B, n) of a 3-D input or None)"""
+        shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+        lead = None
+        if len(shape) == 3:
+            if offsets is not None or lengths is not None:
+                raise InvalidInput("a 3-D input has equal segments: no offsets / lengths")
+            lead = (int(shape[0]), int(shape[1]))
+            x = x.reshape(lead[0] * lead[1], shape[2]) if (_is_torch(x) or isinstance(x, np.ndarray)) else np.asarray(x).reshape(-1, shape[2])
+            offsets = np.arange(lead[0] + 1, dtype=np.int64) * lead[1]
+        elif lengths is not None:
+            if offsets is not None:
+                raise InvalidInput("give offsets or lengths, not both")
+            offsets = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
+        elif offsets is None:
+            raise InvalidInput("a 2-D input needs offsets or lengths")
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        if off.size < 1:
+            raise InvalidInput("offsets needs n_segments + 1 values")
+        return x, off, lead
+
+    @staticmethod
+    def _shaped(y, lead):
+        return y if lead is None else y.reshape(lead[0], lead[1], y.shape[1])
+
+    def _inner_fit(self, x, offsets, lengths, want_y: bool):
+        x, off, lead = self._rows(x, offsets, lengths)
+        keep = []
+        mx = describe(x, keep)
+        ctx = self._ctx()
+        npdt = _np_dtype(mx.dtype)
+        nseg, k, d = off.size - 1, self._k, mx.cols
+        comp = np.zeros((nseg, k, d), dtype=npdt)
+        means = np.zeros((nseg, d), dtype=npdt)
+        sing = np.zeros((nseg, k), dtype=npdt)
+        tv = np.zeros(nseg, dtype=npdt)
+        status = np.zeros(nseg, dtype=np.int32)
+        ks = C.c_int64(0)
+        y, my = None, None
+        if want_y:
+            y = _alloc_like(x, mx.rows, k, mx.dtype)
+            my = describe(y, keep)
+        ctx.check(ctx.lib.petal_pca_fit_segments(
+            ctx._h, C.byref(mx), off.ctypes.data_as(_L), nseg, k, int(self.centering), comp.ctypes.data, means.ctypes.data,
+            sing.ctypes.data, tv.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(my) if my is not None else None,
+            C.byref(ks)))
+        self._components, self._means, self._singular, self._total_variance = comp, means, sing, tv
+        self._status, self._kernel_segments, self._dt = status, int(ks.value), mx.dtype
+        return None if y is None else self._shaped(y, lead)
+
+    def fit(self, x, offsets=None, lengths=None):
+        self._inner_fit(x, offsets, lengths, False)
+        return self
+
+    def fit_transform(self, x, offsets=None, lengths=None):
+        return self._inner_fit(x, offsets, lengths, True)
+
+    def _apply(self, entry, a, offsets, lengths, cols_in, cols_out):
+        a, off, lead = self._rows(a, offsets, lengths)
+        keep = []
+        ma = describe(a, keep)
+        ctx = self._ctx()
+        nseg, d = self._means.shape
+        if ma.cols != cols_in:
+            raise InvalidInput(f"# of columns should be {cols_in}")
+        if off.size - 1 != nseg:
+            raise InvalidInput(f"the model holds {nseg} segments, offsets describe {off.size - 1}")
+        out = _alloc_like(a, ma.rows, cols_out, ma.dtype)
+        mo = describe(out, keep)
+        comp = _host(self._components, ma.dtype)
+        mu = _host(self._means, ma.dtype)
+        ctx.check(entry(ctx._h, C.byref(ma), off.ctypes.data_as(_L), nseg, comp.ctypes.data, mu.ctypes.data, self._k, d,
+                        int(self.centering), C.byref(mo)))
+        return self._shaped(out, lead)
+
+    def transform(self, x, offsets=None, lengths=None):
+        return self._apply(self._ctx().lib.petal_transform_segments, x, offsets, lengths, self._means.shape[1], self._k)
+
+    def inverse_transform(self, y, offsets=None, lengths=None):
+        return self._apply(self._ctx().lib.petal_inverse_transform_segments, y, offsets, lengths, self._k, self._means.shape[1])
 
 
 class PcaBuilder:

@@ -1234,6 +1234,224 @@ void inverse_transform(petal_ctx& c, const petal_matrix& y, const void* componen
 }
 
 // ---------------------------------------------------------------------------------------------
+// Segmented Pca (include/petal_hip_segments.h; an extension beyond the crate): Pca::inner_fit (pca.rs:195-231) of every row segment of a
+// row-sorted matrix.  Where the device-op layer has the segment kernel (d <= 64) the batch is one launch; otherwise -- wider data, or a
+// layer without the op (the host simulation): these weak defaults stand in wherever no strong definition is linked -- the single-matrix
+// code above runs segment by segment on row-slice views of the ONE ingested X.  Same results contract on both paths.
+__attribute__((weak)) bool op_pca_segments(Dev*, int, const void*, int64_t, int64_t, const int64_t*, int64_t, int64_t, bool, void*, void*,
+                                           void*, void*, int32_t*, void*) { return false; }
+__attribute__((weak)) bool op_transform_segments(Dev*, int, const void*, int64_t, const int64_t*, int64_t, const void*, const void*, int64_t,
+                                                 int64_t, void*) { return false; }
+__attribute__((weak)) bool op_inverse_transform_segments(Dev*, int, const void*, int64_t, const int64_t*, int64_t, const void*, const void*,
+                                                         int64_t, int64_t, void*) { return false; }
+namespace {
+void check_offsets(const int64_t* offsets, int64_t nseg, int64_t rows) {
+    if (nseg < 0) invalid_input("negative parameter");
+    if (!offsets) invalid_input("offsets must not be null");
+    if (offsets[0] != 0) invalid_input("offsets[0] should be 0 (it is " + std::to_string(offsets[0]) + ")");
+    for (int64_t b = 1; b <= nseg; ++b)
+        if (offsets[b] < offsets[b - 1])
+            invalid_input("offsets should not decrease: offsets[" + std::to_string(b) + "] = " + std::to_string(offsets[b]) + " is below offsets[" +
+                          std::to_string(b - 1) + "] = " + std::to_string(offsets[b - 1]));
+    if (offsets[nseg] != rows)
+        invalid_input("offsets[" + std::to_string(nseg) + "] should be the number of rows " + std::to_string(rows) + " (it is " +
+                      std::to_string(offsets[nseg]) + ")");
+}
+void check_output(const petal_matrix& out, int dt, int64_t rows, int64_t cols) {
+    check_matrix(out, "output");
+    if (out.dtype != dt) invalid_input("output dtype differs from input dtype");
+    if (out.rows != rows || out.cols != cols) invalid_input("output has the wrong shape");
+}
+// rows [r0, r0 + nb) of a caller's matrix, as a matrix of its own
+petal_matrix row_slice(const petal_matrix& m, int64_t r0, int64_t nb) {
+    petal_matrix v = m;
+    v.rows = nb;
+    if (m.data) v.data = static_cast<char*>(m.data) + r0 * m.row_stride * int64_t(dtype_size(m.dtype));
+    return v;
+}
+// the same of an ingested matrix: a device view the single-matrix entry points take in place when no column padding is missing
+petal_matrix row_slice(const DevMat& X, int64_t r0, int64_t nb) {
+    petal_matrix v{};
+    v.data = X.p ? const_cast<char*>(static_cast<const char*>(X.p)) + size_t(r0) * size_t(X.ld) * dtype_size(X.dtype) : nullptr;
+    v.rows = nb; v.cols = X.d; v.row_stride = X.ld; v.col_stride = 1; v.dtype = X.dtype; v.space = PETAL_DEVICE;
+    return v;
+}
+void fill_host(void* p, int dt, int64_t first, int64_t count, double v) {
+    if (p) for (int64_t i = 0; i < count; ++i) put_elem(p, dt, first + i, v);
+}
+// a per-segment, local operation: the single-matrix code it loops over must not see the ctx's collective
+struct LocalScope {
+    petal_ctx& c;
+    int rank, world;
+    petal_allreduce_fn fn;
+    explicit LocalScope(petal_ctx& ctx) : c(ctx), rank(ctx.rank), world(ctx.world), fn(ctx.allreduce) { c.rank = 0; c.world = 1; c.allreduce = nullptr; }
+    ~LocalScope() { c.rank = rank; c.world = world; c.allreduce = fn; }
+};
+}  // namespace
+
+void pca_fit_segments(petal_ctx& c, const petal_matrix& x, const int64_t* offsets, int64_t nseg, int64_t k, bool centering, void* components,
+                      void* means, void* singular, void* total_variance, int32_t* status, const petal_matrix* y_out, int64_t* kernel_segments) {
+    const Timer timer = start_fit(c, x);
+    if (k < 0) invalid_input("negative parameter");
+    const int dt = x.dtype;
+    const int64_t d = x.cols, rows = x.rows;
+    check_offsets(offsets, nseg, rows);
+    for (int64_t b = 0; b < nseg; ++b)   // pca.rs:199-204, per segment
+        if (offsets[b + 1] - offsets[b] < k || d < k)
+            invalid_input("segment " + std::to_string(b) + ": every dimension should be at least " + std::to_string(k));
+    if (y_out) check_output(*y_out, dt, rows, k);
+    if (kernel_segments) *kernel_segments = 0;
+    if (nseg == 0) return;
+    if (k > 0 && !components) invalid_input("components must not be null");
+    if (k > 0 && !singular) invalid_input("singular must not be null");
+    if ((d > 0 && !means) || !total_variance) invalid_input("means / total_variance must not be null");
+    const size_t esz = dtype_size(dt);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    DevMat X;
+    if (rows > 0 && d > 0) X = ingest(c, x);
+
+    if (rows > 0 && d > 0) {   // the segment kernel, where the device-op layer has it
+        DBuf comp(c.dev, esz * size_t(nseg) * size_t(k) * d), mu(c.dev, esz * size_t(nseg) * d), sg(c.dev, esz * size_t(nseg) * k);
+        DBuf tv(c.dev, esz * size_t(nseg)), st(c.dev, sizeof(int32_t) * size_t(nseg)), Y;
+        if (y_out && k > 0) Y = DBuf(c.dev, esz * size_t(rows) * k);
+        if (op_pca_segments(c.dev, dt, X.p, X.ld, d, offsets, nseg, k, centering, comp.p, mu.p, sg.p, tv.p, st.as<int32_t>(), Y.p)) {
+            std::vector<int32_t> hst;
+            if (!status) { hst.resize(size_t(nseg)); status = hst.data(); }
+            dev_d2h(c.dev, components, comp.p, comp.bytes);
+            dev_d2h(c.dev, means, mu.p, mu.bytes);
+            dev_d2h(c.dev, singular, sg.p, sg.bytes);
+            dev_d2h(c.dev, total_variance, tv.p, tv.bytes);
+            dev_d2h(c.dev, status, st.p, st.bytes);
+            if (Y.p) emit(c, dt, Y.p, rows, k, k, *y_out);
+            dev_sync(c.dev);
+            if (!hst.empty())
+                for (int64_t b = 0; b < nseg; ++b)
+                    if (hst[b] != 0) linalg_error("segment " + std::to_string(b) + ": did not converge");   // linalg.rs:84
+            if (kernel_segments) *kernel_segments = nseg;
+            finish_stats(c, timer);
+            return;
+        }
+    }
+
+    // the loop: Pca::fit of every segment on a row-slice view
+    LocalScope local(c);
+    for (int64_t b = 0; b < nseg; ++b) {
+        const int64_t r0 = offsets[b], nb = offsets[b + 1] - r0;
+        void* comp_b = components ? static_cast<char*>(components) + esz * size_t(b) * size_t(k) * d : nullptr;
+        void* mu_b = means ? static_cast<char*>(means) + esz * size_t(b) * d : nullptr;
+        void* sg_b = singular ? static_cast<char*>(singular) + esz * size_t(b) * k : nullptr;
+        void* tv_b = static_cast<char*>(total_variance) + esz * size_t(b);
+        if (status) status[b] = 0;
+        if (nb == 0) {   // (k == 0) an empty segment: zero means, zero variance
+            fill_host(mu_b, dt, 0, d, 0.0);
+            put_elem(tv_b, dt, 0, 0.0);
+            continue;
+        }
+        const petal_matrix xv = d > 0 ? row_slice(X, r0, nb) : row_slice(x, r0, nb);
+        petal_matrix yv{};
+        if (y_out) yv = row_slice(*y_out, r0, nb);
+        try {
+            pca_fit(c, xv, k, centering, comp_b, mu_b, sg_b, tv_b, y_out ? &yv : nullptr);
+        } catch (const Error& e) {
+            if (e.code != PETAL_LINALG_ERROR) throw;
+            if (!status) linalg_error("segment " + std::to_string(b) + ": " + e.what());
+            dev_abort(c.dev);
+            status[b] = 1;
+            fill_host(comp_b, dt, 0, k * d, nan);
+            fill_host(mu_b, dt, 0, d, nan);
+            fill_host(sg_b, dt, 0, k, nan);
+            put_elem(tv_b, dt, 0, nan);
+            if (y_out && k > 0) {
+                std::vector<char> h(esz * size_t(nb) * k);
+                fill_host(h.data(), dt, 0, nb * k, nan);
+                DBuf Yn(c.dev, h.size());
+                dev_h2d(c.dev, Yn.p, h.data(), h.size());
+                emit(c, dt, Yn.p, nb, k, k, yv);
+                dev_sync(c.dev);
+            }
+        }
+    }
+}
+
+namespace {
+// the arguments transform_segments and inverse_transform_segments share; returns true when there is nothing to compute
+void check_segment_model(const void* components, const void* means, int64_t k, int64_t d, bool centering) {
+    if (k < 0 || d < 0) invalid_input("negative parameter");
+    if (k > 0 && d > 0 && !components) invalid_input("components must not be null");
+    if (centering && d > 0 && !means) invalid_input("means must not be null");
+}
+}  // namespace
+
+void transform_segments(petal_ctx& c, const petal_matrix& x, const int64_t* offsets, int64_t nseg, const void* components, const void* means,
+                        int64_t k, int64_t d, bool centering, const petal_matrix& y_out) {
+    check_matrix(x, "input");
+    if (x.cols != d) invalid_input("# of columns should be " + std::to_string(d));  // pca.rs:736-741
+    check_segment_model(components, means, k, d, centering);
+    const int dt = x.dtype;
+    const int64_t rows = x.rows;
+    check_offsets(offsets, nseg, rows);
+    check_output(y_out, dt, rows, k);
+    if (rows == 0 || k == 0) return;
+    const size_t esz = dtype_size(dt);
+    if (d == 0) {   // no columns: every projection is zero
+        DBuf Z(c.dev, esz * size_t(rows) * k);
+        dev_memset(c.dev, Z.p, 0, Z.bytes);
+        emit(c, dt, Z.p, rows, k, k, y_out);
+        dev_sync(c.dev);
+        return;
+    }
+    DevMat X = ingest(c, x);
+    if (d <= 64 && k <= 64) {
+        DBuf comp(c.dev, esz * size_t(nseg) * size_t(k) * d), mu, Y(c.dev, esz * size_t(rows) * k);
+        dev_h2d_async(c.dev, comp.p, components, comp.bytes);
+        if (centering) { mu = DBuf(c.dev, esz * size_t(nseg) * d); dev_h2d_async(c.dev, mu.p, means, mu.bytes); }
+        if (op_transform_segments(c.dev, dt, X.p, X.ld, offsets, nseg, comp.p, mu.p, k, d, Y.p)) {
+            emit(c, dt, Y.p, rows, k, k, y_out);
+            dev_sync(c.dev);
+            return;
+        }
+    }
+    for (int64_t b = 0; b < nseg; ++b) {
+        const int64_t r0 = offsets[b], nb = offsets[b + 1] - r0;
+        if (nb == 0) continue;
+        transform(c, row_slice(X, r0, nb), static_cast<const char*>(components) + esz * size_t(b) * size_t(k) * d,
+                  means ? static_cast<const char*>(means) + esz * size_t(b) * d : nullptr, k, d, centering, row_slice(y_out, r0, nb));
+    }
+}
+
+void inverse_transform_segments(petal_ctx& c, const petal_matrix& y, const int64_t* offsets, int64_t nseg, const void* components,
+                                const void* means, int64_t k, int64_t d, bool centering, const petal_matrix& x_out) {
+    check_matrix(y, "input");
+    if (y.cols != k) invalid_input("# of columns should be " + std::to_string(k));  // pca.rs:798-803
+    check_segment_model(components, means, k, d, centering);
+    const int dt = y.dtype;
+    const int64_t rows = y.rows;
+    check_offsets(offsets, nseg, rows);
+    check_output(x_out, dt, rows, d);
+    if (rows == 0 || d == 0) return;
+    const size_t esz = dtype_size(dt);
+    DevMat Y;
+    if (k > 0) Y = ingest(c, y);
+    if (k > 0 && d <= 64 && k <= 64) {
+        DBuf comp(c.dev, esz * size_t(nseg) * size_t(k) * d), mu, Xo(c.dev, esz * size_t(rows) * d);
+        dev_h2d_async(c.dev, comp.p, components, comp.bytes);
+        if (centering) { mu = DBuf(c.dev, esz * size_t(nseg) * d); dev_h2d_async(c.dev, mu.p, means, mu.bytes); }
+        if (op_inverse_transform_segments(c.dev, dt, Y.p, Y.ld, offsets, nseg, comp.p, mu.p, k, d, Xo.p)) {
+            emit(c, dt, Xo.p, rows, d, d, x_out);
+            dev_sync(c.dev);
+            return;
+        }
+    }
+    for (int64_t b = 0; b < nseg; ++b) {
+        const int64_t r0 = offsets[b], nb = offsets[b + 1] - r0;
+        if (nb == 0) continue;
+        const petal_matrix yv = k > 0 ? row_slice(Y, r0, nb) : row_slice(y, r0, nb);
+        inverse_transform(c, yv, components ? static_cast<const char*>(components) + esz * size_t(b) * size_t(k) * d : nullptr,
+                          means ? static_cast<const char*>(means) + esz * size_t(b) * d : nullptr, k, d, centering, row_slice(x_out, r0, nb));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Row scores against a fitted projection (include/petal_hip_score.h; an extension beyond the crate): residual and weighted energy of
 // every row from the one pass of the product kernel.  A device-op layer may lack the op (the host simulation does): this default stands
 // in wherever no strong definition is linked, and refuses -- after every check of the arguments has been made.

@@ -6,6 +6,7 @@
 
 #include "ctx.h"
 #include "../../include/petal_hip_score.h"
+#include "../../include/petal_hip_segments.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -198,6 +199,39 @@ int petal_score_rows(petal_ctx* ctx, const petal_matrix* x, const void* componen
         need(x, "x");
         need(out, "out");
         score_rows(*ctx, *x, components, means, k, d, centering != 0, weights, *out, y_out);
+    });
+}
+
+// ---- include/petal_hip_segments.h: one exact Pca per row segment ------------------------------------------------------------------
+int petal_pca_fit_segments(petal_ctx* ctx, const petal_matrix* x, const int64_t* offsets, int64_t n_segments, int64_t k, int centering,
+                           void* components, void* means, void* singular, void* total_variance, int32_t* status,
+                           const petal_matrix* y_out, int64_t* kernel_segments) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(offsets, "offsets");
+        pca_fit_segments(*ctx, *x, offsets, n_segments, k, centering != 0, components, means, singular, total_variance, status, y_out,
+                         kernel_segments);
+    });
+}
+
+int petal_transform_segments(petal_ctx* ctx, const petal_matrix* x, const int64_t* offsets, int64_t n_segments, const void* components,
+                             const void* means, int64_t k, int64_t d, int centering, const petal_matrix* y_out) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(offsets, "offsets");
+        need(y_out, "y_out");
+        transform_segments(*ctx, *x, offsets, n_segments, components, means, k, d, centering != 0, *y_out);
+    });
+}
+
+int petal_inverse_transform_segments(petal_ctx* ctx, const petal_matrix* y, const int64_t* offsets, int64_t n_segments,
+                                     const void* components, const void* means, int64_t k, int64_t d, int centering,
+                                     const petal_matrix* x_out) {
+    return guarded(ctx, [&] {
+        need(y, "y");
+        need(offsets, "offsets");
+        need(x_out, "x_out");
+        inverse_transform_segments(*ctx, *y, offsets, n_segments, components, means, k, d, centering != 0, *x_out);
     });
 }
 

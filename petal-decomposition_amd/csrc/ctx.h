@@ -96,6 +96,14 @@ void score_rows(petal_ctx& c, const petal_matrix& x, const void* components, con
                 const void* weights, const petal_matrix& out, const petal_matrix* y_out);
 void inverse_transform(petal_ctx& c, const petal_matrix& y, const void* components, const void* means, int64_t k,
                        int64_t d, bool centering, const petal_matrix& x_out);
+// include/petal_hip_segments.h: one exact Pca per row segment
+void pca_fit_segments(petal_ctx& c, const petal_matrix& x, const int64_t* offsets, int64_t n_segments, int64_t k, bool centering,
+                      void* components, void* means, void* singular, void* total_variance, int32_t* status, const petal_matrix* y_out,
+                      int64_t* kernel_segments);
+void transform_segments(petal_ctx& c, const petal_matrix& x, const int64_t* offsets, int64_t n_segments, const void* components,
+                        const void* means, int64_t k, int64_t d, bool centering, const petal_matrix& y_out);
+void inverse_transform_segments(petal_ctx& c, const petal_matrix& y, const int64_t* offsets, int64_t n_segments, const void* components,
+                                const void* means, int64_t k, int64_t d, bool centering, const petal_matrix& x_out);
 void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, double tol, int64_t max_iter, int mode,
                  const void* w_init, void* components, void* means, int64_t* n_iter, const petal_matrix* y_out);
 void ica_par(petal_ctx& c, const petal_matrix& x1, double tol, int64_t max_iter, int mode, const void* w_init,

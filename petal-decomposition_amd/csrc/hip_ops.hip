@@ -17,6 +17,7 @@
 //     Cholesky + explicit inverse), k_tridiag_r / k_tridiag_w +
 //     k_trieig_r (symmetric eigenproblem up to order 138), k_jacobi_* (fallbacks and one-sided SVD), k_symdecorr / k_ica_tail
 //     (symmetric decorrelation: scaled Newton-Schulz polar factor in LDS)
+//   segmented Pca: k_pca_segments (one workgroup per row segment: means, fp64 Gram, wg_jacobi_fast, svd_flip, outputs), k_seg_project
 //   *_simple     generic (any shape, f32 / f64, fp64 accumulate) kernels for small / unaligned / f64 inputs
 //
 // wave = 64 lanes everywhere.  MFMA 16x16x4 f32 fragment maps (cdna_hip_programming.md section 3):
@@ -578,4 +579,5 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #include "kernels/host_small.inc"   // host-side launchers: FastICA step / tail, fp64 small-matrix ops, re-basing
 #include "kernels/k_gram.inc"   // the split-product Gram kernel of the FastICA whitening (k_gram5) and its launcher
 #include "kernels/host_pow3_eigh.inc"   // host-side launchers: the fused pass, Cholesky / eigen-solver / remaining small ops
+#include "kernels/k_pca_segments.inc"   // segmented Pca: one workgroup per row segment (k_pca_segments), k_seg_project, their launchers
 }  // namespace petal

@@ -142,6 +142,20 @@ void op_gemm_xp_absmax(Dev*, int dtype, const void* X, int64_t n, int64_t K, int
 // any-shape kernel, one wave per row: the slow path).
 void op_gemm_xp_scores(Dev*, int dtype, const void* X, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* P, int64_t N,
                        int64_t ldp, const void* wts, void* Z, int64_t ldz, void* st, int64_t ldst);
+// Segmented Pca (include/petal_hip_segments.h; an extension beyond the crate): an exact Pca of every row segment [offsets[b], offsets[b + 1])
+// of X (row-major, unit column stride, ldx) in ONE launch, a workgroup per segment.  offsets: HOST, nseg + 1 values, validated by the
+// caller.  Results to DEVICE buffers in dtype: comp nseg x k x d (svd_flip's sign applied), means nseg x d, sing nseg x k, tv nseg;
+// status nseg int32 (1: the segment holds a non-finite value -- its results and its rows of Y are NaN); Y (nullable): rows x k, leading
+// dimension k, = Xc V_k^T signed.  Each returns "this layer did the work": false, NOTHING done, where the layer has no kernel for the
+// shape (d > 64) or lacks the op altogether -- algo.cpp's weak defaults return false, and the caller then loops over the segments with
+// the single-matrix code.  op_transform_segments / op_inverse_transform_segments: comp and means (nullable: no centring) are DEVICE
+// arrays in dtype as above; Y / X out: rows x k / rows x d with leading dimension k / d.
+bool op_pca_segments(Dev*, int dtype, const void* X, int64_t ldx, int64_t d, const int64_t* offsets, int64_t nseg, int64_t k, bool centering,
+                     void* comp, void* means, void* sing, void* tv, int32_t* status, void* Y);
+bool op_transform_segments(Dev*, int dtype, const void* X, int64_t ldx, const int64_t* offsets, int64_t nseg, const void* comp,
+                           const void* means, int64_t k, int64_t d, void* Y);
+bool op_inverse_transform_segments(Dev*, int dtype, const void* Y, int64_t ldy, const int64_t* offsets, int64_t nseg, const void* comp,
+                                   const void* means, int64_t k, int64_t d, void* X);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.

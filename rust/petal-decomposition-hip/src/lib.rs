@@ -4,11 +4,12 @@
 //! (`src/pca.rs:41-51, 317-329`, `src/ica.rs:41-50`), so serde persistence keeps its field names.
 mod ffi;
 mod ffi_score;
+mod ffi_segments;
 mod ica;
 mod pca;
 
 pub use ica::{Contrast, FastIca, FastIcaBuilder};
-pub use pca::{Pca, PcaBuilder, RandomizedPca, RandomizedPcaBuilder};
+pub use pca::{Pca, PcaBuilder, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
 
 use ndarray::{ArrayBase, Data, Ix2};
 use std::ffi::CStr;

@@ -1,6 +1,6 @@
 //! `Pca` (`src/pca.rs:41-231` of the reference) and `RandomizedPca` (`src/pca.rs:317-663`) over the C ABI.
-use crate::{ffi, ffi_score, view, with_ctx, DecompositionError, HipScalar};
-use ndarray::{Array1, Array2, ArrayBase, Data, Ix2};
+use crate::{ffi, ffi_score, ffi_segments, view, with_ctx, DecompositionError, HipScalar};
+use ndarray::{Array1, Array2, Array3, ArrayBase, Data, Ix2};
 use rand::Rng;
 use rand_distr::StandardNormal;
 use rand_pcg::Mcg128Xsl64 as Pcg;
@@ -339,4 +339,122 @@ fn score_samples<A: HipScalar, S: Data<Elem = A>>(
         + (d - k) as f64 * s2.ln();
     let sc = score_rows(input, components, means, centering, Some(&w))?;
     Ok(Array1::from_iter(sc.rows().into_iter().map(|r| A::from_f64(-0.5 * (c + r[0].to_f64() / s2 + r[1].to_f64())))))
+}
+
+/// One exact `Pca` per row segment of a row-sorted matrix, in one call (include/petal_hip_segments.h: an extension beyond the crate).
+/// Segment `b` is rows `offsets[b] .. offsets[b + 1]` and gets what `Pca::fit` gives on those rows alone; for d <= 64 the batch is one
+/// launch, a workgroup per segment (a very long segment is correct and not fast: fit it with `Pca`).
+pub struct SegmentedPca<A: HipScalar> {
+    n_components: usize,
+    centering: bool,
+    components: Array3<A>,
+    means: Array2<A>,
+    singular: Array2<A>,
+    total_variance: Array1<A>,
+    status: Vec<i32>,
+    kernel_segments: i64,
+}
+
+impl<A: HipScalar> SegmentedPca<A> {
+    pub fn new(n_components: usize) -> Self { Self::with_centering(n_components, true) }
+    pub fn with_centering(n_components: usize, centering: bool) -> Self {
+        SegmentedPca {
+            n_components, centering, components: Array3::default((0, n_components, 0)), means: Array2::default((0, 0)),
+            singular: Array2::default((0, n_components)), total_variance: Array1::default(0), status: Vec::new(), kernel_segments: 0,
+        }
+    }
+    /// (B, k, d), svd_flip's sign applied
+    pub fn components(&self) -> &Array3<A> { &self.components }
+    pub fn mean(&self) -> &Array2<A> { &self.means }
+    pub fn n_components(&self) -> usize { self.n_components }
+    pub fn singular_values(&self) -> &Array2<A> { &self.singular }
+    /// 0: fitted; 1: the segment held a NaN or an infinity and its results are NaN
+    pub fn status(&self) -> &[i32] { &self.status }
+    /// how many segments of the last fit the segment kernel fitted (0: the call looped over `Pca`'s code)
+    pub fn kernel_segments(&self) -> i64 { self.kernel_segments }
+    pub fn explained_variance_ratio(&self) -> Array2<A> {
+        let mut r = self.singular.clone();
+        for (b, mut row) in r.rows_mut().into_iter().enumerate() {
+            let tv = self.total_variance[b].to_f64();
+            row.mapv_inplace(|s| A::from_f64(s.to_f64() * s.to_f64() / tv));
+        }
+        r
+    }
+
+    pub fn fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, offsets: &[i64]) -> Result<(), DecompositionError> {
+        self.inner_fit(input, offsets, None)
+    }
+    pub fn fit_transform<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, offsets: &[i64]) -> Result<Array2<A>, DecompositionError> {
+        let mut y = Array2::<A>::default((input.nrows(), self.n_components));
+        self.inner_fit(input, offsets, Some(&mut y))?;
+        Ok(y)
+    }
+    pub fn transform<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>, offsets: &[i64]) -> Result<Array2<A>, DecompositionError> {
+        let (nseg, d) = self.means.dim();
+        check_offsets_len(offsets, nseg)?;
+        let mut y = Array2::<A>::default((input.nrows(), self.n_components));
+        let (x, yv) = (view(input), view(&y));
+        with_ctx(
+            |ctx| unsafe {
+                ffi_segments::petal_transform_segments(ctx, &x, offsets.as_ptr(), nseg as i64, self.components.as_ptr() as *const c_void,
+                    self.means.as_ptr() as *const c_void, self.n_components as i64, d as i64, self.centering as i32, &yv)
+            },
+            || (),
+        )?;
+        let _ = &mut y; // written through yv
+        Ok(y)
+    }
+    pub fn inverse_transform<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>, offsets: &[i64]) -> Result<Array2<A>, DecompositionError> {
+        let (nseg, d) = self.means.dim();
+        check_offsets_len(offsets, nseg)?;
+        let mut x_out = Array2::<A>::default((input.nrows(), d));
+        let (yv, xv) = (view(input), view(&x_out));
+        with_ctx(
+            |ctx| unsafe {
+                ffi_segments::petal_inverse_transform_segments(ctx, &yv, offsets.as_ptr(), nseg as i64,
+                    self.components.as_ptr() as *const c_void, self.means.as_ptr() as *const c_void, self.n_components as i64, d as i64,
+                    self.centering as i32, &xv)
+            },
+            || (),
+        )?;
+        let _ = &mut x_out;
+        Ok(x_out)
+    }
+
+    fn inner_fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, offsets: &[i64], y: Option<&mut Array2<A>>) -> Result<(), DecompositionError> {
+        if offsets.is_empty() {
+            return Err(DecompositionError::InvalidInput("offsets needs n_segments + 1 values".into()));
+        }
+        let (nseg, k, d) = (offsets.len() - 1, self.n_components, input.ncols());
+        let mut comps = Array3::<A>::default((nseg, k, d));
+        let mut means = Array2::<A>::default((nseg, d));
+        let mut sing = Array2::<A>::default((nseg, k));
+        let mut tv = Array1::<A>::default(nseg);
+        let mut status = vec![0i32; nseg];
+        let mut ks = 0i64;
+        let x = view(input);
+        let yv = y.as_ref().map(|y| view(&**y));
+        with_ctx(
+            |ctx| unsafe {
+                ffi_segments::petal_pca_fit_segments(ctx, &x, offsets.as_ptr(), nseg as i64, k as i64, self.centering as i32,
+                    comps.as_mut_ptr() as *mut c_void, means.as_mut_ptr() as *mut c_void, sing.as_mut_ptr() as *mut c_void,
+                    tv.as_mut_ptr() as *mut c_void, status.as_mut_ptr(), yv.as_ref().map_or(std::ptr::null(), |v| v as *const _), &mut ks)
+            },
+            || (),
+        )?;
+        self.components = comps;
+        self.means = means;
+        self.singular = sing;
+        self.total_variance = tv;
+        self.status = status;
+        self.kernel_segments = ks;
+        Ok(())
+    }
+}
+
+fn check_offsets_len(offsets: &[i64], nseg: usize) -> Result<(), DecompositionError> {
+    if offsets.len() != nseg + 1 {
+        return Err(DecompositionError::InvalidInput(format!("the model holds {} segments, offsets describe {}", nseg, offsets.len() as i64 - 1)));
+    }
+    Ok(())
 }
