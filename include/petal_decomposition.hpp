@@ -23,6 +23,7 @@
 #include "petal_hip.h"
 #include "petal_hip_score.h"
 #include "petal_hip_segments.h"
+#include "petal_hip_sparse.h"
 
 namespace petal_decomposition {
 
@@ -370,6 +371,47 @@ class PcaBuilder {  // src/pca.rs:246-283
     int64_t k_; bool centering_ = true; Context* ctx_ = nullptr;
 };
 
+// A sparse matrix in CSR form, resident with its ctx (petal_hip_sparse.h: an extension beyond the crate).  The arrays are checked and
+// copied, the transposed image and the work items are built on the host, both images are uploaded once; RandomizedPca::fit,
+// fit_transform and transform take it in place of an Array2.  Indices inside a row need not be sorted, duplicates act as their sum.
+// Destroy it before its Context.
+template <class A>
+class CsrMatrix {
+  public:
+    CsrMatrix(int64_t rows, int64_t cols, const std::vector<int64_t>& indptr, const std::vector<int32_t>& indices, const std::vector<A>& values,
+              Context* ctx = nullptr)
+        : rows_(rows), cols_(cols), nnz_(int64_t(values.size())), ctx_(ctx) {
+        if (int64_t(indptr.size()) != rows + 1)
+            throw DecompositionError(DecompositionError::InvalidInput, "indptr should have " + std::to_string(rows + 1) + " entries");
+        if (indices.size() != values.size()) throw DecompositionError(DecompositionError::InvalidInput, "indices and values differ in length");
+        context().check(petal_csr_create(context().get(), rows, cols, nnz_, indptr.data(), indices.data(), values.data(),
+                                         sizeof(A) == 4 ? PETAL_F32 : PETAL_F64, &h_));
+    }
+    CsrMatrix(const CsrMatrix&) = delete;
+    CsrMatrix& operator=(const CsrMatrix&) = delete;
+    CsrMatrix(CsrMatrix&& o) noexcept : rows_(o.rows_), cols_(o.cols_), nnz_(o.nnz_), ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    ~CsrMatrix() { petal_csr_destroy(h_); }
+    int64_t nrows() const { return rows_; }
+    int64_t ncols() const { return cols_; }
+    int64_t nnz() const { return nnz_; }
+    bool resident() const { int64_t v[8]; petal_csr_info(h_, v); return v[4] != 0; }   // false: no sparse kernel in the device-op layer, the entries densify
+    const petal_csr* get() const { return h_; }
+    Context& context() const { return ctx_ ? *ctx_ : Context::global(); }
+    // test aid (petal_csr_gemm): X . P or X^T . P minus a s^T (s empty: no epilogue; a empty: all ones), row-major float64
+    std::vector<double> gemm(const std::vector<double>& p, int64_t n, bool transposed = false, const std::vector<double>& a = {},
+                             const std::vector<double>& s = {}) const {
+        std::vector<double> out(size_t((transposed ? cols_ : rows_) * n));
+        context().check(petal_csr_gemm(context().get(), h_, transposed, p.data(), n, a.empty() ? nullptr : a.data(), s.empty() ? nullptr : s.data(),
+                                       out.data()));
+        return out;
+    }
+
+  private:
+    int64_t rows_, cols_, nnz_;
+    Context* ctx_;
+    petal_csr* h_ = nullptr;
+};
+
 template <class A, class R = Pcg>
 class RandomizedPca {  // src/pca.rs:317-551
   public:
@@ -392,6 +434,23 @@ class RandomizedPca {  // src/pca.rs:317-551
     }
     Array2<A> transform(const Array2<A>& input) const { return st_.transform(input); }
     Array2<A> inverse_transform(const Array2<A>& input) const { return st_.inverse_transform(input); }
+    // extension beyond the crate (petal_hip_sparse.h): sparse CSR input, never densified.  Row scores take dense input only.
+    void fit(const CsrMatrix<A>& input) { inner_fit_sparse(input, nullptr); }
+    Array2<A> fit_transform(const CsrMatrix<A>& input) {
+        Array2<A> y(input.nrows(), st_.k);
+        inner_fit_sparse(input, &y);
+        return y;
+    }
+    Array2<A> transform(const CsrMatrix<A>& input) {
+        const int64_t d = int64_t(st_.means.size());
+        if (input.ncols() != d) throw DecompositionError(DecompositionError::InvalidInput, "# of columns should be " + std::to_string(d));
+        Array2<A> y(input.nrows(), st_.k);
+        petal_matrix my = y.view();
+        st_.context().check(petal_transform_csr(st_.context().get(), input.get(), st_.components.data.data(), st_.means.data(), st_.k, d,
+                                                st_.centering, &my, &kernel_path_));
+        return y;
+    }
+    int64_t kernel_path() const { return kernel_path_; }   // the last sparse call: 1 the sparse product kernel, 0 the densifying fall-back
     // extension beyond the crate (petal_hip_score.h): scores of rows against the fitted model, one pass over the input each
     std::vector<A> explained_variance() const { return st_.explained_variance(); }
     A noise_variance() const { return st_.noise_variance(); }
@@ -423,8 +482,29 @@ class RandomizedPca {  // src/pca.rs:317-551
         st_.components = std::move(comp); st_.means = std::move(means); st_.singular = std::move(sing);
         st_.total_variance = tv; st_.n_samples = input.nrows();
     }
+    void inner_fit_sparse(const CsrMatrix<A>& input, Array2<A>* y) {
+        const int64_t d = input.ncols(), k = st_.k, l = k + N_OVERSAMPLE;
+        std::vector<A> omega;
+        const bool will_draw = !(input.nrows() < k || d < k) && !(st_.centering && input.nrows() == 0);
+        if (will_draw) {
+            omega.resize(size_t(d) * l);
+            for (auto& v : omega) v = A(rng_.standard_normal());
+        }
+        Array2<A> comp(k, d);
+        std::vector<A> means(d), sing(k);
+        A tv = A(0);
+        petal_matrix my{};
+        if (y) my = y->view();
+        st_.context().check(petal_rpca_fit_csr(st_.context().get(), input.get(), k, N_OVERSAMPLE, N_ITER, st_.centering,
+                                               omega.empty() ? nullptr : omega.data(), comp.data.data(), means.data(), sing.data(), &tv,
+                                               y ? &my : nullptr, &kernel_path_));
+        if (st_.centering && input.nrows() == 0) return;
+        st_.components = std::move(comp); st_.means = std::move(means); st_.singular = std::move(sing);
+        st_.total_variance = tv; st_.n_samples = input.nrows();
+    }
     R rng_;
     detail::PcaState<A> st_;
+    int64_t kernel_path_ = 0;
 };
 
 template <class R = Pcg>

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from typing import Optional
 
 import numpy as np
@@ -151,6 +152,21 @@ ABI_PROBE = [
                                     C.c_double, _D, C.c_int64, _D]),
 ]
 
+# every symbol include/petal_hip_sparse.h declares (RandomizedPca on sparse CSR data: an extension beyond the crate, kept apart from the
+# mirrored set above)
+_I32 = C.POINTER(C.c_int32)
+ABI_SPARSE = [
+    ("petal_csr_create", C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _L, _I32, _P, C.c_int32, C.POINTER(_P)]),
+    ("petal_csr_destroy", None, [_P]),
+    ("petal_csr_info", C.c_int, [_P, _L]),
+    ("petal_csr_image", C.c_int, [_P, C.c_int, _L, _I32, _P, _L]),
+    ("petal_rpca_fit_csr", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _M, _L]),
+    ("petal_transform_csr", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, _M, _L]),
+    ("petal_csr_gemm", C.c_int, [_P, _P, C.c_int, _D, C.c_int64, _D, _D, _D]),
+    ("petal_ctx_workspace_in_use", C.c_int, [_P, _L, _L]),
+]
+CSR_ITEM_NNZ = 256   # PETAL_CSR_ITEM_NNZ
+
 
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
@@ -168,7 +184,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -177,7 +193,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -271,9 +287,12 @@ class Context:
             raise DeviceError(f"petal_ctx_create(device={device}) failed with code {rc}: no usable gfx950 device? "
                               f"(library {getattr(self.lib, '_petal_path', '?')})")
         self.rank, self.world_size = 0, 1
+        self._csr = weakref.WeakSet()   # the sparse matrices resident with this ctx: released before it
 
     def close(self):
         if getattr(self, "_h", None):
+            for m in list(getattr(self, "_csr", ())):
+                m.close()
             self.lib.petal_ctx_destroy(self._h)
             self._h = None
 
@@ -288,6 +307,13 @@ class Context:
             return
         msg = (self.lib.petal_last_error(self._h) or b"").decode()
         raise {PETAL_INVALID_INPUT: InvalidInput, PETAL_LINALG_ERROR: LinalgError}.get(rc, DeviceError)(msg)
+
+    def workspace_in_use(self):
+        """(blocks, bytes) of device memory the ctx's allocator has handed out and not got back (test aid, include/petal_hip_sparse.h);
+        (-1, -1) where the device-op layer keeps no count."""
+        blocks, nbytes = C.c_int64(0), C.c_int64(0)
+        self.check(self.lib.petal_ctx_workspace_in_use(self._h, C.byref(blocks), C.byref(nbytes)))
+        return int(blocks.value), int(nbytes.value)
 
     def set_profiling(self, level):
         """0/False off, 1/True one sampled launch of each hot kernel per fit, 2 every launch (petal_hip.h)."""
@@ -436,6 +462,116 @@ def _rng_to_serde(rng):
 
 
 # ------------------------------------------------------------------------------------------------
+def _is_sparse(x) -> bool:
+    """A CsrMatrix, or any object with .data / .indices / .indptr / .shape (scipy.sparse.csr_matrix among them; scipy is never imported)."""
+    if isinstance(x, CsrMatrix):
+        return True
+    if isinstance(x, np.ndarray) or _is_torch(x):
+        return False
+    return all(hasattr(x, a) for a in ("data", "indices", "indptr", "shape"))
+
+
+class CsrMatrix:
+    """A sparse matrix in CSR form, resident with its ctx (``petal_csr``, include/petal_hip_sparse.h): the arrays are checked, the
+    transposed image and the work items of both images are built on the host, and both images are uploaded once.  ``RandomizedPca.fit``,
+    ``fit_transform`` and ``transform`` take it in place of a dense matrix.  An extension beyond the crate.
+
+    ``indices`` inside a row need not be sorted, duplicates act as their sum, explicit zeros, empty rows and empty columns are legal."""
+
+    def __init__(self, data, indices, indptr, shape, ctx: Optional["Context"] = None):
+        data = np.asarray(data)
+        if data.dtype not in (np.float32, np.float64):
+            data = data.astype(np.float64)
+        data = np.ascontiguousarray(data).ravel()
+        if len(tuple(shape)) != 2:
+            raise InvalidInput("expected a 2-D shape")
+        rows, cols = int(shape[0]), int(shape[1])
+        if cols >= 2 ** 31 or rows >= 2 ** 31:
+            raise InvalidInput("sparse input: too many rows/columns (32-bit indices)")
+        idx = np.asarray(indices).ravel()
+        if idx.size and (int(idx.max()) >= 2 ** 31 or int(idx.min()) < -2 ** 31):
+            raise InvalidInput("sparse input: a column index does not fit 32 bits")
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        ptr = np.ascontiguousarray(np.asarray(indptr).ravel(), dtype=np.int64)
+        if ptr.size != rows + 1:
+            raise InvalidInput(f"indptr should have {rows + 1} entries (it has {ptr.size})")
+        if idx.size != data.size:
+            raise InvalidInput(f"indices and data differ in length ({idx.size} and {data.size})")
+        self.ctx = ctx if ctx is not None else default_context()
+        self.shape, self.nnz, self.dtype = (rows, cols), int(data.size), data.dtype
+        self._dt = PETAL_F32 if data.dtype == np.float32 else PETAL_F64
+        self._h = C.c_void_p()
+        lib = self.ctx.lib
+        self.ctx.check(lib.petal_csr_create(self.ctx._h, rows, cols, self.nnz, ptr.ctypes.data_as(_L), idx.ctypes.data_as(_I32),
+                                            data.ctypes.data, self._dt, C.byref(self._h)))
+        self.ctx._csr.add(self)
+
+    @classmethod
+    def from_scipy_like(cls, obj, ctx: Optional["Context"] = None):
+        """From any object with ``.data``, ``.indices``, ``.indptr`` and ``.shape`` laid out as CSR."""
+        if isinstance(obj, cls):
+            return obj
+        return cls(obj.data, obj.indices, obj.indptr, obj.shape, ctx=ctx)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self.ctx.lib.petal_csr_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise InvalidInput("the sparse matrix was closed (or its ctx was)")
+        return self._h
+
+    def info(self) -> dict:
+        out = (C.c_int64 * 8)()
+        if self.ctx.lib.petal_csr_info(self._handle(), out) != PETAL_OK:
+            raise InvalidInput("petal_csr_info failed")
+        keys = ("rows", "cols", "nnz", "dtype", "resident", "items", "items_transposed", "item_nnz")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    @property
+    def resident(self) -> bool:
+        return bool(self.info()["resident"])
+
+    def image(self, transposed: bool = False):
+        """Debug accessor of a handle that is not resident: (indptr, indices, values, items) of the matrix or of its transposed image as
+        the library built them; items is an (n, 3) array of (image row, first position, one past the last)."""
+        inf = self.info()
+        rows = inf["cols"] if transposed else inf["rows"]
+        ptr, idx = np.zeros(rows + 1, dtype=np.int64), np.zeros(self.nnz, dtype=np.int32)
+        val = np.zeros(self.nnz, dtype=self.dtype)
+        items = np.zeros((inf["items_transposed" if transposed else "items"], 3), dtype=np.int64)
+        self.ctx.check(self.ctx.lib.petal_csr_image(self._handle(), int(bool(transposed)), ptr.ctypes.data_as(_L), idx.ctypes.data_as(_I32),
+                                                    val.ctypes.data, items.ctypes.data_as(_L)))
+        return ptr, idx, val, items
+
+
+def csr_gemm(x: "CsrMatrix", p, transposed: bool = False, a=None, s=None):
+    """Test aid (``petal_csr_gemm``): ``x @ p`` or ``x.T @ p`` through the sparse product, minus ``outer(a, s)`` when ``s`` is given
+    (``a`` defaults to ones) -- the implicit centring.  float64 in and out; a float32 matrix rounds ``p`` and the result to float32."""
+    p = np.ascontiguousarray(np.asarray(p, dtype=np.float64))
+    rows, inner = (x.shape[1], x.shape[0]) if transposed else x.shape
+    if p.ndim != 2 or p.shape[0] != inner:
+        raise InvalidInput(f"expected {inner} rows in p")
+    N = p.shape[1]
+    out = np.zeros((rows, N))
+    a = None if a is None else _host(a, PETAL_F64, (rows,))
+    s = None if s is None else _host(s, PETAL_F64, (N,))
+    ctx = x.ctx
+    ctx.check(ctx.lib.petal_csr_gemm(ctx._h, x._handle(), int(bool(transposed)), p.ctypes.data_as(_D), N,
+                                     a.ctypes.data_as(_D) if a is not None else None, s.ctypes.data_as(_D) if s is not None else None,
+                                     out.ctypes.data_as(_D)))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 class _PcaModel:
     """State shared by Pca and RandomizedPca (src/pca.rs:41-51, 317-329)."""
 
@@ -485,6 +621,8 @@ class _PcaModel:
         return np.asarray((float(self._total_variance) - float(np.sum(s * s))) / (self.n_samples - 1) / rest, dtype=self._singular.dtype)[()]
 
     def _score(self, x, weights):
+        if _is_sparse(x):
+            raise InvalidInput("row scores (reconstruction_error, hotelling_t2, score_samples) are not available for sparse input")
         return score_rows(x, self._components, self._means, weights=weights, centering=self.centering, ctx=self._ctx())[0]
 
     def reconstruction_error(self, x):
@@ -770,6 +908,7 @@ class RandomizedPca(_PcaModel):
         self.rng = rng if rng is not None else np.random.default_rng()
         self.n_oversample = self.N_OVERSAMPLE if n_oversample is None else int(n_oversample)
         self.n_iter = self.N_ITER if n_iter is None else int(n_iter)
+        self.kernel_path = None   # sparse input: 1 when the sparse product kernel ran, 0 for the densifying fall-back
 
     @classmethod
     def new(cls, n_components: int, ctx=None):
@@ -800,7 +939,69 @@ class RandomizedPca(_PcaModel):
         size = self._k + self.n_oversample
         return self.rng.standard_normal((d, size)).astype(_np_dtype(dtype_code))  # f64 draw cast to A::Real
 
+    def _sparse(self, x):
+        """x as a CsrMatrix on this model's ctx, and whether it was made here (and is released when the call is over)."""
+        if isinstance(x, CsrMatrix):
+            if self.ctx is None:
+                self.ctx = x.ctx
+            return x, False
+        return CsrMatrix.from_scipy_like(x, ctx=self._ctx()), True
+
+    def _inner_fit_sparse(self, x, want_y: bool, omega=None):
+        """fit / fit_transform on sparse input (include/petal_hip_sparse.h): X is never densified; ``kernel_path`` says whether the
+        sparse product kernel ran (1) or the library's densifying fall-back (0: a device-op layer without the kernel)."""
+        sx, mine = self._sparse(x)
+        try:
+            ctx = self._ctx()
+            rows, cols = sx.shape
+            npdt = _np_dtype(sx._dt)
+            if omega is None:
+                omega = self.draw_omega(cols, sx._dt)
+            omega = _host(omega, sx._dt, (cols, self._k + self.n_oversample))
+            comp, means = np.empty((self._k, cols), dtype=npdt), np.zeros(cols, dtype=npdt)
+            sing, tv = np.empty(self._k, dtype=npdt), np.zeros(1, dtype=npdt)
+            keep, y, my = [], None, None
+            if want_y:
+                y = np.empty((rows, self._k), dtype=npdt)
+                my = describe(y, keep)
+            path = C.c_int64(0)
+            ctx.check(ctx.lib.petal_rpca_fit_csr(ctx._h, sx._handle(), self._k, self.n_oversample, self.n_iter, int(self.centering),
+                                                 omega.ctypes.data, comp.ctypes.data, means.ctypes.data, sing.ctypes.data, tv.ctypes.data,
+                                                 C.byref(my) if my is not None else None, C.byref(path)))
+            self.kernel_path = int(path.value)
+            if not (self.centering and rows == 0):
+                self._store(comp, means, sing, tv, rows)
+            return y
+        finally:
+            if mine:
+                sx.close()
+
+    def transform(self, x):
+        """src/pca.rs:444-449; sparse input (a CsrMatrix or an object with .data / .indices / .indptr / .shape) goes through the sparse product."""
+        if not _is_sparse(x):
+            return super().transform(x)
+        sx, mine = self._sparse(x)
+        try:
+            ctx = self._ctx()
+            d = self._means.shape[0]
+            if sx.shape[1] != d:
+                raise InvalidInput(f"# of columns should be {d}")
+            keep = []
+            y = np.empty((sx.shape[0], self._k), dtype=_np_dtype(sx._dt))
+            my = describe(y, keep)
+            comp, mu = _host(self._components, sx._dt), _host(self._means, sx._dt)
+            path = C.c_int64(0)
+            ctx.check(ctx.lib.petal_transform_csr(ctx._h, sx._handle(), comp.ctypes.data, mu.ctypes.data, self._k, d, int(self.centering),
+                                                  C.byref(my), C.byref(path)))
+            self.kernel_path = int(path.value)
+            return y
+        finally:
+            if mine:
+                sx.close()
+
     def _inner_fit(self, x, want_y: bool, omega=None):
+        if _is_sparse(x):
+            return self._inner_fit_sparse(x, want_y, omega)
         keep = []
         mx = describe(x, keep)
         ctx = self._ctx()

@@ -7,8 +7,10 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
+#include <memory>
 
 #include "ctx.h"
+#include "../../include/petal_hip_sparse.h"
 
 namespace petal {
 
@@ -2130,6 +2132,401 @@ void probe_dgemm(petal_ctx& c, bool ta, bool tb, int64_t M, int64_t N, int64_t K
     dev_sync(c.dev);
     for (int64_t i = 0; i < M; ++i)
         for (int64_t j = 0; j < (i < M - 1 ? ldc : N); ++j) C[i * ldc + j] = ch[size_t(i) * ldc + j];
+}
+
+// ---------------------------------------------------------------------------------------------
+// RandomizedPca on sparse CSR data (include/petal_hip_sparse.h; an extension beyond the crate).  The range finder (pca.rs:689-718) needs
+// only X . P and X^T . Z; the centring stays implicit (Xc P = X P - 1 (mu^T P), Xc^T Z = X^T Z - mu (1^T Z)), so X is never densified.
+// A device-op layer without the sparse product (the host simulation) gets these weak defaults: the handle then keeps its host arrays,
+// the fit and the transform densify into a host matrix and run the dense entries, and petal_csr_gemm is a plain host loop.
+__attribute__((weak)) bool op_csr_supported(Dev*) { return false; }
+__attribute__((weak)) bool dev_live(Dev*, int64_t*, int64_t*) { return false; }
+__attribute__((weak)) bool op_csr_gemm(Dev*, int, const CsrImage&, const void*, int64_t, int64_t, const double*, const double*, void*, int64_t) {
+    return false;
+}
+__attribute__((weak)) bool op_csr_colstats(Dev*, int, const CsrImage&, double*) { return false; }
+__attribute__((weak)) bool op_tall_times_small(Dev*, int, const void*, int64_t, int64_t, int64_t, const double*, int64_t, int64_t, void*, int64_t) {
+    return false;
+}
+
+namespace {
+constexpr int64_t CSR_ITEM_NNZ = PETAL_CSR_ITEM_NNZ;
+
+// The work items of one image: a row of at most CSR_ITEM_NNZ nonzeros (an empty one too) is one item that owns its output row; a longer
+// row becomes consecutive items with consecutive partial-result slots and one CsrSplit that names them.
+void csr_build_items(petal_csr::Image& im, int64_t rows) {
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t first = im.ptr[r], len = im.ptr[r + 1] - first;
+        if (len <= CSR_ITEM_NNZ) { im.items.push_back({first, int32_t(r), int32_t(len), -1, 0}); continue; }
+        const int64_t pieces = (len + CSR_ITEM_NNZ - 1) / CSR_ITEM_NNZ;
+        if (im.n_slots + pieces >= (int64_t(1) << 31)) invalid_input("too many nonzeros");
+        im.splits.push_back({int32_t(r), int32_t(im.n_slots), int32_t(pieces), 0});
+        for (int64_t q = 0; q < pieces; ++q)
+            im.items.push_back({first + q * CSR_ITEM_NNZ, int32_t(r), int32_t(std::min(CSR_ITEM_NNZ, len - q * CSR_ITEM_NNZ)), int32_t(im.n_slots++), 0});
+    }
+}
+void csr_upload(petal_ctx& c, petal_csr& x, int t) {
+    petal_csr::Image& im = x.host[t];
+    const void* src[4] = {im.idx.data(), im.val.data(), im.items.data(), im.splits.data()};
+    const size_t bytes[4] = {sizeof(int32_t) * im.idx.size(), im.val.size(), sizeof(CsrItem) * im.items.size(), sizeof(CsrSplit) * im.splits.size()};
+    for (int b = 0; b < 4; ++b) {
+        if (!bytes[b]) continue;
+        x.blocks[t][b] = dev_alloc(c.dev, bytes[b]);
+        dev_h2d(c.dev, x.blocks[t][b], src[b], bytes[b]);
+    }
+    CsrImage& dv = x.dev[t];
+    dv.rows = t ? x.cols : x.rows;
+    dv.nnz = x.nnz;
+    dv.idx = static_cast<const int32_t*>(x.blocks[t][0]);
+    dv.val = x.blocks[t][1];
+    dv.items = static_cast<const CsrItem*>(x.blocks[t][2]);
+    dv.n_items = int64_t(im.items.size());
+    dv.splits = static_cast<const CsrSplit*>(x.blocks[t][3]);
+    dv.n_splits = int64_t(im.splits.size());
+    dv.n_slots = im.n_slots;
+}
+void csr_usable(petal_ctx& c, const petal_csr& x) {
+    if (x.owner != &c) invalid_input("the sparse matrix was created with another ctx");
+    if (sharded(c)) invalid_input("sparse input on a sharded ctx is not supported in this version");
+}
+// the matrix as a dense row-major host array in its own type (duplicates add up in position order)
+std::vector<char> csr_densify(const petal_csr& x) {
+    std::vector<char> dense(dtype_size(x.dtype) * size_t(x.rows) * size_t(x.cols), 0);
+    const petal_csr::Image& im = x.host[0];
+    auto fill = [&](auto* out, const auto* val) {
+        for (int64_t r = 0; r < x.rows; ++r)
+            for (int64_t t = im.ptr[r]; t < im.ptr[r + 1]; ++t) out[r * x.cols + im.idx[t]] += val[t];
+    };
+    if (x.dtype == F64) fill(reinterpret_cast<double*>(dense.data()), reinterpret_cast<const double*>(im.val.data()));
+    else fill(reinterpret_cast<float*>(dense.data()), reinterpret_cast<const float*>(im.val.data()));
+    return dense;
+}
+petal_matrix csr_dense_view(const petal_csr& x, std::vector<char>& dense) {
+    petal_matrix m{};
+    m.data = dense.data(); m.rows = x.rows; m.cols = x.cols; m.row_stride = x.cols; m.col_stride = 1; m.dtype = x.dtype; m.space = PETAL_HOST;
+    return m;
+}
+// host doubles -> a device block of `count` elements in dt, the first `used` from h, zeros behind
+DBuf csr_stage(petal_ctx& c, int dt, const double* h, int64_t used, int64_t count) {
+    std::vector<char> tmp(dtype_size(dt) * size_t(count), 0);
+    for (int64_t i = 0; i < used; ++i) put_elem(tmp.data(), dt, i, h[i]);
+    DBuf b(c.dev, tmp.size());
+    dev_h2d(c.dev, b.p, tmp.data(), b.bytes);
+    return b;
+}
+}  // namespace
+
+petal_csr* csr_create(petal_ctx& c, int64_t rows, int64_t cols, int64_t nnz, const int64_t* indptr, const int32_t* indices, const void* values,
+                      int32_t dtype) {
+    if (dtype != PETAL_F32 && dtype != PETAL_F64) invalid_input("sparse input: unsupported dtype");
+    if (rows < 0 || cols < 0 || nnz < 0) invalid_input("sparse input: negative shape");
+    if (rows >= (int64_t(1) << 31) || cols >= (int64_t(1) << 31)) invalid_input("sparse input: too many rows/columns (32-bit indices)");
+    if (!indptr) invalid_input("indptr must not be null");
+    if (nnz > 0 && (!indices || !values)) invalid_input("indices and values must not be null");
+    if (indptr[0] != 0) invalid_input("indptr[0] should be 0 (it is " + std::to_string(indptr[0]) + ")");
+    for (int64_t r = 1; r <= rows; ++r)
+        if (indptr[r] < indptr[r - 1])
+            invalid_input("indptr should not decrease: indptr[" + std::to_string(r) + "] = " + std::to_string(indptr[r]) + " is below indptr[" +
+                          std::to_string(r - 1) + "] = " + std::to_string(indptr[r - 1]));
+    if (indptr[rows] != nnz)
+        invalid_input("indptr[" + std::to_string(rows) + "] should be the number of nonzeros " + std::to_string(nnz) + " (it is " +
+                      std::to_string(indptr[rows]) + ")");
+    for (int64_t t = 0; t < nnz; ++t)
+        if (indices[t] < 0 || indices[t] >= cols)
+            invalid_input("indices[" + std::to_string(t) + "] = " + std::to_string(indices[t]) + " is outside [0, " + std::to_string(cols) + ")");
+    std::unique_ptr<petal_csr> x(new petal_csr());
+    x->owner = &c; x->rows = rows; x->cols = cols; x->nnz = nnz; x->dtype = dtype;
+    const size_t esz = dtype_size(dtype);
+    petal_csr::Image &a = x->host[0], &t = x->host[1];
+    a.ptr.assign(indptr, indptr + rows + 1);
+    a.idx.assign(indices, indices + nnz);
+    a.val.assign(static_cast<const char*>(values), static_cast<const char*>(values) + esz * size_t(nnz));
+    // the transposed image by a STABLE counting sort over the column indices: the rows stay ascending inside every column (and
+    // duplicates in their order), so the summation order of X^T . Z is a function of the data alone
+    t.ptr.assign(size_t(cols) + 1, 0);
+    for (int64_t q = 0; q < nnz; ++q) ++t.ptr[size_t(indices[q]) + 1];
+    for (int64_t j = 0; j < cols; ++j) t.ptr[j + 1] += t.ptr[j];
+    t.idx.resize(size_t(nnz));
+    t.val.resize(esz * size_t(nnz));
+    {
+        std::vector<int64_t> next(t.ptr.begin(), t.ptr.end() - 1);
+        for (int64_t r = 0; r < rows; ++r)
+            for (int64_t q = indptr[r]; q < indptr[r + 1]; ++q) {
+                const int64_t pos = next[indices[q]]++;
+                t.idx[pos] = int32_t(r);
+                std::memcpy(&t.val[esz * size_t(pos)], static_cast<const char*>(values) + esz * size_t(q), esz);
+            }
+    }
+    csr_build_items(a, rows);
+    csr_build_items(t, cols);
+    x->resident = op_csr_supported(c.dev);
+    if (x->resident) {
+        try {
+            csr_upload(c, *x, 0);
+            csr_upload(c, *x, 1);
+        } catch (...) {
+            csr_destroy(x.release());
+            throw;
+        }
+        for (petal_csr::Image& im : x->host) { const int64_t slots = im.n_slots; im = petal_csr::Image(); im.n_slots = slots; }   // the host copies are not kept
+    }
+    return x.release();
+}
+
+void csr_destroy(petal_csr* x) {
+    if (!x) return;
+    for (auto& img : x->blocks)
+        for (void* b : img)
+            if (b) dev_free(x->owner->dev, b);
+    delete x;
+}
+
+void csr_image(const petal_csr& x, int transposed, int64_t* indptr, int32_t* indices, void* values, int64_t* items) {
+    if (x.resident) invalid_input("the images of a resident sparse matrix are not kept on the host");
+    const petal_csr::Image& im = x.host[transposed ? 1 : 0];
+    if (indptr) std::copy(im.ptr.begin(), im.ptr.end(), indptr);
+    if (indices) std::copy(im.idx.begin(), im.idx.end(), indices);
+    if (values && !im.val.empty()) std::memcpy(values, im.val.data(), im.val.size());
+    if (items)
+        for (size_t i = 0; i < im.items.size(); ++i) {
+            items[3 * i] = im.items[i].row; items[3 * i + 1] = im.items[i].first; items[3 * i + 2] = im.items[i].first + im.items[i].count;
+        }
+}
+
+namespace {
+// One fit on the resident images: sizes, buffers and the named stages of the range finder and of randomized_svd (pca.rs:668-718).
+// Every iterate -- n x LP on the tall side, d x LP on the feature side -- is a dense block in the data's type, padded to 16 columns;
+// only the two products with X are sparse, everything behind them is the dense fit's own ops.
+struct CsrRun {
+    petal_ctx& c;
+    const petal_csr& x;
+    const int dt;
+    const int64_t n, d, dp, k, L, LP, kp;
+    const bool centering;
+    const double tol;      // dependence test of the fp64 Gram matrices (the dense fit's tol_tall)
+    DBuf mu64, s, Pd, G, T, A, A1, B, B1, Btd, S, Uh, lam, comp, U, flip;
+    CsrRun(petal_ctx& c_, const petal_csr& x_, int64_t k_, int64_t L_, bool centering_)
+        : c(c_), x(x_), dt(x_.dtype), n(x_.rows), d(x_.cols), dp(round_up(x_.cols, 16)), k(k_), L(L_), LP(round_up(L_, 16)),
+          kp(std::min(LP, round_up(std::max<int64_t>(k_, 1), 16))), centering(centering_), tol(dt == F32 ? 1e-12 : 1e-13) {
+        const size_t esz = dtype_size(dt);
+        s = DBuf(c.dev, sizeof(double) * LP);
+        if (dt == F32) Pd = DBuf(c.dev, sizeof(double) * d * LP);
+        G = DBuf(c.dev, sizeof(double) * LP * LP);
+        T = DBuf(c.dev, sizeof(double) * LP * LP);
+        A = DBuf(c.dev, esz * size_t(n) * LP);
+        A1 = DBuf(c.dev, esz * size_t(n) * LP);
+        B = DBuf(c.dev, esz * size_t(d) * LP);
+        B1 = DBuf(c.dev, esz * size_t(d) * LP);
+        Btd = DBuf(c.dev, sizeof(double) * dp * LP);
+        S = DBuf(c.dev, sizeof(double) * LP * LP);
+        Uh = DBuf(c.dev, sizeof(double) * LP * LP);
+        lam = DBuf(c.dev, sizeof(double) * LP);
+        comp = DBuf(c.dev, std::max<size_t>(esz * size_t(k) * d, 8));
+        U = DBuf(c.dev, esz * size_t(n) * kp);
+        flip = DBuf(c.dev, sizeof(double) * 3 * kp);
+    }
+    // column sums and sums of squares in one pass over the transposed image -> the means (host and device), the total variance, and
+    // the verdict on non-finite values (every one of them reaches a column's sums)
+    void column_stats(std::vector<double>& hmu, double& tv) {
+        DBuf st(c.dev, sizeof(double) * 2 * d);
+        dev_set_tag(c.dev, TAG_STREAM);
+        op_csr_colstats(c.dev, dt, x.dev[1], st.f64());
+        dev_set_tag(c.dev, TAG_NONE);
+        std::vector<double> h(static_cast<size_t>(2 * d));
+        dev_d2h(c.dev, h.data(), st.p, st.bytes);
+        dev_sync(c.dev);
+        hmu.assign(size_t(dp), 0.0);
+        tv = 0.0;
+        bool finite = true;
+        for (int64_t j = 0; j < d; ++j) {
+            finite = finite && std::isfinite(h[2 * j]) && std::isfinite(h[2 * j + 1]);
+            if (centering) hmu[j] = h[2 * j] / double(n);
+            tv += centering ? std::max(0.0, h[2 * j + 1] - double(n) * hmu[j] * hmu[j]) : h[2 * j + 1];   // sum x^2 - n mu^2 per column, as the dense fp32 fit
+        }
+        if (!finite) linalg_error("did not converge");
+        mu64 = DBuf(c.dev, sizeof(double) * dp);
+        dev_h2d(c.dev, mu64.p, hmu.data(), mu64.bytes);
+    }
+    // Zout (n x LP) = Xc . P  (P: d x LP, pca.rs:707 / 714)
+    void product_xp(const void* P, void* Zout) {
+        if (centering) {   // s = mu^T P, from the very values the kernel multiplies
+            const double* P64 = static_cast<const double*>(P);
+            if (dt == F32) { op_cvt_to_f64(c.dev, dt, Pd.f64(), P, d * LP); P64 = Pd.f64(); }
+            op_dgemm(c.dev, true, false, 1, LP, d, 1.0, mu64.f64(), 1, P64, LP, 0.0, s.f64(), LP);
+        }
+        dev_set_tag(c.dev, TAG_XP);
+        op_csr_gemm(c.dev, dt, x.dev[0], P, LP, LP, nullptr, centering ? s.f64() : nullptr, Zout, LP);
+        dev_set_tag(c.dev, TAG_NONE);
+    }
+    // Yout (d x LP) = Xc^T . Z  (Z: n x LP, pca.rs:711 / 681)
+    void product_xtz(const void* Z, void* Yout) {
+        if (centering) op_colsum(c.dev, dt, Z, n, LP, LP, s.f64());   // s = 1^T Z
+        dev_set_tag(c.dev, TAG_ATB);
+        op_csr_gemm(c.dev, dt, x.dev[1], Z, LP, LP, centering ? mu64.f64() : nullptr, centering ? s.f64() : nullptr, Yout, LP);
+        dev_set_tag(c.dev, TAG_NONE);
+    }
+    // out = M R^-1 with M^T M = R^T R: one Cholesky-QR step on an fp64 Gram matrix of the stored iterate (stands for the pivoted-LU
+    // re-basings of pca.rs:709-713: the next product only needs SOME well-conditioned basis of the same range).  The product M R^-1 is
+    // op_tall_times_small -- fp64 throughout, not op_gemm_xp, whose kernel and rounding follow the ctx's GEMM mode.  A dependent column
+    // (pivot below tol of its diagonal) is dropped -- zeroed -- as on the dense fit's Cholesky-QR2 path: rank-deficient and all-zero
+    // data are legal input, so nothing is raised.
+    void rebase(const void* M, int64_t rows, void* out) {
+        op_gemm_atb(c.dev, dt, M, LP, LP, nullptr, M, LP, LP, nullptr, rows, G.f64(), LP, /*precise=*/true);
+        op_chol_inv(c.dev, G.f64(), L, LP, T.f64(), LP, tol, nullptr, LP);
+        op_tall_times_small(c.dev, dt, M, rows, LP, LP, T.f64(), LP, LP, out, LP);
+    }
+    // the range finder: returns Q (n x LP, orthonormal columns by Cholesky-QR2)
+    const void* range_finder(const void* omega, int64_t l_req, int64_t n_iter) {
+        {   // Omega: the first L columns of the d x l_req draw, padded to LP
+            std::vector<char> h(dtype_size(dt) * size_t(d) * LP, 0);
+            for (int64_t i = 0; i < d; ++i)
+                std::memcpy(&h[dtype_size(dt) * size_t(i) * LP], static_cast<const char*>(omega) + dtype_size(dt) * size_t(i) * l_req, dtype_size(dt) * size_t(L));
+            dev_h2d(c.dev, B.p, h.data(), B.bytes);
+        }
+        product_xp(B.p, A.p);
+        for (int64_t it = 0; it < n_iter; ++it) {
+            rebase(A.p, n, A1.p);
+            product_xtz(A1.p, B.p);
+            rebase(B.p, d, B1.p);
+            product_xp(B1.p, A.p);
+        }
+        rebase(A.p, n, A1.p);
+        rebase(A1.p, n, A.p);
+        return A.p;
+    }
+    // B^T = Xc^T Q, the economy SVD of B through the eigen-decomposition of B B^T in fp64, the components, U = Q Uh and svd_flip's scan
+    void small_stage(const void* Q) {
+        product_xtz(Q, B.p);
+        dev_memset(c.dev, Btd.p, 0, Btd.bytes);
+        op_cvt_to_f64(c.dev, dt, Btd.f64(), B.p, d * LP);
+        op_dgemm(c.dev, true, false, LP, LP, dp, 1.0, Btd.f64(), LP, Btd.f64(), LP, 0.0, S.f64(), LP);
+        dev_memset(c.dev, lam.p, 0, lam.bytes);
+        op_eigh(c.dev, S.f64(), L, LP, Uh.f64(), LP, lam.f64(), dt == F32 ? 1e-8 : 1e-15, false, LP);
+        op_components_out(c.dev, dt, Btd.f64(), LP, Uh.f64(), LP, lam.f64(), dt == F32 ? 1e-7 : 1e-12, d, L, k, comp.p);
+        dev_set_tag(c.dev, TAG_STREAM);
+        op_tall_times_small(c.dev, dt, Q, n, LP, LP, Uh.f64(), kp, LP, U.p, kp);
+        dev_set_tag(c.dev, TAG_NONE);
+        op_col_absmax(c.dev, dt, U.p, n, kp, kp, 0, flip.f64(), flip.f64() + kp, flip.f64() + 2 * kp);
+    }
+    void write_out(const PcaOutputs& out, const std::vector<double>& hmu, double tv) {
+        std::vector<double> hlam(static_cast<size_t>(LP)), hflip(static_cast<size_t>(3 * kp));
+        std::vector<char> hcomp(dtype_size(dt) * size_t(k) * d);
+        dev_d2h(c.dev, hlam.data(), lam.p, lam.bytes);
+        dev_d2h(c.dev, hflip.data(), flip.p, flip.bytes);
+        if (!hcomp.empty()) dev_d2h(c.dev, hcomp.data(), comp.p, hcomp.size());
+        dev_sync(c.dev);
+        std::vector<double> hs(size_t(std::max<int64_t>(k, 1)), 0.0);
+        for (int64_t j = 0; j < k; ++j) {
+            if (!std::isfinite(hlam[j])) linalg_error("did not converge");
+            hs[j] = std::sqrt(std::max(hlam[j], 0.0));
+        }
+        const std::vector<double> sg = signs_from_triple(hflip, kp);
+        write_pca_outputs(c, out, dt, k, d, hcomp.data(), sg.data(), hs.data(), hmu.data(), tv, U.p, n, kp);
+    }
+};
+}  // namespace
+
+void rpca_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, int64_t n_oversample, int64_t n_iter, bool centering, const void* omega,
+                  void* components, void* means, void* singular, void* total_variance, const petal_matrix* y_out, int64_t* kernel_path) {
+    csr_usable(c, x);
+    if (kernel_path) *kernel_path = 0;
+    if (!x.resident) {
+        std::vector<char> dense = csr_densify(x);
+        rpca_fit(c, csr_dense_view(x, dense), k, n_oversample, n_iter, centering, omega, components, means, singular, total_variance, y_out);
+        return;
+    }
+    const Timer timer;
+    dev_reset_timing(c.dev);
+    c.stats = petal_stats{};
+    if (k < 0 || n_oversample < 0 || n_iter < 0) invalid_input("negative parameter");
+    const int dt = x.dtype;
+    const int64_t n = x.rows, d = x.cols, l_req = k + n_oversample;
+    if (n < k || d < k) invalid_input("every dimension should be at least " + std::to_string(k));  // pca.rs:513-518
+    if (centering && n == 0) {   // mean_axis -> None (pca.rs:521-525): Ok, model untouched
+        if (y_out && y_out->rows != 0) invalid_input("output has the wrong shape");
+        return;
+    }
+    const int64_t L = std::min(l_req, std::min(n, d));
+    if (L > 0 && omega == nullptr) invalid_input("omega is required");
+    if (d == 0 || L == 0) {   // nothing to decompose: k == 0 here
+        if (total_variance) put_elem(total_variance, dt, 0, 0.0);
+        if (y_out) emit(c, dt, nullptr, n, 0, 0, *y_out);
+        return;
+    }
+    CsrRun run(c, x, k, L, centering);
+    std::vector<double> hmu;
+    double tv = 0.0;
+    run.column_stats(hmu, tv);
+    run.small_stage(run.range_finder(omega, l_req, n_iter));
+    run.write_out({components, means, singular, total_variance, y_out}, hmu, tv);
+    if (kernel_path) *kernel_path = 1;
+    finish_stats(c, timer);
+}
+
+void transform_csr(petal_ctx& c, const petal_csr& x, const void* components, const void* means, int64_t k, int64_t d, bool centering,
+                   const petal_matrix& y_out, int64_t* kernel_path) {
+    csr_usable(c, x);
+    if (kernel_path) *kernel_path = 0;
+    if (x.cols != d) invalid_input("# of columns should be " + std::to_string(d));  // pca.rs:736-741
+    if (k < 0) invalid_input("negative parameter");
+    const int dt = x.dtype;
+    if (x.rows == 0 || k == 0) { emit(c, dt, nullptr, x.rows, k, 0, y_out); return; }
+    if (!x.resident) {
+        std::vector<char> dense = csr_densify(x);
+        transform(c, csr_dense_view(x, dense), components, means, k, d, centering, y_out);
+        return;
+    }
+    const int64_t kp = round_up(k, 16);
+    const std::vector<double> hP = components_operand(components, dt, k, d, d, kp, true);   // P = V^T as d x kp
+    std::vector<double> hs(static_cast<size_t>(kp), 0.0);                                   // s = mu^T P
+    if (centering)
+        for (int64_t i = 0; i < d; ++i) {
+            const double m = get_elem(means, dt, i);
+            for (int64_t j = 0; j < k; ++j) hs[j] += m * hP[size_t(i) * kp + j];
+        }
+    DBuf P = csr_stage(c, dt, hP.data(), d * kp, d * kp), s = csr_stage(c, F64, hs.data(), kp, kp);
+    DBuf Y(c.dev, dtype_size(dt) * size_t(x.rows) * kp);
+    op_csr_gemm(c.dev, dt, x.dev[0], P.p, kp, kp, nullptr, centering ? s.f64() : nullptr, Y.p, kp);
+    emit(c, dt, Y.p, x.rows, k, kp, y_out);
+    dev_sync(c.dev);
+    if (kernel_path) *kernel_path = 1;
+}
+
+void csr_gemm(petal_ctx& c, const petal_csr& x, bool transposed, const double* P, int64_t N, const double* a, const double* s, double* out) {
+    csr_usable(c, x);
+    if (N < 0) invalid_input("negative parameter");
+    const int dt = x.dtype;
+    const int64_t rows = transposed ? x.cols : x.rows, inner = transposed ? x.rows : x.cols;
+    if (rows == 0 || N == 0) return;
+    if (!P && inner > 0) invalid_input("P must not be null");
+    if (!out) invalid_input("out must not be null");
+    const auto rounded = [&](double v) { return dt == F32 ? double(float(v)) : v; };
+    if (!x.resident) {   // the plain host loop of a layer without the op: same order, same roundings
+        const petal_csr::Image& im = x.host[transposed ? 1 : 0];
+        std::vector<double> acc(static_cast<size_t>(N), 0.0);
+        for (int64_t r = 0; r < rows; ++r) {
+            std::fill(acc.begin(), acc.end(), 0.0);
+            for (int64_t t = im.ptr[r]; t < im.ptr[r + 1]; ++t) {
+                const double v = get_elem(im.val.data(), dt, t);
+                for (int64_t j = 0; j < N; ++j) acc[j] += v * rounded(P[int64_t(im.idx[t]) * N + j]);
+            }
+            for (int64_t j = 0; j < N; ++j) out[r * N + j] = rounded(s ? acc[j] - (a ? a[r] : 1.0) * s[j] : acc[j]);
+        }
+        return;
+    }
+    const int64_t NP = round_up(N, 16);
+    std::vector<double> hP(size_t(std::max<int64_t>(inner, 1)) * NP, 0.0);
+    for (int64_t i = 0; i < inner; ++i) std::copy(P + i * N, P + (i + 1) * N, hP.begin() + i * NP);
+    DBuf dP = csr_stage(c, dt, hP.data(), int64_t(hP.size()), int64_t(hP.size())), ds, da;
+    if (s) ds = csr_stage(c, F64, s, N, NP);
+    if (s && a) da = csr_stage(c, F64, a, rows, rows);
+    DBuf dO(c.dev, dtype_size(dt) * size_t(rows) * NP);
+    op_csr_gemm(c.dev, dt, x.dev[transposed ? 1 : 0], dP.p, NP, NP, (s && a) ? da.f64() : nullptr, s ? ds.f64() : nullptr, dO.p, NP);
+    std::vector<char> hO(dO.bytes);
+    dev_d2h(c.dev, hO.data(), dO.p, dO.bytes);
+    dev_sync(c.dev);
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t j = 0; j < N; ++j) out[r * N + j] = get_elem(hO.data(), dt, r * NP + j);
 }
 
 }  // namespace petal

@@ -7,6 +7,7 @@
 #include "ctx.h"
 #include "../../include/petal_hip_score.h"
 #include "../../include/petal_hip_segments.h"
+#include "../../include/petal_hip_sparse.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -199,6 +200,65 @@ int petal_score_rows(petal_ctx* ctx, const petal_matrix* x, const void* componen
         need(x, "x");
         need(out, "out");
         score_rows(*ctx, *x, components, means, k, d, centering != 0, weights, *out, y_out);
+    });
+}
+
+// ---- include/petal_hip_sparse.h: RandomizedPca on a resident CSR matrix ------------------------------------------------------------
+int petal_csr_create(petal_ctx* ctx, int64_t rows, int64_t cols, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                     const void* values, int32_t dtype, petal_csr** out) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(out, "out");
+        *out = csr_create(*ctx, rows, cols, nnz, indptr, indices, values, dtype);
+    });
+}
+void petal_csr_destroy(petal_csr* x) {
+    if (!x) return;
+    try {
+        DeviceScope scope(x->owner->dev);
+        csr_destroy(x);
+    } catch (...) {}
+}
+int petal_csr_info(const petal_csr* x, int64_t* out8) {
+    if (!x || !out8) return PETAL_INVALID_INPUT;
+    const int64_t items[2] = {x->resident ? x->dev[0].n_items : int64_t(x->host[0].items.size()),
+                              x->resident ? x->dev[1].n_items : int64_t(x->host[1].items.size())};
+    const int64_t v[8] = {x->rows, x->cols, x->nnz, x->dtype, x->resident ? 1 : 0, items[0], items[1], PETAL_CSR_ITEM_NNZ};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    return PETAL_OK;
+}
+int petal_csr_image(const petal_csr* x, int transposed, int64_t* indptr, int32_t* indices, void* values, int64_t* items) {
+    if (!x) return PETAL_INVALID_INPUT;
+    return guarded(x->owner, [&] { csr_image(*x, transposed, indptr, indices, values, items); });
+}
+int petal_rpca_fit_csr(petal_ctx* ctx, const petal_csr* x, int64_t k, int64_t n_oversample, int64_t n_iter, int centering,
+                       const void* omega, void* components, void* means, void* singular, void* total_variance,
+                       const petal_matrix* y_out, int64_t* kernel_path) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        rpca_fit_csr(*ctx, *x, k, n_oversample, n_iter, centering != 0, omega, components, means, singular, total_variance, y_out, kernel_path);
+    });
+}
+int petal_transform_csr(petal_ctx* ctx, const petal_csr* x, const void* components, const void* means, int64_t k, int64_t d,
+                        int centering, const petal_matrix* y_out, int64_t* kernel_path) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(y_out, "y_out");
+        transform_csr(*ctx, *x, components, means, k, d, centering != 0, *y_out, kernel_path);
+    });
+}
+int petal_ctx_workspace_in_use(petal_ctx* ctx, int64_t* blocks, int64_t* bytes) {
+    return guarded(ctx, [&] {
+        need(blocks, "blocks");
+        need(bytes, "bytes");
+        if (!dev_live(ctx->dev, blocks, bytes)) { *blocks = -1; *bytes = -1; }
+    });
+}
+int petal_csr_gemm(petal_ctx* ctx, const petal_csr* x, int transposed, const double* P, int64_t N, const double* a, const double* s,
+                   double* out) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        csr_gemm(*ctx, *x, transposed != 0, P, N, a, s, out);
     });
 }
 

@@ -27,6 +27,25 @@ struct petal_ctx {
     int64_t topk_seed_d = 0, topk_seed_dp = 0, topk_seed_p = 0;
 };
 
+// include/petal_hip_sparse.h: a sparse matrix and its transposed image with their work items, in device memory (resident) or, where the
+// device-op layer has no sparse product, on the host
+struct petal_csr {
+    petal_ctx* owner = nullptr;
+    int64_t rows = 0, cols = 0, nnz = 0;
+    int dtype = 0;
+    bool resident = false;
+    struct Image {                       // [0] the matrix, [1] its transpose
+        std::vector<int64_t> ptr;        // image rows + 1 (host only)
+        std::vector<int32_t> idx;
+        std::vector<char> val;
+        std::vector<petal::CsrItem> items;
+        std::vector<petal::CsrSplit> splits;
+        int64_t n_slots = 0;
+    } host[2];
+    petal::CsrImage dev[2];              // resident: views of the four device blocks of each image
+    void* blocks[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
+};
+
 namespace petal {
 
 struct Error : std::runtime_error {
@@ -104,6 +123,16 @@ void transform_segments(petal_ctx& c, const petal_matrix& x, const int64_t* offs
                         const void* means, int64_t k, int64_t d, bool centering, const petal_matrix& y_out);
 void inverse_transform_segments(petal_ctx& c, const petal_matrix& y, const int64_t* offsets, int64_t n_segments, const void* components,
                                 const void* means, int64_t k, int64_t d, bool centering, const petal_matrix& x_out);
+// include/petal_hip_sparse.h: RandomizedPca on a resident CSR matrix
+petal_csr* csr_create(petal_ctx& c, int64_t rows, int64_t cols, int64_t nnz, const int64_t* indptr, const int32_t* indices, const void* values,
+                      int32_t dtype);
+void csr_destroy(petal_csr* x);
+void csr_image(const petal_csr& x, int transposed, int64_t* indptr, int32_t* indices, void* values, int64_t* items);
+void rpca_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, int64_t n_oversample, int64_t n_iter, bool centering, const void* omega,
+                  void* components, void* means, void* singular, void* total_variance, const petal_matrix* y_out, int64_t* kernel_path);
+void transform_csr(petal_ctx& c, const petal_csr& x, const void* components, const void* means, int64_t k, int64_t d, bool centering,
+                   const petal_matrix& y_out, int64_t* kernel_path);
+void csr_gemm(petal_ctx& c, const petal_csr& x, bool transposed, const double* P, int64_t N, const double* a, const double* s, double* out);
 void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, double tol, int64_t max_iter, int mode,
                  const void* w_init, void* components, void* means, int64_t* n_iter, const petal_matrix* y_out);
 void ica_par(petal_ctx& c, const petal_matrix& x1, double tol, int64_t max_iter, int mode, const void* w_init,

@@ -18,6 +18,8 @@
 //     k_trieig_r (symmetric eigenproblem up to order 138), k_jacobi_* (fallbacks and one-sided SVD), k_symdecorr / k_ica_tail
 //     (symmetric decorrelation: scaled Newton-Schulz polar factor in LDS)
 //   segmented Pca: k_pca_segments (one workgroup per row segment: means, fp64 Gram, wg_jacobi_fast, svd_flip, outputs), k_seg_project
+//   sparse data: k_spmm (CSR x tall-skinny dense, one wave per work item of <= 256 nonzeros, gathered rows of P in 16-byte loads, fp64
+//     accumulators, implicit centring in the epilogue), k_spmm_combine (split rows, in item order), k_csr_rowstats
 //   *_simple     generic (any shape, f32 / f64, fp64 accumulate) kernels for small / unaligned / f64 inputs
 //
 // wave = 64 lanes everywhere.  MFMA 16x16x4 f32 fragment maps (cdna_hip_programming.md section 3):
@@ -273,6 +275,13 @@ void dev_free(Dev* d, void* p) {
     // stream-ordered reuse: every consumer of this block was enqueued on d->stream before this call
     d->free_list.emplace(it->second, p);
     d->live.erase(it);
+}
+// the blocks handed out and not yet returned (include/petal_hip_sparse.h: petal_ctx_workspace_in_use, a test aid)
+bool dev_live(Dev* d, int64_t* blocks, int64_t* bytes) {
+    *blocks = int64_t(d->live.size());
+    *bytes = 0;
+    for (auto& kv : d->live) *bytes += int64_t(kv.second);
+    return true;
 }
 // Fork / join of a side stream.  Between dev_fork() and dev_fork_end() every launch and copy goes to the side stream, which
 // starts behind everything the main stream holds at the fork; after dev_fork_end() work goes to the main stream again and the
@@ -580,4 +589,5 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #include "kernels/k_gram.inc"   // the split-product Gram kernel of the FastICA whitening (k_gram5) and its launcher
 #include "kernels/host_pow3_eigh.inc"   // host-side launchers: the fused pass, Cholesky / eigen-solver / remaining small ops
 #include "kernels/k_pca_segments.inc"   // segmented Pca: one workgroup per row segment (k_pca_segments), k_seg_project, their launchers
+#include "kernels/k_spmm.inc"   // sparse (CSR) x dense products of RandomizedPca on sparse data (k_spmm, k_spmm_combine, k_csr_rowstats), their launchers
 }  // namespace petal

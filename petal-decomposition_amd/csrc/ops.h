@@ -33,6 +33,7 @@ void  dev_destroy(Dev*);
 void* dev_stream(Dev*);
 void* dev_alloc(Dev*, size_t bytes);      // cached; never returns nullptr (throws std::runtime_error)
 void  dev_free(Dev*, void*);
+bool  dev_live(Dev*, int64_t* blocks, int64_t* bytes);   // the blocks handed out and not yet returned; false: this layer keeps no count (algo.cpp's weak default)
 void  dev_memset(Dev*, void* p, int v, size_t bytes);
 void  dev_h2d(Dev*, void* dst, const void* src, size_t bytes);
 void  dev_h2d_async(Dev*, void* dst, const void* src, size_t bytes);  // src is consumed before the call returns; no host wait
@@ -156,6 +157,38 @@ bool op_transform_segments(Dev*, int dtype, const void* X, int64_t ldx, const in
                            const void* means, int64_t k, int64_t d, void* Y);
 bool op_inverse_transform_segments(Dev*, int dtype, const void* Y, int64_t ldy, const int64_t* offsets, int64_t nseg, const void* comp,
                                    const void* means, int64_t k, int64_t d, void* X);
+// Sparse products (include/petal_hip_sparse.h; an extension beyond the crate).  One image of a CSR matrix as algo.cpp's csr_create lays
+// it out in DEVICE memory: positions [first, first + count) of idx / val belong to image row `row`; a whole row is ONE item with
+// slot < 0 (an empty row too: count == 0), a row of more than PETAL_CSR_ITEM_NNZ nonzeros is several consecutive items with consecutive
+// slots >= 0, and `splits` names each such row with its first slot and its number of items.
+struct CsrItem { int64_t first; int32_t row, count, slot, pad; };
+struct CsrSplit { int32_t row, first_slot, count, pad; };
+struct CsrImage {
+    int64_t rows = 0, nnz = 0;             // rows of THIS image (the columns of the other one)
+    const int32_t* idx = nullptr;          // nnz: the row of the dense operand each nonzero multiplies
+    const void* val = nullptr;             // nnz values in the handle's dtype
+    const CsrItem* items = nullptr;
+    int64_t n_items = 0;
+    const CsrSplit* splits = nullptr;
+    int64_t n_splits = 0, n_slots = 0;
+};
+// Does this layer have the sparse product?  algo.cpp's weak defaults say no (and the two ops below return false, nothing done): the
+// handle then keeps its host arrays and the entries densify.
+bool op_csr_supported(Dev*);
+// out[r, :] (img.rows x N in dtype, ldo) = sum over the nonzeros t of image row r, in position order, of val[t] * P[idx[t], :]
+// (P: dtype, ldp), minus a[r] * s[:] when s != nullptr (a, s: DEVICE fp64; a == nullptr: a[r] = 1) -- the implicit centring.  N, ldp,
+// ldo: multiples of 16 (the iterates' padding), P and out 16-byte aligned.  Every product and sum in fp64, no atomics: a split row's
+// partial sums are added in item order by a second launch.
+bool op_csr_gemm(Dev*, int dtype, const CsrImage& img, const void* P, int64_t N, int64_t ldp, const double* a, const double* s,
+                 void* out, int64_t ldo);
+// stats[r] = { sum_t val[t], sum_t val[t]^2 } over the nonzeros of image row r (fp64, DEVICE, 2 img.rows doubles): on the transposed
+// image the column sums and column sums of squares of the matrix.
+bool op_csr_colstats(Dev*, int dtype, const CsrImage& img, double* stats);
+// out (rows x N in dtype, ldo) = M (rows x K in dtype, ldm) . S (K x N fp64, lds): the dense products of the sparse fit (re-basing
+// M R^-1, U = Q Uh) with every product and sum in fp64 -- ONE form, independent of the ctx's GEMM mode and options (op_gemm_xp would
+// send float32 data through the split-product or the fp32-MFMA kernel as the mode says).
+bool op_tall_times_small(Dev*, int dtype, const void* M, int64_t rows, int64_t K, int64_t ldm, const double* S, int64_t N, int64_t lds,
+                         void* out, int64_t ldo);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.

@@ -5,11 +5,12 @@
 mod ffi;
 mod ffi_score;
 mod ffi_segments;
+mod ffi_sparse;
 mod ica;
 mod pca;
 
 pub use ica::{Contrast, FastIca, FastIcaBuilder};
-pub use pca::{Pca, PcaBuilder, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
+pub use pca::{CsrMatrix, Pca, PcaBuilder, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
 
 use ndarray::{ArrayBase, Data, Ix2};
 use std::ffi::CStr;

@@ -1,5 +1,5 @@
 //! `Pca` (`src/pca.rs:41-231` of the reference) and `RandomizedPca` (`src/pca.rs:317-663`) over the C ABI.
-use crate::{ffi, ffi_score, ffi_segments, view, with_ctx, DecompositionError, HipScalar};
+use crate::{ffi, ffi_score, ffi_segments, ffi_sparse, view, with_ctx, DecompositionError, HipScalar};
 use ndarray::{Array1, Array2, Array3, ArrayBase, Data, Ix2};
 use rand::Rng;
 use rand_distr::StandardNormal;
@@ -174,6 +174,63 @@ impl<A: HipScalar, R: Rng> RandomizedPca<A, R> {
     /// Log-likelihood of each row under the probabilistic-PCA model (scikit-learn's `score_samples`).
     pub fn score_samples<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array1<A>, DecompositionError> {
         score_samples(input, &self.components, &self.means, self.centering, &self.explained_variance(), self.noise_variance())
+    }
+
+    // ---- sparse CSR input, never densified: an extension beyond the crate (include/petal_hip_sparse.h) ----
+    pub fn fit_csr(&mut self, input: &CsrMatrix<A>) -> Result<(), DecompositionError> {
+        self.inner_fit_csr(input, None)
+    }
+    pub fn fit_transform_csr(&mut self, input: &CsrMatrix<A>) -> Result<Array2<A>, DecompositionError> {
+        let mut y = Array2::<A>::default((input.nrows(), self.n_components()));
+        self.inner_fit_csr(input, Some(&mut y))?;
+        Ok(y)
+    }
+    pub fn transform_csr(&self, input: &CsrMatrix<A>) -> Result<Array2<A>, DecompositionError> {
+        let (k, d) = (self.n_components(), self.means.len());
+        if input.ncols() != d {
+            return Err(DecompositionError::InvalidInput(format!("# of columns should be {d}")));
+        }
+        let y = Array2::<A>::default((input.nrows(), k));
+        let yv = view(&y);   // (the library writes through the view's pointer, as transform() above)
+        with_ctx(
+            |ctx| unsafe {
+                ffi_sparse::petal_transform_csr(ctx, input.raw, self.components.as_ptr() as *const c_void, self.means.as_ptr() as *const c_void,
+                    k as i64, d as i64, self.centering as i32, &yv, std::ptr::null_mut())
+            },
+            || (),
+        )?;
+        Ok(y)
+    }
+    fn inner_fit_csr(&mut self, input: &CsrMatrix<A>, y: Option<&mut Array2<A>>) -> Result<(), DecompositionError> {
+        let (k, d) = (self.n_components(), input.ncols());
+        if input.nrows() < k || d < k {
+            return Err(DecompositionError::InvalidInput(format!("every dimension should be at least {k}")));
+        }
+        if input.nrows() == 0 && self.centering {
+            return Ok(());
+        }
+        let l = k + N_OVERSAMPLE;
+        let omega = Array2::<A>::from_shape_fn((d, l), |_| A::from_f64(self.rng.sample::<f64, _>(StandardNormal)));
+        let mut comps = Array2::<A>::default((k, d));
+        let mut means = Array1::<A>::default(d);
+        let mut sing = Array1::<A>::default(k);
+        let mut tv = A::default();
+        let yv = y.as_ref().map(|y| view(&**y));
+        with_ctx(
+            |ctx| unsafe {
+                ffi_sparse::petal_rpca_fit_csr(ctx, input.raw, k as i64, N_OVERSAMPLE as i64, N_ITER, self.centering as i32,
+                    omega.as_ptr() as *const c_void, comps.as_mut_ptr() as *mut c_void, means.as_mut_ptr() as *mut c_void,
+                    sing.as_mut_ptr() as *mut c_void, &mut tv as *mut A as *mut c_void,
+                    yv.as_ref().map_or(std::ptr::null(), |v| v as *const _), std::ptr::null_mut())
+            },
+            || (),
+        )?;
+        self.components = comps;
+        self.means = means;
+        self.singular = sing;
+        self.total_variance = tv;
+        self.n_samples = input.nrows();
+        Ok(())
     }
 
     fn inner_fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, y: Option<&mut Array2<A>>) -> Result<(), DecompositionError> {
@@ -457,4 +514,48 @@ fn check_offsets_len(offsets: &[i64], nseg: usize) -> Result<(), DecompositionEr
         return Err(DecompositionError::InvalidInput(format!("the model holds {} segments, offsets describe {}", nseg, offsets.len() as i64 - 1)));
     }
     Ok(())
+}
+
+/// A sparse matrix in CSR form, resident on the device with the process's context (include/petal_hip_sparse.h: an extension beyond the
+/// crate).  The arrays are checked and copied; the transposed image and the work items are built on the host and uploaded once.
+/// Indices inside a row need not be sorted, duplicates act as their sum, explicit zeros and empty rows / columns are legal.
+pub struct CsrMatrix<A: HipScalar> {
+    raw: *mut ffi_sparse::PetalCsr,
+    rows: usize,
+    cols: usize,
+    nnz: usize,
+    _elem: std::marker::PhantomData<A>,
+}
+unsafe impl<A: HipScalar> Send for CsrMatrix<A> {}
+
+impl<A: HipScalar> CsrMatrix<A> {
+    pub fn new(rows: usize, cols: usize, indptr: &[i64], indices: &[i32], values: &[A]) -> Result<Self, DecompositionError> {
+        if indptr.len() != rows + 1 {
+            return Err(DecompositionError::InvalidInput(format!("indptr should have {} entries (it has {})", rows + 1, indptr.len())));
+        }
+        if indices.len() != values.len() {
+            return Err(DecompositionError::InvalidInput("indices and values differ in length".into()));
+        }
+        let mut raw = std::ptr::null_mut();
+        with_ctx(
+            |ctx| unsafe {
+                ffi_sparse::petal_csr_create(ctx, rows as i64, cols as i64, values.len() as i64, indptr.as_ptr(), indices.as_ptr(),
+                    values.as_ptr() as *const c_void, A::DTYPE, &mut raw)
+            },
+            || (),
+        )?;
+        Ok(Self { raw, rows, cols, nnz: values.len(), _elem: std::marker::PhantomData })
+    }
+    pub fn nrows(&self) -> usize { self.rows }
+    pub fn ncols(&self) -> usize { self.cols }
+    pub fn nnz(&self) -> usize { self.nnz }
+    /// false where the device-op layer has no sparse product: the fit and the transform then densify on the host
+    pub fn resident(&self) -> bool {
+        let mut v = [0i64; 8];
+        unsafe { ffi_sparse::petal_csr_info(self.raw, v.as_mut_ptr()) };
+        v[4] != 0
+    }
+}
+impl<A: HipScalar> Drop for CsrMatrix<A> {
+    fn drop(&mut self) { unsafe { ffi_sparse::petal_csr_destroy(self.raw) } }
 }
