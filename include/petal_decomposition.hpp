@@ -24,6 +24,7 @@
 #include "petal_hip_score.h"
 #include "petal_hip_segments.h"
 #include "petal_hip_sparse.h"
+#include "petal_hip_ipca.h"
 
 namespace petal_decomposition {
 
@@ -357,6 +358,100 @@ class SegmentedPca {
     Context* ctx_;
     std::vector<A> comp_, means_, sing_, tv_;
     std::vector<int32_t> status_;
+};
+
+// The exact Pca fitted batch by batch (petal_hip_ipca.h: an extension beyond the crate).  partial_fit folds a batch into the float64
+// statistic (rows seen, mean, M2) resident with the ctx; the model is what Pca::fit returns on the concatenation of the batches, up to
+// the SIGN of each component: its entry of largest magnitude is positive (scikit-learn's rule), because a streaming fit never holds U.
+// The model is refreshed lazily, by the first accessor after a batch.  Gram route only.  Destroy it before its Context.
+template <class A>
+class IncrementalPca {
+  public:
+    explicit IncrementalPca(int64_t n_components, bool centering = true, Context* ctx = nullptr) {
+        st_.k = n_components; st_.centering = centering; st_.ctx = ctx;
+        st_.components = Array2<A>(n_components, 0);
+    }
+    IncrementalPca(const IncrementalPca&) = delete;
+    IncrementalPca& operator=(const IncrementalPca&) = delete;
+    IncrementalPca(IncrementalPca&& o) noexcept : st_(std::move(o.st_)), h_(o.h_), dirty_(o.dirty_) { o.h_ = nullptr; }
+    ~IncrementalPca() { petal_ipca_destroy(h_); }
+    // the first batch fixes d
+    IncrementalPca& partial_fit(const Array2<A>& batch) {
+        open(batch.ncols());
+        petal_matrix mx = batch.view();
+        st_.context().check(petal_ipca_partial_fit(st_.context().get(), h_, &mx));
+        dirty_ = true;
+        return *this;
+    }
+    // adds the statistic of `other` (same ctx, d and centering), exactly; `other` is unchanged
+    IncrementalPca& merge(const IncrementalPca& other) {
+        if (!other.h_) return *this;
+        open(other.info()[0]);
+        st_.context().check(petal_ipca_merge(st_.context().get(), h_, other.h_));
+        dirty_ = true;
+        return *this;
+    }
+    void reset() {
+        if (h_) st_.context().check(petal_ipca_reset(h_));
+        st_.components = Array2<A>(st_.k, 0); st_.means.clear(); st_.singular.clear(); st_.total_variance = A(0); st_.n_samples = 0;
+        dirty_ = false;
+    }
+    // { d, dtype, centering, rows seen, batches, batches the streaming kernel took, merges, 0 }
+    std::vector<int64_t> info() const {
+        std::vector<int64_t> v(8, 0);
+        if (h_) petal_ipca_info(h_, v.data());
+        return v;
+    }
+    int64_t n_samples_seen() const { return info()[3]; }
+    // the statistic as host float64 (checkpoints; combining several processes by hand): returns rows seen
+    double get_state(std::vector<double>& mean, std::vector<double>& m2) const {
+        if (!h_) throw DecompositionError(DecompositionError::InvalidInput, "no batch has been seen yet");
+        const int64_t d = info()[0];
+        double n = 0;
+        mean.assign(size_t(d), 0.0); m2.assign(size_t(d * d), 0.0);
+        st_.context().check(petal_ipca_get_state(st_.context().get(), h_, &n, mean.data(), m2.data()));
+        return n;
+    }
+    void set_state(double n, const std::vector<double>& mean, const std::vector<double>& m2) {
+        if (m2.size() != mean.size() * mean.size()) throw DecompositionError(DecompositionError::InvalidInput, "m2 should be d x d");
+        open(int64_t(mean.size()));
+        st_.context().check(petal_ipca_set_state(st_.context().get(), h_, n, mean.data(), m2.data()));
+        dirty_ = true;
+    }
+    const Array2<A>& components() { return model().components; }
+    const std::vector<A>& mean() { return model().means; }
+    int64_t n_components() const { return st_.k; }
+    const std::vector<A>& singular_values() { return model().singular; }
+    std::vector<A> explained_variance_ratio() { return model().explained_variance_ratio(); }
+    Array2<A> transform(const Array2<A>& input) { return model().transform(input); }
+    Array2<A> inverse_transform(const Array2<A>& input) { return model().inverse_transform(input); }
+    std::vector<A> explained_variance() { return model().explained_variance(); }
+    A noise_variance() { return model().noise_variance(); }
+    std::vector<A> reconstruction_error(const Array2<A>& input) { return model().reconstruction_error(input); }
+    std::vector<A> hotelling_t2(const Array2<A>& input) { return model().hotelling_t2(input); }
+    std::vector<A> score_samples(const Array2<A>& input) { return model().score_samples(input); }
+
+  private:
+    void open(int64_t d) {
+        if (h_) return;
+        st_.context().check(petal_ipca_create(st_.context().get(), d, DTypeOf<A>::value, st_.centering, &h_));
+    }
+    const detail::PcaState<A>& model() {
+        if (dirty_ && h_ && n_samples_seen() > 0) {   // (nothing seen yet: the model stays empty, as an unfitted Pca's)
+            const int64_t d = info()[0], k = st_.k;
+            Array2<A> comp(k, d);
+            std::vector<A> means(d), sing(k);
+            A tv = A(0);
+            st_.context().check(petal_ipca_finalize(st_.context().get(), h_, k, comp.data.data(), means.data(), sing.data(), &tv));
+            st_.components = std::move(comp); st_.means = std::move(means); st_.singular = std::move(sing);
+            st_.total_variance = tv; st_.n_samples = n_samples_seen();
+            dirty_ = false;
+        }
+        return st_;
+    }
+    detail::PcaState<A> st_;
+    petal_ipca* h_ = nullptr;
+    bool dirty_ = false;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

@@ -30,7 +30,8 @@ GEMM_SPLIT_BF16X3, GEMM_FP32_MFMA, GEMM_SPLIT_BF16X3_EXACT = 0, 1, 2
 # petal_ctx_set_option (petal_hip.h PETAL_OPT_*): name -> option number
 OPTIONS = {"two_plane_operands": 0, "two_plane_omega": 1, "two_plane_iterate": 2, "steering_passes": 3, "fused_pass": 4,
            "fused_pass_min_rows": 5, "verdict_threshold": 6, "means_fold_rows": 7, "gram_split": 8, "gram_split_hook": 9,
-           "d2h_kernel": 10, "row_pad": 11, "eigh_jacobi": 12, "poison": 13, "force_collective": 14, "steering_hook": 15}
+           "d2h_kernel": 10, "row_pad": 11, "eigh_jacobi": 12, "poison": 13, "force_collective": 14, "steering_hook": 15,
+           "ipca_fallback": 32}   # (32: PETAL_OPT_IPCA_FALLBACK, include/petal_hip_ipca.h -- a test aid)
 ICA_TEXTBOOK, ICA_REFERENCE_LITERAL = 0, 1
 # the contrast function of the FastICA iteration: bits 4-7 of the same `mode` argument (include/petal_hip.h); EXP and CUBE are an
 # extension beyond the crate, whose only contrast is logcosh
@@ -167,6 +168,20 @@ ABI_SPARSE = [
 ]
 CSR_ITEM_NNZ = 256   # PETAL_CSR_ITEM_NNZ
 
+# every symbol include/petal_hip_ipca.h declares (IncrementalPca: an extension beyond the crate)
+ABI_IPCA = [
+    ("petal_ipca_create", C.c_int, [_P, C.c_int64, C.c_int32, C.c_int, C.POINTER(_P)]),
+    ("petal_ipca_destroy", None, [_P]),
+    ("petal_ipca_reset", C.c_int, [_P]),
+    ("petal_ipca_partial_fit", C.c_int, [_P, _P, _M]),
+    ("petal_ipca_merge", C.c_int, [_P, _P, _P]),
+    ("petal_ipca_finalize", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P]),
+    ("petal_ipca_info", C.c_int, [_P, _L]),
+    ("petal_ipca_get_state", C.c_int, [_P, _P, _D, _D, _D]),
+    ("petal_ipca_set_state", C.c_int, [_P, _P, C.c_double, _D, _D]),
+]
+IPCA_KERNEL_MAX_D = 1024   # PETAL_IPCA_KERNEL_MAX_D
+
 
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
@@ -184,7 +199,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -193,7 +208,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -288,10 +303,11 @@ class Context:
                               f"(library {getattr(self.lib, '_petal_path', '?')})")
         self.rank, self.world_size = 0, 1
         self._csr = weakref.WeakSet()   # the sparse matrices resident with this ctx: released before it
+        self._ipca = weakref.WeakSet()  # ... and the IncrementalPca statistics
 
     def close(self):
         if getattr(self, "_h", None):
-            for m in list(getattr(self, "_csr", ())):
+            for m in list(getattr(self, "_csr", ())) + list(getattr(self, "_ipca", ())):
                 m.close()
             self.lib.petal_ctx_destroy(self._h)
             self._h = None
@@ -754,6 +770,159 @@ class Pca(_PcaModel):
 
     def fit_transform(self, x):
         return self._inner_fit(x, True)
+
+
+def _lazy_field(name):
+    """A model field of IncrementalPca: reading it brings the model up to date with the batches seen so far."""
+    def get(self):
+        self._refresh()
+        return self.__dict__[name]
+
+    def put(self, value):
+        self.__dict__[name] = value
+    return property(get, put)
+
+
+class IncrementalPca(_PcaModel):
+    """The exact ``Pca`` fitted batch by batch (``petal_ipca``, include/petal_hip_ipca.h; an extension beyond the crate, DESIGN.md
+    section 7): ``partial_fit`` folds a batch into the float64 statistic (rows seen, mean, M2) resident with the ctx, and the model is
+    what ``Pca.fit`` returns on the concatenation of the batches -- up to the SIGN of each component, which is decided from the
+    component itself (its entry of largest magnitude is positive; scikit-learn's rule) because a streaming fit never holds U.
+
+    The model is refreshed lazily: the first ``components()``, ``mean()``, ``singular_values()``, ``transform(...)`` ... after a batch
+    solves the eigenproblem once; every member inherited from the Pca model then works unchanged.  d and dtype are fixed by the first
+    batch.  Gram route only (no accurate small-sigma route): about eps64 (sigma_1 / sigma_j)^2 over the relative gap."""
+
+    _components = _lazy_field("_components")
+    _means = _lazy_field("_means")
+    _singular = _lazy_field("_singular")
+    _total_variance = _lazy_field("_total_variance")
+    n_samples = _lazy_field("n_samples")
+
+    def __init__(self, n_components: int, centering: bool = True, ctx: Optional[Context] = None):
+        self._h, self._dirty, self._d = None, False, None
+        super().__init__(n_components, centering, ctx)
+
+    # ---- the handle -------------------------------------------------------------------------------------------------------------------
+    def _open(self, d: int, dtype_code: int):
+        ctx = self._ctx()
+        self._h = C.c_void_p()
+        ctx.check(ctx.lib.petal_ipca_create(ctx._h, int(d), int(dtype_code), int(self.centering), C.byref(self._h)))
+        ctx._ipca.add(self)
+        self._d, self._dt = int(d), int(dtype_code)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self.ctx.lib.petal_ipca_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise InvalidInput("no batch has been seen yet (or the model's ctx was closed)")
+        return self._h
+
+    def info(self) -> dict:
+        """d, dtype, centering, rows seen, batches, batches the streaming kernel took, merges."""
+        out = (C.c_int64 * 8)()
+        if self.ctx.lib.petal_ipca_info(self._handle(), out) != PETAL_OK:
+            raise InvalidInput("petal_ipca_info failed")
+        keys = ("d", "dtype", "centering", "n_samples_seen", "batches", "kernel_batches", "merges")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    @property
+    def n_samples_seen(self) -> int:
+        return self.info()["n_samples_seen"] if self._h else 0
+
+    # ---- the statistic ----------------------------------------------------------------------------------------------------------------
+    def partial_fit(self, x):
+        """Fold one batch (host or device, float32 or float64; the first batch fixes d and dtype) into the statistic."""
+        keep = []
+        mx = describe(x, keep)
+        if not self._h:
+            self._open(mx.cols, mx.dtype)
+        ctx = self._ctx()
+        ctx.check(ctx.lib.petal_ipca_partial_fit(ctx._h, self._handle(), C.byref(mx)))
+        self._dirty = True
+        return self
+
+    def fit(self, x, batch_size=None):
+        """A fresh fit of x (host or device array) in row slices of ``batch_size`` (default 5 d, scikit-learn's)."""
+        rows, cols = int(x.shape[0]), int(x.shape[1])
+        if self._h:
+            self.reset()
+        step = max(int(batch_size) if batch_size else 5 * cols, 1)
+        if rows == 0:
+            self.partial_fit(x)
+        for r in range(0, rows, step):
+            self.partial_fit(x[r:r + step])
+        return self
+
+    def merge(self, other: "IncrementalPca"):
+        """Add the statistic of another model (same ctx, d, dtype and centering), exactly: the pairwise form, free of the
+        cancellation a drifting stream causes in ``partial_fit``.  ``other`` is unchanged."""
+        if not other._h:
+            return self
+        if not self._h:
+            if self.ctx is None:
+                self.ctx = other.ctx
+            self._open(other._d, other._dt)
+        ctx = self._ctx()
+        ctx.check(ctx.lib.petal_ipca_merge(ctx._h, self._handle(), other._handle()))
+        self._dirty = True
+        return self
+
+    def reset(self):
+        if self._h:
+            self._ctx().check(self.ctx.lib.petal_ipca_reset(self._h))
+        dt = self._dt
+        _PcaModel.__init__(self, self._k, self.centering, self.ctx)
+        self._dt, self._dirty = dt, False       # (the handle keeps its d and dtype)
+        return self
+
+    def state(self) -> dict:
+        """The statistic as host float64 arrays: for checkpoints, and for combining the work of several processes or GPUs by hand."""
+        ctx, d = self._ctx(), self._d
+        self._handle()
+        n, mean, m2 = C.c_double(0), np.zeros(d), np.zeros((d, d))
+        ctx.check(ctx.lib.petal_ipca_get_state(ctx._h, self._h, C.byref(n), mean.ctypes.data_as(_D), m2.ctypes.data_as(_D)))
+        return {"n": float(n.value), "mean": mean, "m2": m2, "dtype": _np_dtype(self._dt), "centering": self.centering}
+
+    @classmethod
+    def from_state(cls, state: dict, n_components: int, ctx: Optional[Context] = None):
+        m = cls(n_components, bool(state["centering"]), ctx)
+        mean = np.ascontiguousarray(state["mean"], dtype=np.float64)
+        m2 = np.ascontiguousarray(state["m2"], dtype=np.float64)
+        if m2.shape != (mean.shape[0], mean.shape[0]):
+            raise InvalidInput("m2 should be d x d")
+        m._open(mean.shape[0], PETAL_F32 if np.dtype(state["dtype"]) == np.float32 else PETAL_F64)
+        c = m._ctx()
+        c.check(c.lib.petal_ipca_set_state(c._h, m._h, float(state["n"]), mean.ctypes.data_as(_D), m2.ctypes.data_as(_D)))
+        m._dirty = True
+        return m
+
+    # ---- the model --------------------------------------------------------------------------------------------------------------------
+    def finalize(self, n_components=None):
+        """(components, means, singular values, total variance) of the rows seen so far; the statistic is not modified."""
+        ctx, d = self._ctx(), self._d
+        h = self._handle()
+        k = self._k if n_components is None else int(n_components)
+        npdt = _np_dtype(self._dt)
+        comp, means = np.zeros((max(k, 0), d), dtype=npdt), np.zeros(d, dtype=npdt)
+        sing, tv = np.zeros(max(k, 0), dtype=npdt), np.zeros(1, dtype=npdt)
+        ctx.check(ctx.lib.petal_ipca_finalize(ctx._h, h, k, comp.ctypes.data, means.ctypes.data, sing.ctypes.data, tv.ctypes.data))
+        return comp, means, sing, tv
+
+    def _refresh(self):
+        if self.__dict__.get("_dirty") and self._h and self.n_samples_seen > 0:   # (nothing seen: the model stays empty, as an unfitted Pca's)
+            comp, means, sing, tv = self.finalize()
+            self._dirty = False   # (cleared first: _store assigns the fields this method guards)
+            self._store(comp, means, sing, tv, self.info()["n_samples_seen"])
 
 
 class SegmentedPca:

@@ -10,6 +10,7 @@ SOURCES = ["hip_ops.hip", "algo.cpp", "api.cpp", "rccl.cpp"]
 HEADERS = ["ops.h", "ctx.h", os.path.join("..", "..", "include", "petal_hip.h"), os.path.join("..", "..", "include", "petal_hip_score.h"),
            os.path.join("..", "..", "include", "petal_hip_segments.h"),
            os.path.join("..", "..", "include", "petal_hip_sparse.h"),
+           os.path.join("..", "..", "include", "petal_hip_ipca.h"),
            os.path.join("..", "..", "include", "petal_hip_probe.h")] + \
     [os.path.join("kernels", f) for f in sorted(os.listdir(os.path.join(CSRC, "kernels"))) if f.endswith(".inc")]   # the parts of hip_ops.hip
 

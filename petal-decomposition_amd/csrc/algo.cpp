@@ -11,6 +11,7 @@
 
 #include "ctx.h"
 #include "../../include/petal_hip_sparse.h"
+#include "../../include/petal_hip_ipca.h"
 
 namespace petal {
 
@@ -392,6 +393,24 @@ GramEigen gram_topk_eigh(petal_ctx& c, int dt, const DBuf& C, int64_t d, int64_t
     if (dt == F64) { g.Ckeep = DBuf(c.dev, C.bytes); dev_d2d(c.dev, g.Ckeep.p, C.p, C.bytes); }
     g.vtol = dt == F32 ? 1e-12 : 3e-14;
     g.topk = topk_eigh(c, C.f64(), d, dp, nc, V, w, dt == F32 ? 1e-8 : 1e-5, r3, g.vtol);
+    return g;
+}
+
+// Gram matrix -> (V, lambda), the step Pca and IncrementalPca share.  total_variance = sigma . sigma over ALL singular values
+// (pca.rs:224) = trace of the Gram matrix: its diagonal is set aside in `diag` before the eigen-solvers overwrite C.  Then gram_topk_eigh
+// with its verdict, otherwise the full eigen-solver:
+// (order d, not the padded dp: the zero padding would only add dp - d exact zero eigenvalues, a cluster that sends the
+// two-stage solver to its Jacobi fallback; V and lam beyond d stay at the zeros set here)
+// (... and the closeness verdict of the two-stage solver covers the k pairs that reach the outputs: the noise-floor
+// eigenvalues behind them cluster on every planted spectrum and would send each such fit to the Jacobi solver -- 98 + 24 us of
+// configs[0]'s 0.34 ms -- for vectors whose only use is a discarded sign)
+GramEigen gram_eigen(petal_ctx& c, int dt, const DBuf& C, int64_t d, int64_t dp, int64_t k, const DBuf& diag, const DBuf& V, const DBuf& lam,
+                     double* r3) {
+    dev_copy2d(c.dev, diag.p, sizeof(double), C.p, (dp + 1) * sizeof(double), sizeof(double), size_t(dp), 2);
+    dev_memset(c.dev, V.p, 0, V.bytes);
+    dev_memset(c.dev, lam.p, 0, lam.bytes);
+    GramEigen g = gram_topk_eigh(c, dt, C, d, dp, k, V.f64(), lam.f64(), r3);
+    if (!g.topk) op_eigh(c.dev, C.f64(), d, dp, V.f64(), dp, lam.f64(), dt == F32 ? 1e-8 : 1e-15, false, 0, std::max<int64_t>(k, 1));
     return g;
 }
 
@@ -1076,20 +1095,10 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
     auto pipeline = [&](bool optimistic, bool route_check) -> bool {
     op_gemm_atb(c.dev, dt, X.p, X.ld, dp, muT.p, X.p, X.ld, dp, muT.p, n, C.f64(), dp, true);
     allreduce_f64(c, C.f64(), dp * dp, PETAL_SUM);
-    // total_variance = sigma . sigma over ALL singular values (pca.rs:224) = trace of the Gram matrix: its diagonal is set aside
-    // before the eigen-solvers overwrite C
-    dev_copy2d(c.dev, diag.p, sizeof(double), C.p, (dp + 1) * sizeof(double), sizeof(double), size_t(dp), 2);
-    dev_memset(c.dev, V.p, 0, V.bytes);
-    dev_memset(c.dev, lam.p, 0, lam.bytes);
-    // only the top-k pairs reach the outputs (components, singular values, the k columns of U that svd_flip signs)
-    const GramEigen g = gram_topk_eigh(c, dt, C, d, dp, k, V.f64(), lam.f64(), optimistic ? r3.f64() : nullptr);
+    // (total_variance = trace of the Gram matrix; only the top-k pairs reach the outputs: components, singular values, the k columns of
+    // U that svd_flip signs)
+    const GramEigen g = gram_eigen(c, dt, C, d, dp, k, diag, V, lam, optimistic ? r3.f64() : nullptr);
     const bool partial = g.topk;
-    // (order d, not the padded dp: the zero padding would only add dp - d exact zero eigenvalues, a cluster that sends the
-    // two-stage solver to its Jacobi fallback; V and lam beyond d stay at the zeros set above)
-    // (... and the closeness verdict of the two-stage solver covers the k pairs that reach the outputs: the noise-floor
-    // eigenvalues behind them cluster on every planted spectrum and would send each such fit to the Jacobi solver -- 98 + 24 us of
-    // configs[0]'s 0.34 ms -- for vectors whose only use is a discarded sign)
-    if (!partial) op_eigh(c.dev, C.f64(), d, dp, V.f64(), dp, lam.f64(), dt == F32 ? 1e-8 : 1e-15, false, 0, std::max<int64_t>(k, 1));
     // fp64 data with wanted singular values below 10^-3.5 sigma_1 (by the Gram route's own estimate): the QR + one-sided
     // Jacobi route keeps them to eps sigma_1 / sigma_k like the crate's gesvd (linalg.rs:70-91); two more passes over X
     // (the check needs the spectrum on the host: the first run skips it and the caller looks at the singular values that come back
@@ -2527,6 +2536,214 @@ void csr_gemm(petal_ctx& c, const petal_csr& x, bool transposed, const double* P
     dev_sync(c.dev);
     for (int64_t r = 0; r < rows; ++r)
         for (int64_t j = 0; j < N; ++j) out[r * N + j] = get_elem(hO.data(), dt, r * NP + j);
+}
+
+// ---------------------------------------------------------------------------------------------
+// IncrementalPca (include/petal_hip_ipca.h; an extension beyond the crate): the sufficient statistic (n, mean, M2)
+// of exact Pca's Gram route, accumulated batch by batch and merged exactly.  A device-op layer without the streaming kernel (the host
+// simulation), a batch wider than the kernel takes and PETAL_OPT_IPCA_FALLBACK go through the library's other ops: two passes per batch.
+__attribute__((weak)) bool op_ipca_accumulate(Dev*, int, const void*, int64_t, int64_t, int64_t, const double*, double, double*, double*) {
+    return false;
+}
+__attribute__((weak)) bool op_ipca_merge(Dev*, int64_t, double, double*, const double*, double*, double, const double*, const double*) {
+    return false;
+}
+namespace {
+void ipca_usable(const petal_ctx& c, const petal_ipca& h) {
+    if (h.owner != &c) invalid_input("the IncrementalPca handle belongs to another ctx");
+    if (c.world > 1) invalid_input("IncrementalPca: a sharded ctx (world size > 1) is not supported in this version");
+}
+// h += (n_b, mean_b, M2_b), the pairwise form: M2 = M2_a + M2_b + (n_a n_b / n) dd^T, d = mean_b - mean_a (mean_b, M2_b: DEVICE, padded as h's)
+void ipca_merge_stat(petal_ctx& c, petal_ipca& h, double n_b, const double* mean_b, const double* m2_b) {
+    if (n_b == 0) return;
+    const int64_t dp = h.dp;
+    if (h.n == 0) {   // (the state of a fresh handle is all zeros: the other statistic as it is)
+        dev_d2d(c.dev, h.m2, m2_b, sizeof(double) * dp * dp);
+        dev_d2d(c.dev, h.mean, mean_b, sizeof(double) * dp);
+        h.n = n_b;
+        return;
+    }
+    const double n = h.n + n_b;
+    DBuf delta(c.dev, sizeof(double) * dp);   // the kernel: the new mean (it reads the old one in every workgroup); below: mean_b - mean_a
+    if (!c.ipca_fallback && op_ipca_merge(c.dev, dp, h.n, h.m2, h.mean, delta.f64(), n_b, m2_b, mean_b)) {
+        dev_d2d(c.dev, h.mean, delta.p, delta.bytes);
+    } else {
+        op_daxpy(c.dev, dp * dp, 1.0, m2_b, h.m2);
+        if (h.centering) {
+            dev_d2d(c.dev, delta.p, mean_b, delta.bytes);
+            op_daxpy(c.dev, dp, -1.0, h.mean, delta.f64());
+            op_dgemm(c.dev, true, false, dp, dp, 1, h.n * n_b / n, delta.f64(), dp, delta.f64(), dp, 1.0, h.m2, dp);
+            op_daxpy(c.dev, dp, n_b / n, delta.f64(), h.mean);
+        }
+    }
+    h.n = n;
+}
+}  // namespace
+
+petal_ipca* ipca_create(petal_ctx& c, int64_t d, int32_t dtype, bool centering) {
+    if (dtype != PETAL_F32 && dtype != PETAL_F64) invalid_input("IncrementalPca: unsupported dtype");
+    if (d < 0) invalid_input("IncrementalPca: negative shape");
+    if (d > (int64_t(1) << 15)) invalid_input("IncrementalPca: too many columns (the statistic is d x d)");
+    if (c.world > 1) invalid_input("IncrementalPca: a sharded ctx (world size > 1) is not supported in this version");
+    std::unique_ptr<petal_ipca> h(new petal_ipca());
+    h->owner = &c; h->d = d; h->dp = round_up(std::max<int64_t>(d, 1), 16); h->dtype = dtype; h->centering = centering;
+    h->mean = static_cast<double*>(dev_alloc(c.dev, sizeof(double) * h->dp));
+    try {
+        h->m2 = static_cast<double*>(dev_alloc(c.dev, sizeof(double) * h->dp * h->dp));
+    } catch (...) {
+        dev_free(c.dev, h->mean);
+        throw;
+    }
+    ipca_reset(*h);
+    return h.release();
+}
+void ipca_destroy(petal_ipca* h) {
+    if (h->mean) dev_free(h->owner->dev, h->mean);
+    if (h->m2) dev_free(h->owner->dev, h->m2);
+    delete h;
+}
+void ipca_reset(petal_ipca& h) {
+    dev_memset(h.owner->dev, h.mean, 0, sizeof(double) * h.dp);
+    dev_memset(h.owner->dev, h.m2, 0, sizeof(double) * h.dp * h.dp);
+    h.n = 0;
+    h.batches = h.kernel_batches = h.merges = 0;
+}
+
+void ipca_partial_fit(petal_ctx& c, petal_ipca& h, const petal_matrix& x) {
+    ipca_usable(c, h);
+    check_matrix(x, "input");
+    if (x.dtype != h.dtype) invalid_input("input dtype differs from the IncrementalPca handle's dtype");
+    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    if (x.rows == 0) return;
+    if (h.d == 0) { h.n += double(x.rows); ++h.batches; return; }
+    const DevMat X = ingest(c, x);
+    const int dt = X.dtype;
+    const int64_t m = X.n, dp = h.dp;
+    bool kernel = false;
+    if (!c.ipca_fallback) {
+        // the centre of the pass: the running mean; the first batch has none yet and takes the mean of its first rows (any centre near
+        // the data serves: the update moves the statistic to the true mean)
+        const double* centre = h.centering ? h.mean : nullptr;
+        DBuf c64, cT;
+        if (h.centering && h.n == 0) {
+            const int64_t first = std::min<int64_t>(m, 64);
+            c64 = DBuf(c.dev, sizeof(double) * dp);
+            cT = DBuf(c.dev, dtype_size(dt) * dp);
+            op_colmean(c.dev, dt, X.p, first, dp, X.ld, double(first), c64.f64(), cT.p, false);
+            centre = c64.f64();
+        }
+        kernel = op_ipca_accumulate(c.dev, dt, X.p, m, dp, X.ld, centre, h.n, h.m2, h.mean);
+        if (kernel) h.n += double(m);
+    }
+    if (!kernel) {
+        // two passes from existing ops: the batch's own means, its Gram matrix about them, the pairwise merge.  op_gemm_atb centres in
+        // the storage type (the crate's `input - &means`): a float32 batch is widened first, so that here too the centre is subtracted
+        // in fp64 and the statistic does not depend on the batching beyond fp64 rounding.
+        const void* Xp = X.p;
+        int bdt = dt;
+        DBuf wide;
+        if (dt == F32 && h.centering) {
+            const int64_t count = (m - 1) * X.ld + dp;   // (to the end of the last row: a zero-copy input ends there)
+            wide = DBuf(c.dev, sizeof(double) * size_t(count));
+            op_cvt_to_f64(c.dev, F32, wide.f64(), X.p, count);
+            Xp = wide.p;
+            bdt = F64;
+        }
+        DBuf mu64(c.dev, sizeof(double) * dp), muT(c.dev, dtype_size(bdt) * dp), G(c.dev, sizeof(double) * dp * dp);
+        if (h.centering) op_colmean(c.dev, bdt, Xp, m, dp, X.ld, double(m), mu64.f64(), muT.p, false);
+        else dev_memset(c.dev, mu64.p, 0, mu64.bytes);
+        const void* mu = h.centering ? muT.p : nullptr;
+        op_gemm_atb(c.dev, bdt, Xp, X.ld, dp, mu, Xp, X.ld, dp, mu, m, G.f64(), dp, true);
+        ipca_merge_stat(c, h, double(m), mu64.f64(), G.f64());
+    }
+    ++h.batches;
+    if (kernel) ++h.kernel_batches;
+    if (x.space == PETAL_HOST) dev_sync(c.dev);   // (the staged copy of a host batch is released behind the kernels; device input: no wait)
+}
+
+void ipca_merge(petal_ctx& c, petal_ipca& into, const petal_ipca& other) {
+    ipca_usable(c, into);
+    ipca_usable(c, other);
+    if (&into == &other) invalid_input("cannot merge an IncrementalPca handle into itself");
+    if (into.d != other.d || into.dtype != other.dtype || into.centering != other.centering)
+        invalid_input("IncrementalPca merge: the handles differ in d, dtype or centering");
+    if (other.n == 0) return;
+    ipca_merge_stat(c, into, other.n, other.mean, other.m2);
+    ++into.merges;
+}
+
+void ipca_finalize(petal_ctx& c, const petal_ipca& h, int64_t k, void* components, void* means, void* singular, void* total_variance) {
+    ipca_usable(c, h);
+    if (k < 0) invalid_input("negative parameter");
+    if (h.n == 0) invalid_input("no rows have been seen");
+    const int dt = h.dtype;
+    const int64_t d = h.d, dp = h.dp, n_total = int64_t(h.n);
+    if (n_total < k || d < k) invalid_input("every dimension should be at least " + std::to_string(k));  // pca.rs:199-204
+    if (d == 0) {
+        if (total_variance) put_elem(total_variance, dt, 0, 0.0);
+        return;
+    }
+    const size_t esz = dtype_size(dt);
+    // the eigen-solvers overwrite their input: they get a copy, the statistic stays as it is
+    DBuf C(c.dev, sizeof(double) * dp * dp), V(c.dev, sizeof(double) * dp * dp), lam(c.dev, sizeof(double) * dp);
+    DBuf sig(c.dev, sizeof(double) * dp), inv(c.dev, sizeof(double) * dp), diag(c.dev, sizeof(double) * dp);
+    DBuf compd(c.dev, esz * size_t(std::max<int64_t>(k, 1)) * d);
+    dev_d2d(c.dev, C.p, h.m2, C.bytes);
+    gram_eigen(c, dt, C, d, dp, k, diag, V, lam, nullptr);
+    op_sigma_inv(c.dev, lam.f64(), sig.f64(), inv.f64(), dp, dt == F32 ? 1e-6 : 1e-10);
+    op_transpose_out(c.dev, dt, V.f64(), dp, d, k, compd.p);
+    std::vector<double> hdiag(dp), hs(dp), hmu(dp);
+    std::vector<char> hcomp(esz * size_t(k) * d);
+    {
+        void* dsts[4] = {hdiag.data(), hs.data(), hmu.data(), hcomp.data()};
+        const void* srcs[4] = {diag.p, sig.p, h.mean, compd.p};
+        const size_t lens[4] = {diag.bytes, sig.bytes, sizeof(double) * size_t(dp), hcomp.size()};
+        dev_d2h_multi(c.dev, 4, dsts, srcs, lens);
+    }
+    dev_sync(c.dev);
+    double tvar = 0;
+    for (int64_t j = 0; j < d; ++j) tvar += hdiag[j];
+    if (!std::isfinite(tvar)) linalg_error("did not converge");   // (a NaN or an infinity in some batch: as pca_fit's trace check)
+    // Signs.  svd_flip decides from U (pca.rs:826-839), which a streaming fit never holds: the entry of largest magnitude of every
+    // component is made positive instead (ties: the lowest index) -- scikit-learn's rule for its incremental PCA.
+    const auto rows = [&](const auto* src, auto* dst) {
+        for (int64_t j = 0; j < k; ++j) {
+            int64_t best = 0;
+            for (int64_t i = 1; i < d; ++i)
+                if (std::fabs(src[j * d + i]) > std::fabs(src[j * d + best])) best = i;
+            const bool flip = src[j * d + best] < 0;
+            for (int64_t i = 0; i < d; ++i) dst[j * d + i] = flip ? -src[j * d + i] : src[j * d + i];
+        }
+    };
+    if (k > 0 && !components) invalid_input("components must not be null");
+    if (dt == F32) rows(reinterpret_cast<const float*>(hcomp.data()), static_cast<float*>(components));
+    else rows(reinterpret_cast<const double*>(hcomp.data()), static_cast<double*>(components));
+    for (int64_t j = 0; j < k && singular; ++j) put_elem(singular, dt, j, hs[j]);
+    for (int64_t i = 0; i < d && means; ++i) put_elem(means, dt, i, hmu[i]);
+    if (total_variance) put_elem(total_variance, dt, 0, tvar);
+}
+
+void ipca_get_state(petal_ctx& c, const petal_ipca& h, double* n, double* mean, double* m2) {
+    ipca_usable(c, h);
+    if (n) *n = h.n;
+    if (h.d == 0) return;
+    if (mean) dev_d2h(c.dev, mean, h.mean, sizeof(double) * h.d);
+    if (m2) dev_copy2d(c.dev, m2, sizeof(double) * h.d, h.m2, sizeof(double) * h.dp, sizeof(double) * h.d, size_t(h.d), 1);
+    dev_sync(c.dev);
+}
+void ipca_set_state(petal_ctx& c, petal_ipca& h, double n, const double* mean, const double* m2) {
+    ipca_usable(c, h);
+    if (!(n >= 0) || !std::isfinite(n) || n != std::floor(n)) invalid_input("the number of rows seen should be a non-negative whole number");
+    const int64_t batches = h.batches, kernel_batches = h.kernel_batches, merges = h.merges;
+    if (n > 0 && h.d > 0 && (!m2 || (h.centering && !mean))) invalid_input("mean and m2 must not be null");
+    ipca_reset(h);
+    h.batches = batches; h.kernel_batches = kernel_batches; h.merges = merges;
+    if (n == 0) return;
+    h.n = n;
+    if (h.d == 0) return;
+    if (h.centering) dev_h2d(c.dev, h.mean, mean, sizeof(double) * h.d);
+    dev_copy2d(c.dev, h.m2, sizeof(double) * h.dp, m2, sizeof(double) * h.d, sizeof(double) * h.d, size_t(h.d), 0);
+    dev_sync(c.dev);
 }
 
 }  // namespace petal

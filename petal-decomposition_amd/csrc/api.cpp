@@ -8,6 +8,7 @@
 #include "../../include/petal_hip_score.h"
 #include "../../include/petal_hip_segments.h"
 #include "../../include/petal_hip_sparse.h"
+#include "../../include/petal_hip_ipca.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -139,6 +140,7 @@ int petal_ctx_set_gemm_mode(petal_ctx* ctx, int mode) {
 int petal_ctx_set_option(petal_ctx* ctx, int option, double value) {
     return guarded(ctx, [&] {
         if (option == PETAL_OPT_FORCE_COLLECTIVE) { ctx->force_collective = value != 0; return; }
+        if (option == PETAL_OPT_IPCA_FALLBACK) { ctx->ipca_fallback = value != 0; return; }
         if (option < 0 || option >= OPT_COUNT || !(value == value)) invalid_input("unknown ctx option or NaN value");
         dev_set_option(ctx->dev, option, value);
     });
@@ -147,6 +149,7 @@ int petal_ctx_set_option(petal_ctx* ctx, int option, double value) {
 int petal_ctx_get_option(const petal_ctx* ctx, int option, double* value) {
     if (!ctx || !value) return PETAL_INVALID_INPUT;
     if (option == PETAL_OPT_FORCE_COLLECTIVE) { *value = ctx->force_collective ? 1.0 : 0.0; return PETAL_OK; }
+    if (option == PETAL_OPT_IPCA_FALLBACK) { *value = ctx->ipca_fallback ? 1.0 : 0.0; return PETAL_OK; }
     if (option < 0 || option >= OPT_COUNT) return PETAL_INVALID_INPUT;
     *value = dev_option(ctx->dev, option);
     return PETAL_OK;
@@ -259,6 +262,65 @@ int petal_csr_gemm(petal_ctx* ctx, const petal_csr* x, int transposed, const dou
     return guarded(ctx, [&] {
         need(x, "x");
         csr_gemm(*ctx, *x, transposed != 0, P, N, a, s, out);
+    });
+}
+
+// ---- include/petal_hip_ipca.h: IncrementalPca --------------------------------------------------------------------------------------
+int petal_ipca_create(petal_ctx* ctx, int64_t d, int32_t dtype, int centering, petal_ipca** out) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(out, "out");
+        *out = ipca_create(*ctx, d, dtype, centering != 0);
+    });
+}
+void petal_ipca_destroy(petal_ipca* h) {
+    if (!h) return;
+    try {
+        DeviceScope scope(h->owner->dev);
+        ipca_destroy(h);
+    } catch (...) {}
+}
+int petal_ipca_reset(petal_ipca* h) {
+    if (!h) return PETAL_INVALID_INPUT;
+    return guarded(h->owner, [&] { ipca_reset(*h); });
+}
+int petal_ipca_partial_fit(petal_ctx* ctx, petal_ipca* h, const petal_matrix* x) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        need(x, "x");
+        ipca_partial_fit(*ctx, *h, *x);
+    });
+}
+int petal_ipca_merge(petal_ctx* ctx, petal_ipca* into, const petal_ipca* other) {
+    return guarded(ctx, [&] {
+        need(into, "into");
+        need(other, "other");
+        ipca_merge(*ctx, *into, *other);
+    });
+}
+int petal_ipca_finalize(petal_ctx* ctx, const petal_ipca* h, int64_t k, void* components, void* means, void* singular,
+                        void* total_variance) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        ipca_finalize(*ctx, *h, k, components, means, singular, total_variance);
+    });
+}
+int petal_ipca_info(const petal_ipca* h, int64_t* out8) {
+    if (!h || !out8) return PETAL_INVALID_INPUT;
+    const int64_t v[8] = {h->d, h->dtype, h->centering ? 1 : 0, int64_t(h->n), h->batches, h->kernel_batches, h->merges, 0};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    return PETAL_OK;
+}
+int petal_ipca_get_state(petal_ctx* ctx, const petal_ipca* h, double* n, double* mean_d, double* m2_dxd) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        ipca_get_state(*ctx, *h, n, mean_d, m2_dxd);
+    });
+}
+int petal_ipca_set_state(petal_ctx* ctx, petal_ipca* h, double n, const double* mean_d, const double* m2_dxd) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        ipca_set_state(*ctx, *h, n, mean_d, m2_dxd);
     });
 }
 

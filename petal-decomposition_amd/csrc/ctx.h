@@ -18,6 +18,7 @@ struct petal_ctx {
     void* allreduce_user = nullptr;
     int rank = 0, world = 1;
     int profiling = 0;
+    bool ipca_fallback = false;      // PETAL_OPT_IPCA_FALLBACK (include/petal_hip_ipca.h): a test aid
     bool force_collective = false;   // PETAL_OPT_FORCE_COLLECTIVE (default: env PETAL_FORCE_COLLECTIVE at petal_ctx_create)
     petal_stats stats{};
     void* rccl = nullptr;  // the built-in RCCL communicator (rccl.cpp), when petal_ctx_init_rccl installed it
@@ -44,6 +45,18 @@ struct petal_csr {
     } host[2];
     petal::CsrImage dev[2];              // resident: views of the four device blocks of each image
     void* blocks[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
+};
+
+// include/petal_hip_ipca.h: the running statistic of an IncrementalPca, resident with its ctx
+struct petal_ipca {
+    petal_ctx* owner = nullptr;
+    int64_t d = 0, dp = 0;
+    int dtype = 0;
+    bool centering = true;
+    double n = 0;                        // rows seen (the one part of the statistic that lives on the host)
+    int64_t batches = 0, kernel_batches = 0, merges = 0;
+    double* mean = nullptr;              // device fp64, dp (zero when centering is off)
+    double* m2 = nullptr;                // device fp64, dp x dp, symmetric, both triangles
 };
 
 namespace petal {
@@ -133,6 +146,15 @@ void rpca_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, int64_t n_oversam
 void transform_csr(petal_ctx& c, const petal_csr& x, const void* components, const void* means, int64_t k, int64_t d, bool centering,
                    const petal_matrix& y_out, int64_t* kernel_path);
 void csr_gemm(petal_ctx& c, const petal_csr& x, bool transposed, const double* P, int64_t N, const double* a, const double* s, double* out);
+// include/petal_hip_ipca.h: IncrementalPca
+petal_ipca* ipca_create(petal_ctx& c, int64_t d, int32_t dtype, bool centering);
+void ipca_destroy(petal_ipca* h);
+void ipca_reset(petal_ipca& h);
+void ipca_partial_fit(petal_ctx& c, petal_ipca& h, const petal_matrix& x);
+void ipca_merge(petal_ctx& c, petal_ipca& into, const petal_ipca& other);
+void ipca_finalize(petal_ctx& c, const petal_ipca& h, int64_t k, void* components, void* means, void* singular, void* total_variance);
+void ipca_get_state(petal_ctx& c, const petal_ipca& h, double* n, double* mean, double* m2);
+void ipca_set_state(petal_ctx& c, petal_ipca& h, double n, const double* mean, const double* m2);
 void fastica_fit(petal_ctx& c, const petal_matrix& x, int64_t n_components, double tol, int64_t max_iter, int mode,
                  const void* w_init, void* components, void* means, int64_t* n_iter, const petal_matrix* y_out);
 void ica_par(petal_ctx& c, const petal_matrix& x1, double tol, int64_t max_iter, int mode, const void* w_init,

@@ -20,6 +20,8 @@
 //   segmented Pca: k_pca_segments (one workgroup per row segment: means, fp64 Gram, wg_jacobi_fast, svd_flip, outputs), k_seg_project
 //   sparse data: k_spmm (CSR x tall-skinny dense, one wave per work item of <= 256 nonzeros, gathered rows of P in 16-byte loads, fp64
 //     accumulators, implicit centring in the epilogue), k_spmm_combine (split rows, in item order), k_csr_rowstats
+//   IncrementalPca: k_gram_stream (fp64-MFMA Gram matrix and column sums of one batch about an fp64 centre, x widened before the centre is
+//     subtracted; row-chunk slabs), k_ipca_merge (slabs summed in order, rank-one terms, M2 and the mean updated; also the pairwise merge)
 //   *_simple     generic (any shape, f32 / f64, fp64 accumulate) kernels for small / unaligned / f64 inputs
 //
 // wave = 64 lanes everywhere.  MFMA 16x16x4 f32 fragment maps (cdna_hip_programming.md section 3):
@@ -590,4 +592,5 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #include "kernels/host_pow3_eigh.inc"   // host-side launchers: the fused pass, Cholesky / eigen-solver / remaining small ops
 #include "kernels/k_pca_segments.inc"   // segmented Pca: one workgroup per row segment (k_pca_segments), k_seg_project, their launchers
 #include "kernels/k_spmm.inc"   // sparse (CSR) x dense products of RandomizedPca on sparse data (k_spmm, k_spmm_combine, k_csr_rowstats), their launchers
+#include "kernels/k_ipca.inc"   // IncrementalPca: the per-batch fp64 Gram + column sums about a fixed centre (k_gram_stream), the statistic's update (k_ipca_merge)
 }  // namespace petal

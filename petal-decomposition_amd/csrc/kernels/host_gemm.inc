@@ -600,6 +600,43 @@ static void launch_atb(Dev* d, const float* A, int64_t lda, int M, const float* 
     launch_check();
 }
 
+// live 32 x 64 wave tiles of a symmetric fp64-MFMA product (the enumeration of k_atb_f64 / k_gram_stream), four to a workgroup
+static int gram64_sym_workgroups(int mslices, int npanels) {
+    int tiles = 0;
+    for (int a = 0; a < mslices; ++a) tiles += npanels - std::min(npanels, a / 2);
+    return cdiv(tiles, 4);
+}
+// The row split of the fp64-MFMA products (k_atb_f64, k_gram_stream): the number of row chunks for `active` workgroups per chunk, and
+// *chunk, the rows of each (a multiple of 16).
+static int64_t gram64_row_split(int64_t n, int64_t M, int64_t N, int active, int64_t* chunk) {
+    // row split: workgroups are dealt round-robin to the 256 CUs (up to three resident on each: the kernel's register
+    // budget), so the launch takes ceil(active * ns / 256) / ns of the single-split time t1 -- one workgroup's four 32 x 64
+    // tiles over all n rows, ~0.1 us a row (20000 x 256 in 15 splits: 119 us) -- plus what the ns fp64 slabs cost to write and
+    // to combine (M N 16 bytes each at ~4 TB/s); pick the ns that minimises the sum.  (Round 4: a hard cap "slabs <= 40 % of
+    // the input traffic" stood here and left 20000 x 256 on 75 workgroups: 119 us where 250 take half that.)
+    const int64_t ns_max = std::min<int64_t>(128, std::max<int64_t>(1, n / 64));
+    const double t1 = 0.1 * double(n), slab_us = double(M) * double(N) * 16.0 / 4.0e6;
+    auto launch_us = [&](int64_t ns) { return t1 * double((active * ns + 255) / 256) / double(ns) * (active * ns <= 256 ? 1.25 : 1.0); };
+    // (a single workgroup per CU leaves one wave per SIMD and the load latency exposed: measured 312 vs 265 us)
+    int64_t nsplit = 1;
+    double best = 1e30;
+    for (int64_t ns = 1; ns <= ns_max; ++ns) {
+        const double cost = launch_us(ns) + slab_us * double(ns);
+        if (cost < best * 0.97) { best = cost; nsplit = ns; }
+    }
+    // among the splits that tie with the best one, the finest up to 96: whole "rounds" of workgroups cost the same in this
+    // model, but a finer split keeps three workgroups on a CU and shortens the tail of the launch (500000 x 512: 2909 us at
+    // 28 splits, 2863 at 42, 2837 at 56, 2757 at 84 -- against 0.4 us of k_sum_parts2 per extra slab) -- while the slabs stay
+    // small change (3 % of the launch)
+    {
+        const double base = launch_us(nsplit);
+        for (int64_t ns = nsplit + 1; ns <= std::min<int64_t>(ns_max, 96); ++ns)
+            if (launch_us(ns) <= base * 1.005 && slab_us * double(ns) <= 0.03 * base) nsplit = ns;
+    }
+    *chunk = ((n + nsplit - 1) / nsplit + 15) / 16 * 16;
+    return (n + *chunk - 1) / *chunk;
+}
+
 void op_gemm_atb(Dev* d, int dt, const void* A, int64_t lda, int64_t M, const void* muA, const void* B, int64_t ldb, int64_t N,
                  const void* muB, int64_t n, double* C, int64_t ldc, bool precise, bool steering) {
     if (M == 0 || N == 0) return;
@@ -618,38 +655,10 @@ void op_gemm_atb(Dev* d, int dt, const void* A, int64_t lda, int64_t M, const vo
         const int mslices = cdiv(M, 32), npanels = ne5 ? (int)(N / 80) : cdiv(N, 64);
         const int gx = cdiv(M, 128);
         int active = gx * npanels;  // workgroups per row chunk
-        if (sym) {   // live 32 x 64 wave tiles, four to a workgroup
-            int tiles = 0;
-            for (int a = 0; a < mslices; ++a) tiles += npanels - std::min(npanels, a / 2);
-            active = cdiv(tiles, 4);
-        }
-        // row split: workgroups are dealt round-robin to the 256 CUs (up to three resident on each: the kernel's register
-        // budget), so the launch takes ceil(active * ns / 256) / ns of the single-split time t1 -- one workgroup's four 32 x 64
-        // tiles over all n rows, ~0.1 us a row (20000 x 256 in 15 splits: 119 us) -- plus what the ns fp64 slabs cost to write and
-        // to combine (M N 16 bytes each at ~4 TB/s); pick the ns that minimises the sum.  (Round 4: a hard cap "slabs <= 40 % of
-        // the input traffic" stood here and left 20000 x 256 on 75 workgroups: 119 us where 250 take half that.)
-        const int64_t ns_max = std::min<int64_t>(128, std::max<int64_t>(1, n / 64));
-        const double t1 = 0.1 * double(n), slab_us = double(M) * double(N) * 16.0 / 4.0e6;
-        auto launch_us = [&](int64_t ns) { return t1 * double((active * ns + 255) / 256) / double(ns) * (active * ns <= 256 ? 1.25 : 1.0); };
-        // (a single workgroup per CU leaves one wave per SIMD and the load latency exposed: measured 312 vs 265 us)
-        int64_t nsplit = 1;
-        double best = 1e30;
-        for (int64_t ns = 1; ns <= ns_max; ++ns) {
-            const double cost = launch_us(ns) + slab_us * double(ns);
-            if (cost < best * 0.97) { best = cost; nsplit = ns; }
-        }
-        // among the splits that tie with the best one, the finest up to 96: whole "rounds" of workgroups cost the same in this
-        // model, but a finer split keeps three workgroups on a CU and shortens the tail of the launch (500000 x 512: 2909 us at
-        // 28 splits, 2863 at 42, 2837 at 56, 2757 at 84 -- against 0.4 us of k_sum_parts2 per extra slab) -- while the slabs stay
-        // small change (3 % of the launch)
-        {
-            const double base = launch_us(nsplit);
-            for (int64_t ns = nsplit + 1; ns <= std::min<int64_t>(ns_max, 96); ++ns)
-                if (launch_us(ns) <= base * 1.005 && slab_us * double(ns) <= 0.03 * base) nsplit = ns;
-        }
+        if (sym) active = gram64_sym_workgroups(mslices, npanels);
+        int64_t chunk = 0;
+        const int64_t nsplit = gram64_row_split(n, M, N, active, &chunk);
         (void)mslices;
-        const int64_t chunk = ((n + nsplit - 1) / nsplit + 15) / 16 * 16;
-        nsplit = (n + chunk - 1) / chunk;
         double* part = (double*)dev_alloc(d, sizeof(double) * nsplit * M * N);
         const dim3 grid(sym ? active : gx, sym ? 1 : npanels, (unsigned)nsplit), block(256);
         TagScope ts(d);

@@ -189,6 +189,20 @@ bool op_csr_colstats(Dev*, int dtype, const CsrImage& img, double* stats);
 // send float32 data through the split-product or the fp32-MFMA kernel as the mode says).
 bool op_tall_times_small(Dev*, int dtype, const void* M, int64_t rows, int64_t K, int64_t ldm, const double* S, int64_t N, int64_t lds,
                          void* out, int64_t ldo);
+// IncrementalPca (include/petal_hip_ipca.h; an extension beyond the crate).  The statistic lives in DEVICE memory as fp64: M2 (dp x dp,
+// symmetric, both triangles) and mean (dp); dp a multiple of 16, the padding zero.  Each returns "this layer did the work": false,
+// NOTHING done, where it has no kernel for the shape (dp > 1024) or lacks the op -- algo.cpp's weak defaults return false and the
+// caller then takes two passes with op_colmean / op_gemm_atb(precise) and merges pairwise.
+// One batch X (m rows x dp in dtype, ldx; m > 0) in one pass about `centre` (DEVICE fp64, dp; nullable = centring off):
+//     s = sum (x - centre),  G = sum (x - centre)(x - centre)^T     x widened to fp64 BEFORE the subtraction, all products and sums fp64
+//     M2 += G - s s^T / (n_seen + m),   mean = centre + s / (n_seen + m)     (centre may be mean itself; centring off: M2 += G only)
+// No atomics, no host round trip between the two launches.
+bool op_ipca_accumulate(Dev*, int dtype, const void* X, int64_t m, int64_t dp, int64_t ldx, const double* centre, double n_seen, double* M2,
+                        double* mean);
+// The pairwise merge: M2_a += M2_b + (n_a n_b / n) dd^T, mean_out = mean_a + (n_b / n) d, d = mean_b - mean_a, n = n_a + n_b.
+// mean_out must not be mean_a, and M2_a not M2_b.
+bool op_ipca_merge(Dev*, int64_t dp, double n_a, double* M2_a, const double* mean_a, double* mean_out, double n_b, const double* M2_b,
+                   const double* mean_b);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.

@@ -3,6 +3,7 @@
 //! image) -- see Cargo.toml.  Model state lives in these structs exactly as in the reference
 //! (`src/pca.rs:41-51, 317-329`, `src/ica.rs:41-50`), so serde persistence keeps its field names.
 mod ffi;
+mod ffi_ipca;
 mod ffi_score;
 mod ffi_segments;
 mod ffi_sparse;
@@ -10,7 +11,7 @@ mod ica;
 mod pca;
 
 pub use ica::{Contrast, FastIca, FastIcaBuilder};
-pub use pca::{CsrMatrix, Pca, PcaBuilder, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
+pub use pca::{CsrMatrix, IncrementalPca, Pca, PcaBuilder, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
 
 use ndarray::{ArrayBase, Data, Ix2};
 use std::ffi::CStr;

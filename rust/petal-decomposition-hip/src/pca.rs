@@ -1,5 +1,5 @@
 //! `Pca` (`src/pca.rs:41-231` of the reference) and `RandomizedPca` (`src/pca.rs:317-663`) over the C ABI.
-use crate::{ffi, ffi_score, ffi_segments, ffi_sparse, view, with_ctx, DecompositionError, HipScalar};
+use crate::{ffi, ffi_ipca, ffi_score, ffi_segments, ffi_sparse, view, with_ctx, DecompositionError, HipScalar};
 use ndarray::{Array1, Array2, Array3, ArrayBase, Data, Ix2};
 use rand::Rng;
 use rand_distr::StandardNormal;
@@ -558,4 +558,121 @@ impl<A: HipScalar> CsrMatrix<A> {
 }
 impl<A: HipScalar> Drop for CsrMatrix<A> {
     fn drop(&mut self) { unsafe { ffi_sparse::petal_csr_destroy(self.raw) } }
+}
+
+/// The exact `Pca` fitted batch by batch (include/petal_hip_ipca.h: an extension beyond the crate).  `partial_fit` folds a batch into
+/// the float64 statistic (rows seen, mean, M2) resident on the device; `model` is what `Pca::fit` returns on the concatenation of the
+/// batches, up to the SIGN of each component: its entry of largest magnitude is positive (scikit-learn's rule), because a streaming
+/// fit never holds U.  Gram route only: about eps64 (sigma_1 / sigma_j)^2 over the relative gap.
+pub struct IncrementalPca<A: HipScalar> {
+    raw: *mut ffi_ipca::PetalIpca,
+    model: Pca<A>,
+    dirty: bool,
+}
+unsafe impl<A: HipScalar> Send for IncrementalPca<A> {}
+
+impl<A: HipScalar> IncrementalPca<A> {
+    pub fn new(n_components: usize) -> Self { Self::with_centering(n_components, true) }
+    pub fn with_centering(n_components: usize, centering: bool) -> Self {
+        Self { raw: std::ptr::null_mut(), model: PcaBuilder::new(n_components).centering(centering).build(), dirty: false }
+    }
+    pub fn n_components(&self) -> usize { self.model.n_components() }
+    /// { d, dtype, centering, rows seen, batches, batches the streaming kernel took, merges, 0 }
+    pub fn info(&self) -> [i64; 8] {
+        let mut v = [0i64; 8];
+        if !self.raw.is_null() {
+            unsafe { ffi_ipca::petal_ipca_info(self.raw, v.as_mut_ptr()) };
+        }
+        v
+    }
+    pub fn n_samples_seen(&self) -> usize { self.info()[3] as usize }
+
+    fn open(&mut self, d: usize) -> Result<(), DecompositionError> {
+        if !self.raw.is_null() {
+            return Ok(());
+        }
+        let mut raw = std::ptr::null_mut();
+        with_ctx(|ctx| unsafe { ffi_ipca::petal_ipca_create(ctx, d as i64, A::DTYPE, self.model.centering as i32, &mut raw) }, || ())?;
+        self.raw = raw;
+        Ok(())
+    }
+    /// Folds one batch into the statistic; the first batch fixes d.
+    pub fn partial_fit<S: Data<Elem = A>>(&mut self, batch: &ArrayBase<S, Ix2>) -> Result<(), DecompositionError> {
+        self.open(batch.ncols())?;
+        let x = view(batch);
+        let raw = self.raw;
+        with_ctx(|ctx| unsafe { ffi_ipca::petal_ipca_partial_fit(ctx, raw, &x) }, || ())?;
+        self.dirty = true;
+        Ok(())
+    }
+    /// Adds the statistic of `other` (same d and centering), exactly: the pairwise form.  `other` is unchanged.
+    pub fn merge(&mut self, other: &IncrementalPca<A>) -> Result<(), DecompositionError> {
+        if other.raw.is_null() {
+            return Ok(());
+        }
+        self.open(other.info()[0] as usize)?;
+        let (raw, theirs) = (self.raw, other.raw);
+        with_ctx(|ctx| unsafe { ffi_ipca::petal_ipca_merge(ctx, raw, theirs) }, || ())?;
+        self.dirty = true;
+        Ok(())
+    }
+    pub fn reset(&mut self) -> Result<(), DecompositionError> {
+        let raw = self.raw;
+        if !raw.is_null() {
+            with_ctx(|_| unsafe { ffi_ipca::petal_ipca_reset(raw) }, || ())?;
+        }
+        self.model = PcaBuilder::new(self.model.n_components()).centering(self.model.centering).build();
+        self.dirty = false;
+        Ok(())
+    }
+    /// The statistic as host float64: (rows seen, mean, M2).
+    pub fn state(&self) -> Result<(f64, Array1<f64>, Array2<f64>), DecompositionError> {
+        if self.raw.is_null() {
+            return Err(DecompositionError::InvalidInput("no batch has been seen yet".into()));
+        }
+        let d = self.info()[0] as usize;
+        let (mut n, mut mean, mut m2) = (0f64, Array1::<f64>::default(d), Array2::<f64>::default((d, d)));
+        let raw = self.raw;
+        with_ctx(|ctx| unsafe { ffi_ipca::petal_ipca_get_state(ctx, raw, &mut n, mean.as_mut_ptr(), m2.as_mut_ptr()) }, || ())?;
+        Ok((n, mean, m2))
+    }
+    pub fn set_state(&mut self, n: f64, mean: &Array1<f64>, m2: &Array2<f64>) -> Result<(), DecompositionError> {
+        if m2.dim() != (mean.len(), mean.len()) || !m2.is_standard_layout() {
+            return Err(DecompositionError::InvalidInput("m2 should be d x d in row-major order".into()));
+        }
+        self.open(mean.len())?;
+        let raw = self.raw;
+        with_ctx(|ctx| unsafe { ffi_ipca::petal_ipca_set_state(ctx, raw, n, mean.as_ptr(), m2.as_ptr()) }, || ())?;
+        self.dirty = true;
+        Ok(())
+    }
+    /// The model of the rows seen so far (solved once after each batch, on the first call): every accessor, `transform`,
+    /// `inverse_transform` and row score of `Pca`.  Nothing seen yet: the empty model of an unfitted `Pca`.
+    pub fn model(&mut self) -> Result<&Pca<A>, DecompositionError> {
+        if self.dirty && !self.raw.is_null() && self.n_samples_seen() > 0 {
+            let (k, d) = (self.model.n_components(), self.info()[0] as usize);
+            let mut comps = Array2::<A>::default((k, d));
+            let mut means = Array1::<A>::default(d);
+            let mut sing = Array1::<A>::default(k);
+            let mut tv = A::default();
+            let raw = self.raw;
+            with_ctx(
+                |ctx| unsafe {
+                    ffi_ipca::petal_ipca_finalize(ctx, raw, k as i64, comps.as_mut_ptr() as *mut c_void, means.as_mut_ptr() as *mut c_void,
+                        sing.as_mut_ptr() as *mut c_void, &mut tv as *mut A as *mut c_void)
+                },
+                || (),
+            )?;
+            self.model.components = comps;
+            self.model.means = means;
+            self.model.singular = sing;
+            self.model.total_variance = tv;
+            self.model.n_samples = self.n_samples_seen();
+            self.dirty = false;
+        }
+        Ok(&self.model)
+    }
+}
+impl<A: HipScalar> Drop for IncrementalPca<A> {
+    fn drop(&mut self) { unsafe { ffi_ipca::petal_ipca_destroy(self.raw) } }
 }
