@@ -1,6 +1,7 @@
 /* petal_hip_probe.h -- TEST AIDS: the fp64 small-matrix operations every fit rests on (Cholesky / triangular solves, the fp64 GEMM
  * forms, the symmetric eigen-solvers, the one-sided Jacobi SVD), each through an entry of its own, so that a test can hold one
- * kernel to a long-double reference instead of a whole fit to 1e-5.  Declared beside petal_hip.h, whose set of entry points mirrors
+ * kernel to a long-double reference instead of a whole fit to 1e-5 -- and, further down, the composite operations that steer the
+ * optimistic RandomizedPca fit (re-basing, the means fold).  Declared beside petal_hip.h, whose set of entry points mirrors
  * the crate's public interface one to one; nothing here is part of that interface, and there is no Rust binding.
  *
  * Every matrix argument is HOST memory, fp64, row-major, with an explicit leading dimension.  Each entry stages its inputs on the
@@ -44,6 +45,34 @@ int petal_probe_jacobi_svd_rows(petal_ctx* ctx, const double* A, int64_t L, int6
  * as they went in. */
 int petal_probe_dgemm(petal_ctx* ctx, int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const double* colscale);
+
+/* ---- the composite operations that steer the optimistic RandomizedPca fit, each called the way rpca_fit calls it ---------------------
+ * X (n x K, ldx) and mu (K values) are HOST memory in `dtype` (PETAL_F32 | PETAL_F64); X goes to the device the way a fit's input does
+ * (the row padding of PETAL_OPT_ROW_PAD included).  K and the column counts N / M are the PADDED extents a fit passes: multiples of 16.
+ * Every fp64 argument is as above; muT, mu0 and Z come back WIDENED to fp64 (exactly: they are values of `dtype`).  A sharded ctx is
+ * PETAL_INVALID_INPUT (these operations belong to the single-rank path). */
+
+/* op_power_pass_means: the first fused pass of a fit with the means pass folded in.  X: d real columns, columns d .. K - 1 zero.
+ * P (K x N, ldp; columns L .. N - 1 zero), L < N real columns.  *done: what the operation returned; 0 = nothing launched and EVERY
+ * output below still holds the NaN it was filled with -- except mu0.
+ *   Y (K x N, ldy), mu64 (K), muT (K: the means in dtype), *tv: the operation's results
+ *   mu0 (K): the provisional centre the pass was taken about -- the operation overwrites it with the true means, so the probe forms it
+ *            again with the operation's own first step (op_colmean over the same strided row sample) into a buffer of its own */
+int petal_probe_power_pass_means(petal_ctx* ctx, const void* X, int32_t dtype, int64_t n, int64_t K, int64_t d, int64_t ldx, const double* P,
+                                 int64_t N, int64_t ldp, int64_t L, int* done, double* Y, int64_t ldy, double* mu64, double* muT, double* mu0,
+                                 double* tv);
+
+/* One re-basing step: G (L x L, ldg; upper triangle read) = R^T R, P_out (K x M, ldpo) = A R^-1 (A: K x M, lda; columns L .. M - 1 of
+ * the result zero), Z (n x M, ldz) = (X - mu) P_out, Y (K x M, ldy) = (X - mu)^T Z.  mu nullable.  *ndead: in / out, as petal_probe_chol.
+ *   route 0  op_rebase_xp(p_planes, steering):                      P_out, Z         (*done = 1 always; Y is not touched)
+ *   route 1  op_rebase_power_pass(steering) without Z:              P_out, Y         (Z is not touched)
+ *   route 2  op_rebase_power_pass storing Z (never a steering pass): P_out, Z, Y
+ * Routes 1 and 2 hand the operation ONE device buffer as A and Y, as the fit does (its Yp).  *done = 0 (routes 1, 2): the operation
+ * returned false, nothing was launched, P_out / Z hold NaN, Y is NaN provided the buffer it shares with A still holds A bit for bit
+ * (otherwise what the device holds), and *ndead is as it came in.  p_planes: 2 or 3 (routes 1, 2: ignored). */
+int petal_probe_rebase(petal_ctx* ctx, const void* X, int32_t dtype, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* G,
+                       int64_t L, int64_t ldg, double rel_tol, const double* A, int64_t M, int64_t lda, int p_planes, int steering, int route,
+                       int* done, double* P_out, int64_t ldpo, double* Z, int64_t ldz, double* Y, int64_t ldy, int* ndead);
 
 #ifdef __cplusplus
 }

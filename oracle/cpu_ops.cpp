@@ -137,6 +137,19 @@ static double two_plane(double v) {
     const float f = float(v), h = bf(f), m = bf(f - h);
     return double(h) + double(m);
 }
+// the re-based iterate's rounding (hip_ops.hip: k_trsm_pack<NB, true>): both pieces rounded FROM THE fp64 VALUE, |result - v| <= 2^-17 |v|;
+// where the sum would not be a float32 number the second piece comes from float32(v) as in two_plane()
+static double rne8_f64(double v) {
+    uint64_t u; std::memcpy(&u, &v, 8);
+    u = (u + 0x00000FFFFFFFFFFFull + ((u >> 45) & 1ull)) & 0xFFFFE00000000000ull;
+    double r; std::memcpy(&r, &u, 8); return r;
+}
+static double two_plane_f64(double v) {
+    const double h = rne8_f64(v);
+    double m = rne8_f64(v - h);
+    if (double(float(h + m)) != h + m) m = rne8_f64(double(float(v)) - h);
+    return h + m;
+}
 void op_gemm_xp(Dev* d, int dt, const void* X, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* P0,
                 int64_t N, int64_t ldp0, const void* bias, void* Z, int64_t ldz, double* sumsq, int p_planes, bool steering) {
     const bool x2 = steering && p_planes == 2 && dt == F32 && d->gemm_mode == 0 && !sumsq && N > 80 && d->opt[OPT_STEERING] != 0;
@@ -534,10 +547,11 @@ void op_rebase_xp(Dev* d, int dt, const void* X, int64_t n, int64_t K, int64_t l
                   int64_t ldg, double rel_tol, int* ndead, const double* A, int64_t M, int64_t lda, double* T, int64_t ldt,
                   double* P_out, int64_t ldpo, void* Z, int64_t ldz, int p_planes, bool steering) {
     op_chol_inv(d, G, L, ldg, T, ldt, rel_tol, ndead, M);
-    if (dt == F32 && d->gemm_mode == 0 && p_planes == 2) {   // the two-plane iterate: P_out itself is rounded, every later use sees it
+    // the two-plane iterate where the device applies the factor in RT form (ops.h): P_out itself is rounded, every later use sees it
+    if (dt == F32 && d->gemm_mode == 0 && p_planes == 2 && L <= 140 && M % 16 == 0 && M <= 144) {
         op_dgemm(d, false, false, K, M, M, 1.0, A, lda, T, ldt, 0.0, P_out, ldpo);
         for (int64_t k = 0; k < K; ++k)
-            for (int64_t j = 0; j < M; ++j) P_out[k * ldpo + j] = two_plane(P_out[k * ldpo + j]);
+            for (int64_t j = 0; j < M; ++j) P_out[k * ldpo + j] = two_plane_f64(P_out[k * ldpo + j]);
         op_gemm_xp(d, dt, X, n, K, ldx, mu, P_out, M, ldpo, nullptr, Z, ldz, nullptr, 2, steering);
         return;
     }
@@ -586,15 +600,22 @@ bool op_power_pass(Dev* d, int dt, const void* X, int64_t n, int64_t K, int64_t 
 }
 bool op_power_pass_means(Dev* d, int dt, const void* X, int64_t n, int64_t K, int64_t dcols, int64_t ldx, double n_total, const double* P,
                          int64_t N, int64_t ldp, int64_t L, double* Y, int64_t ldy, double* mu64, void* muT, double* ssq_scratch, double* tv) {
-    const bool off = d->opt[OPT_MEANS_FOLD_ROWS] < 0;
+    const bool off = d->opt[OPT_MEANS_FOLD_ROWS] < 0 || d->opt[OPT_TWO_PLANE] == 0 || d->opt[OPT_TWO_PLANE_OMEGA] == 0;   // (the device's knobs)
     if (off || L >= N || !op_power_pass_applies(d, dt, X, n, K, ldx, muT, N)) return false;
-    // as on the device: a provisional centre from a strided row sample, the exact sums about it from the pass, then the move
+    // as on the device: a provisional centre mu0 from a strided row sample, the sums about it from the pass, then the move.  The sums
+    // are those of the operand product 2 reads (ops.h): in the steering form (k_pow3f) x - mu0 ROUNDED to two bf16 planes, otherwise
+    // the float32 x - mu0 itself (three planes re-add to it exactly); the sum of squares is taken before the rounding in both.
     const int64_t ns = std::min<int64_t>(n, 4096), stride = n / ns;
     op_colmean(d, dt, X, ns, K, ldx * stride, double(ns), mu64, muT, false);
+    const bool two = d->opt[OPT_STEERING] != 0;
     std::vector<double> sums(K, 0.0);
     double ssq = 0;
     for (int64_t i = 0; i < n; ++i)
-        for (int64_t f = 0; f < K; ++f) { const double v = centred(X, dt, i * ldx + f, muT, f); sums[f] += v; ssq += v * v; }
+        for (int64_t f = 0; f < K; ++f) {
+            const double v = centred(X, dt, i * ldx + f, muT, f);
+            sums[f] += two ? two_plane(v) : v;
+            ssq += v * v;
+        }
     if (!op_power_pass(d, dt, X, n, K, ldx, muT, P, N, ldp, nullptr, 0, Y, ldy, /*steering=*/true)) return false;   // (as on the device)
     std::vector<double> t(N, 0.0);
     double q = 0;
@@ -606,7 +627,7 @@ bool op_power_pass_means(Dev* d, int dt, const void* X, int64_t n, int64_t K, in
     }
     for (int64_t f = 0; f < K; ++f) {
         for (int64_t j = 0; j < N; ++j) Y[f * ldy + j] = j == N - 1 ? 0.0 : Y[f * ldy + j] - n_total * sums[f] * t[j];
-        mu64[f] += sums[f];
+        mu64[f] = ld(muT, dt, f) + sums[f];   // (about the centre that was subtracted: muT, not the fp64 mean it was rounded from)
         st(muT, dt, f, mu64[f]);
     }
     *ssq_scratch = ssq;
@@ -620,7 +641,7 @@ bool op_rebase_power_pass(Dev* d, int dt, const void* X, int64_t n, int64_t K, i
     op_chol_inv(d, G, L, ldg, T, ldt, rel_tol, ndead, M);
     op_dgemm(d, false, false, K, M, M, 1.0, A, lda, T, ldt, 0.0, P_out, ldpo);
     for (int64_t k = 0; k < K; ++k)
-        for (int64_t j = 0; j < M; ++j) P_out[k * ldpo + j] = two_plane(P_out[k * ldpo + j]);
+        for (int64_t j = 0; j < M; ++j) P_out[k * ldpo + j] = two_plane_f64(P_out[k * ldpo + j]);
     return op_power_pass(d, dt, X, n, K, ldx, mu, P_out, M, ldpo, Z, ldz, Y, ldy, steering);
 }
 void op_tail_verdict(Dev*, const double* lam, int64_t L, int64_t k, const double* mu_sq, int64_t dp, int64_t d, double n_total,

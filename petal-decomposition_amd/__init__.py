@@ -151,6 +151,10 @@ ABI_PROBE = [
     ("petal_probe_jacobi_svd_rows", C.c_int, [_P, _D, C.c_int64, C.c_int64, _D, C.c_int64, _D, _I]),
     ("petal_probe_dgemm", C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _D, C.c_int64, _D, C.c_int64,
                                     C.c_double, _D, C.c_int64, _D]),
+    ("petal_probe_power_pass_means", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _D, C.c_int64, C.c_int64,
+                                               C.c_int64, _I, _D, C.c_int64, _D, _D, _D, _D]),
+    ("petal_probe_rebase", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _D, C.c_int64, C.c_int64, C.c_double, _D,
+                                     C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _I, _D, C.c_int64, _D, C.c_int64, _D, C.c_int64, _I]),
 ]
 
 # every symbol include/petal_hip_sparse.h declares (RandomizedPca on sparse CSR data: an extension beyond the crate, kept apart from the
@@ -1590,3 +1594,55 @@ def probe_dgemm(ta, tb, M, N, K, alpha, a, b, beta, c, colscale=None, ctx: Optio
     ctx.check(ctx.lib.petal_probe_dgemm(ctx._h, int(bool(ta)), int(bool(tb)), M, N, K, float(alpha), _dp(aa), lda, _dp(bb), ldb, float(beta),
                                         _dp(c), ldc, _dp(cs) if cs is not None else None))
     return c
+
+
+def _data_2d(x):
+    """a 2-D float32 / float64 host array with unit column stride as it is (a row-sliced view keeps its leading dimension)"""
+    x = np.asarray(x)
+    if x.ndim != 2 or x.dtype not in (np.float32, np.float64):
+        raise InvalidInput("expected a 2-D float32 / float64 array")
+    es = x.dtype.itemsize
+    if x.shape[1] > 1 and x.strides[1] != es or x.strides[0] % es or x.strides[0] < es * x.shape[1]:
+        x = np.ascontiguousarray(x)
+    return x, (x.strides[0] // es if x.shape[0] > 1 else max(x.shape[1], 1)), (PETAL_F32 if x.dtype == np.float32 else PETAL_F64)
+
+
+def probe_power_pass_means(x, p, L, d=None, ctx: Optional[Context] = None):
+    """petal_probe_power_pass_means: x (n x K, K a multiple of 16; columns d .. K - 1 zero), p (K x N float64).  Returns a dict:
+    done, y (K x N), mu64, muT, mu0 (K each, float64; muT and mu0 hold values of x's dtype), tv."""
+    ctx = ctx or default_context()
+    x, ldx, dt = _data_2d(x)
+    pp, ldp = _f64_2d(p)
+    n, K = x.shape
+    N = pp.shape[1]
+    if pp.shape[0] != K:
+        raise InvalidInput(f"p should have {K} rows")
+    y = np.full((K, N), np.nan)
+    mu64, muT, mu0, tv = np.full(K, np.nan), np.full(K, np.nan), np.full(K, np.nan), np.full(1, np.nan)
+    done = C.c_int(-1)
+    ctx.check(ctx.lib.petal_probe_power_pass_means(ctx._h, x.ctypes.data, dt, n, K, int(K if d is None else d), ldx, _dp(pp), N, ldp, int(L),
+                                                   C.byref(done), _dp(y), N, _dp(mu64), _dp(muT), _dp(mu0), _dp(tv)))
+    return {"done": done.value, "y": y, "mu64": mu64, "muT": muT, "mu0": mu0, "tv": float(tv[0])}
+
+
+def probe_rebase(x, mu, g, a, rel_tol=1e-15, p_planes=2, steering=False, route=0, ndead_in=0, ctx: Optional[Context] = None):
+    """petal_probe_rebase: x (n x K), mu (K, or None), g (L x L float64), a (K x M float64).  Returns a dict: done, p_out (K x M),
+    z (n x M float64, None on route 1), y (K x M, None on route 0), ndead."""
+    ctx = ctx or default_context()
+    x, ldx, dt = _data_2d(x)
+    gg, ldg = _f64_2d(g)
+    aa, lda = _f64_2d(a)
+    n, K = x.shape
+    L, M = gg.shape[0], aa.shape[1]
+    if aa.shape[0] != K:
+        raise InvalidInput(f"a should have {K} rows")
+    muh = _host(mu, dt, (K,)) if mu is not None else None
+    p_out = np.full((K, M), np.nan)
+    z = np.full((n, M), np.nan) if route != 1 else None
+    y = np.full((K, M), np.nan) if route != 0 else None
+    done, nd = C.c_int(-1), C.c_int(int(ndead_in))
+    ctx.check(ctx.lib.petal_probe_rebase(ctx._h, x.ctypes.data, dt, n, K, ldx, muh.ctypes.data if muh is not None else None, _dp(gg), L, ldg,
+                                         float(rel_tol), _dp(aa), M, lda, int(p_planes), int(bool(steering)), int(route), C.byref(done),
+                                         _dp(p_out), M, _dp(z) if z is not None else None, M, _dp(y) if y is not None else None, M,
+                                         C.byref(nd)))
+    return {"done": done.value, "p_out": p_out, "z": z, "y": y, "ndead": nd.value}

@@ -2143,6 +2143,116 @@ void probe_dgemm(petal_ctx& c, bool ta, bool tb, int64_t M, int64_t N, int64_t K
         for (int64_t j = 0; j < (i < M - 1 ? ldc : N); ++j) C[i * ldc + j] = ch[size_t(i) * ldc + j];
 }
 
+// ---- the composite operations of the optimistic fit (first_products / power_iterations), one call each ---------------------------------
+namespace {
+
+// the host matrix as a fit's input: ingest() gives it the layout (padding, row pitch) the fit's kernels stream
+DevMat probe_ingest(petal_ctx& c, const void* X, int dtype, int64_t n, int64_t K, int64_t ldx) {
+    petal_matrix m{};
+    m.data = const_cast<void*>(X);
+    m.rows = n; m.cols = K; m.row_stride = ldx; m.col_stride = 1;
+    m.dtype = dtype; m.space = PETAL_HOST;
+    return ingest(c, m);
+}
+// a device buffer of `count` values of dtype, every one NaN (all bits set)
+DBuf probe_nan_dt(petal_ctx& c, int dt, size_t count) {
+    DBuf d(c.dev, dtype_size(dt) * count);
+    dev_memset(c.dev, d.p, 0xFF, d.bytes);
+    return d;
+}
+// rows x cols values of dtype (device, leading dimension ldd) widened into a host fp64 matrix
+void probe_fetch_dt(petal_ctx& c, int dt, const void* dev, int64_t rows, int64_t cols, int64_t ldd, double* h, int64_t ldh) {
+    std::vector<char> s(dtype_size(dt) * size_t(rows) * ldd);
+    dev_d2h(c.dev, s.data(), dev, s.size());
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < rows; ++i)
+        for (int64_t j = 0; j < cols; ++j) h[i * ldh + j] = get_elem(s.data(), dt, i * ldd + j);
+}
+void probe_data_shape(const petal_ctx& c, const void* X, int dtype, int64_t n, int64_t K, int64_t ldx, const char* who) {
+    if (sharded(c)) invalid_input(std::string(who) + ": a single-rank operation");
+    if (!X || (dtype != F32 && dtype != F64) || n < 1 || n > (int64_t(1) << 22) || K < 16 || K > 4096 || K % 16 != 0 || ldx < K)
+        invalid_input(std::string(who) + ": X should be n x K in f32 / f64, K a multiple of 16, ldx >= K");
+}
+
+}  // namespace
+
+void probe_power_pass_means(petal_ctx& c, const void* X, int dtype, int64_t n, int64_t K, int64_t d, int64_t ldx, const double* P, int64_t N,
+                            int64_t ldp, int64_t L, int* done, double* Y, int64_t ldy, double* mu64, double* muT, double* mu0, double* tv) {
+    probe_data_shape(c, X, dtype, n, K, ldx, "probe_power_pass_means");
+    if (d < 1 || d > K || N < 16 || N > 2048 || N % 16 != 0 || L < 1 || L > N || ldp < N || ldy < N)
+        invalid_input("probe_power_pass_means: bad column counts or leading dimension");
+    const Timer timer = start_fit(c, petal_matrix{const_cast<void*>(X), n, K, ldx, 1, dtype, PETAL_HOST});
+    DevMat Xd = probe_ingest(c, X, dtype, n, K, ldx);
+    DBuf Pd = probe_stage(c, P, K, N, ldp, N, 0.0);
+    DBuf Yd = probe_nan(c, size_t(K) * N);
+    DBuf mu = probe_nan(c, size_t(K) + 2);                 // [means | tv, scratch], as the fit's result block lays them out
+    DBuf muTd = probe_nan_dt(c, dtype, size_t(K));
+    dev_set_tag(c.dev, TAG_POW);
+    const bool ok = op_power_pass_means(c.dev, dtype, Xd.p, n, K, d, Xd.ld, double(n), Pd.f64(), N, N, L, Yd.f64(), N, mu.f64(), muTd.p,
+                                        mu.f64() + K + 1, mu.f64() + K);
+    dev_set_tag(c.dev, TAG_NONE);
+    *done = ok ? 1 : 0;
+    probe_fetch(c, Yd, K, N, N, Y, ldy);
+    std::vector<double> t(size_t(K) + 2);
+    probe_fetch(c, mu, 1, K + 2, K + 2, t.data(), K + 2);
+    std::copy(t.begin(), t.begin() + K, mu64);
+    *tv = t[size_t(K)];
+    probe_fetch_dt(c, dtype, muTd.p, 1, K, K, muT, K);
+    // the provisional centre again, by the operation's own first step (ops.h: the means of a strided sample of the rows)
+    const int64_t ns = std::min<int64_t>(n, 4096), stride = n / ns;
+    DBuf m0 = probe_nan(c, size_t(K));
+    DBuf m0T = probe_nan_dt(c, dtype, size_t(K));
+    op_colmean(c.dev, dtype, Xd.p, ns, K, Xd.ld * stride, double(ns), m0.f64(), m0T.p, false);
+    probe_fetch_dt(c, dtype, m0T.p, 1, K, K, mu0, K);
+    finish_stats(c, timer);
+}
+
+void probe_rebase(petal_ctx& c, const void* X, int dtype, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* G, int64_t L,
+                  int64_t ldg, double rel_tol, const double* A, int64_t M, int64_t lda, int p_planes, bool steering, int route, int* done,
+                  double* P_out, int64_t ldpo, double* Z, int64_t ldz, double* Y, int64_t ldy, int* ndead) {
+    probe_data_shape(c, X, dtype, n, K, ldx, "probe_rebase");
+    if (M < 16 || M > 2048 || M % 16 != 0 || L < 1 || L > M || ldg < L || lda < M || ldpo < M || route < 0 || route > 2 ||
+        (p_planes != 2 && p_planes != 3) || !(rel_tol >= 0) || (route != 1 && (!Z || ldz < M)) || (route != 0 && (!Y || ldy < M)))
+        invalid_input("probe_rebase: bad order, column count, leading dimension, route, planes or tolerance");
+    const Timer timer = start_fit(c, petal_matrix{const_cast<void*>(X), n, K, ldx, 1, dtype, PETAL_HOST});
+    DevMat Xd = probe_ingest(c, X, dtype, n, K, ldx);
+    const size_t esz = dtype_size(dtype);
+    DBuf muT;
+    if (mu) { muT = DBuf(c.dev, esz * size_t(K)); dev_h2d(c.dev, muT.p, mu, muT.bytes); }
+    DBuf Gd = probe_stage(c, G, L, L, ldg, M, std::numeric_limits<double>::quiet_NaN());   // (only the L x L block is the operation's to read)
+    DBuf Ad = probe_stage(c, A, K, M, lda, M, 0.0);
+    DBuf T = probe_nan(c, size_t(M) * M), Pd = probe_nan(c, size_t(K) * M);
+    DBuf Zd = probe_nan_dt(c, dtype, size_t(n) * M);
+    DBuf nd = probe_int(c, *ndead);
+    bool ok = true;
+    if (route == 0) {
+        dev_set_tag(c.dev, TAG_XP);
+        op_rebase_xp(c.dev, dtype, Xd.p, n, K, Xd.ld, mu ? muT.p : nullptr, Gd.f64(), L, M, rel_tol, nd.as<int>(), Ad.f64(), M, M, T.f64(), M,
+                     Pd.f64(), M, Zd.p, M, p_planes, steering);
+    } else {
+        dev_set_tag(c.dev, TAG_POW);   // (A and Y: the fit's Yp, one buffer)
+        ok = op_rebase_power_pass(c.dev, dtype, Xd.p, n, K, Xd.ld, mu ? muT.p : nullptr, Gd.f64(), L, M, rel_tol, nd.as<int>(), Ad.f64(), M, M,
+                                  T.f64(), M, Pd.f64(), M, route == 2 ? Zd.p : nullptr, M, Ad.f64(), M, steering && route == 1);
+    }
+    dev_set_tag(c.dev, TAG_NONE);
+    *done = ok ? 1 : 0;
+    probe_fetch(c, Pd, K, M, M, P_out, ldpo);
+    if (route != 1) probe_fetch_dt(c, dtype, Zd.p, n, M, M, Z, ldz);
+    if (route != 0) {
+        // Y shares its device buffer with A.  A refused call must have left it as staged: only then does the caller see NaN, otherwise
+        // what the device holds
+        probe_fetch(c, Ad, K, M, M, Y, ldy);
+        bool untouched = !ok;
+        for (int64_t i = 0; untouched && i < K; ++i)
+            untouched = std::memcmp(Y + i * ldy, A + i * lda, sizeof(double) * size_t(M)) == 0;
+        if (untouched)
+            for (int64_t i = 0; i < K; ++i)
+                for (int64_t j = 0; j < M; ++j) Y[i * ldy + j] = std::numeric_limits<double>::quiet_NaN();
+    }
+    *ndead = probe_int_back(c, nd);
+    finish_stats(c, timer);
+}
+
 // ---------------------------------------------------------------------------------------------
 // RandomizedPca on sparse CSR data (include/petal_hip_sparse.h; an extension beyond the crate).  The range finder (pca.rs:689-718) needs
 // only X . P and X^T . Z; the centring stays implicit (Xc P = X P - 1 (mu^T P), Xc^T Z = X^T Z - mu (1^T Z)), so X is never densified.

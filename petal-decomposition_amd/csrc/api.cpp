@@ -474,4 +474,35 @@ int petal_probe_dgemm(petal_ctx* ctx, int ta, int tb, int64_t M, int64_t N, int6
     });
 }
 
+int petal_probe_power_pass_means(petal_ctx* ctx, const void* X, int32_t dtype, int64_t n, int64_t K, int64_t d, int64_t ldx, const double* P,
+                                 int64_t N, int64_t ldp, int64_t L, int* done, double* Y, int64_t ldy, double* mu64, double* muT, double* mu0,
+                                 double* tv) {
+    return guarded(ctx, [&] {
+        need(X, "X");
+        need(P, "P");
+        need(done, "done");
+        need(Y, "Y");
+        need(mu64, "mu64");
+        need(muT, "muT");
+        need(mu0, "mu0");
+        need(tv, "tv");
+        probe_power_pass_means(*ctx, X, dtype, n, K, d, ldx, P, N, ldp, L, done, Y, ldy, mu64, muT, mu0, tv);
+    });
+}
+
+int petal_probe_rebase(petal_ctx* ctx, const void* X, int32_t dtype, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* G,
+                       int64_t L, int64_t ldg, double rel_tol, const double* A, int64_t M, int64_t lda, int p_planes, int steering, int route,
+                       int* done, double* P_out, int64_t ldpo, double* Z, int64_t ldz, double* Y, int64_t ldy, int* ndead) {
+    return guarded(ctx, [&] {
+        need(X, "X");
+        need(G, "G");
+        need(A, "A");
+        need(done, "done");
+        need(P_out, "P_out");
+        need(ndead, "ndead");
+        probe_rebase(*ctx, X, dtype, n, K, ldx, mu, G, L, ldg, rel_tol, A, M, lda, p_planes, steering != 0, route, done, P_out, ldpo, Z, ldz, Y,
+                     ldy, ndead);
+    });
+}
+
 }  // extern "C"

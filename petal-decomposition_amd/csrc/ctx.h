@@ -175,5 +175,11 @@ void probe_eigh(petal_ctx& c, const double* A, int64_t L, int64_t lda, double to
 void probe_jacobi_svd_rows(petal_ctx& c, const double* A, int64_t L, int64_t lda, double* U, int64_t ldu, double* s_inv, int* nonconv);
 void probe_dgemm(petal_ctx& c, bool ta, bool tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
                  const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const double* colscale);
+// ... and the composite operations that steer the optimistic fit (op_power_pass_means; op_rebase_xp / op_rebase_power_pass)
+void probe_power_pass_means(petal_ctx& c, const void* X, int dtype, int64_t n, int64_t K, int64_t d, int64_t ldx, const double* P, int64_t N,
+                            int64_t ldp, int64_t L, int* done, double* Y, int64_t ldy, double* mu64, double* muT, double* mu0, double* tv);
+void probe_rebase(petal_ctx& c, const void* X, int dtype, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* G, int64_t L,
+                  int64_t ldg, double rel_tol, const double* A, int64_t M, int64_t lda, int p_planes, bool steering, int route, int* done,
+                  double* P_out, int64_t ldpo, double* Z, int64_t ldz, double* Y, int64_t ldy, int* ndead);
 
 }  // namespace petal

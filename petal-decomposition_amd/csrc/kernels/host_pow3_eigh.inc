@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void k_mean_fix(double* __restrict__ Y, int K,
         for (int h = 128; h > 0; h >>= 1) { if (tid < h) sr[tid] += sr[tid + h]; __syncthreads(); }
         if (tid == 0) tv[0] = fmax(sr[0] - n_total * q2, 0.0);
         for (int f = tid; f < K; f += 256) {
-            const double m = mu64[f] + sd[f];
+            const double m = (double)muT[f] + sd[f];   // (about the centre the pass SUBTRACTED: the float32 one, not the fp64 mean it was rounded from)
             mu64[f] = m;
             muT[f] = (float)m;
         }

@@ -35,7 +35,9 @@ __device__ __forceinline__ bf16x8 lds_tr2(const unsigned char* a0, const unsigne
 __device__ __forceinline__ int pow3_xoff(int row, int ch) { return row * 128 + 16 * (ch ^ ((2 * ((row >> 1) & 3)) ^ (row & 1))); }
 // MEANS (the FIRST pass of a fit, round 5): `mu` is only a provisional centre mu0 (the means of a strided row sample), and the pass
 // gathers what the separate means pass used to: the LAST column of the last tile -- zero padding of P, so z is 0 there -- is set
-// to 1 for every valid row, which makes Y'[:, 16 NT - 1] = Xc0^T 1 the column sums about mu0 (product 2 forms them for free), and
+// to 1 for every valid row, which makes Y'[:, 16 NT - 1] = Xc0^T 1 the column sums about mu0 (product 2 forms them for free) -- the
+// sums of the operand PRODUCT 2 READS, in fp32 per slab: here the three planes that re-add to fl32(x - mu0), in k_pow3f the TWO-plane
+// rounding of it (a bias of up to 2^-17 mean |x - mu0| per column on data of few distinct values: ops.h states the contract) -- and
 // the splits accumulate sum (x - mu0)^2 over the valid rows (one partial per wave in ssq_part).  k_mean_fix then moves everything
 // to the true centre mu = mu0 + delta, delta = sums / n:  Xc^T Xc P = Xc0^T Xc0 P - n delta (delta^T P),  sum (x - mu)^2 = ssq - n |delta|^2
 // -- a rank-one correction of relative size (delta / sigma)^2, i.e. harmless, where the same identity about mu0 = 0 would cancel
@@ -368,7 +370,8 @@ __global__ __launch_bounds__(512) void k_pow3(const float* __restrict__ X, int64
 #endif
 // MEANS: as k_pow3's (the first pass of a fit about a provisional centre: the last column of z set to one gathers the column sums, the
 // splits accumulate sum (x - mu0)^2 -- from the values BEFORE their rounding; the sums themselves are those of the 16-bit values, off the
-// exact ones by 2^-17 sigma / sqrt(n) per column: 1e-8 sigma at the 200000 rows the fold starts from).
+// exact ones by 2^-17 sigma / sqrt(n) per column on continuous data: 1e-8 sigma at the 200000 rows the fold starts from -- and by up
+// to 2^-17 mean |x - mu0|, whatever n, on columns of few distinct values, where equal values round alike: ops.h, op_power_pass_means).
 template <int NT, bool CENTER, bool MEANS = false, int FC = 2>
 __global__ __launch_bounds__(512) void k_pow3f(const float* __restrict__ X, int64_t n, int64_t ldx, const float* __restrict__ mu,
                                                const bf16x8* __restrict__ Ppk3, int NTtot, float* __restrict__ part, int64_t nstages,

@@ -105,6 +105,21 @@ __host__ __device__ inline size_t trsm_lds_bytes(int M) { return sizeof(double) 
 // P_out too -- the re-based iterate may be any basis of range(A), so this rounding defines the iterate instead of perturbing a
 // product (numpy model, configs[1] / configs[3] spectra: no change in the 5e-6 / 1.5e-5 component errors), and the next product
 // needs five piece products instead of six (k_xp3<..., NPL = 2>).  The third plane is not written.
+// Both pieces are rounded (to nearest, ties to even) FROM THE fp64 VALUE, h = bf16(p), m = bf16(p - h) with p - h exact in fp64, so that
+// |P - p| <= 2^-17 |p|: through float32 first the conversion's 2^-24 |p| came on top (one element in some 25000 was up to 1.004 x
+// 2^-17 off).  Where h + m would not be a float32 number (|p - h| below the float32 resolution of p: m then carries nothing the next
+// product could read) m is taken from float32(p) - h instead, as before; the error there is below 2^-22 |p|.
+__device__ __forceinline__ double rne8_f64(double v) {   // v to 8 significant bits (a bf16 number for every |v| in the float32 range)
+    unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    u = (u + 0x00000FFFFFFFFFFFull + ((u >> 45) & 1ull)) & 0xFFFFE00000000000ull;
+    return __longlong_as_double((long long)u);
+}
+__device__ __forceinline__ void two_plane_f64(double v, double& hd, double& md) {
+    hd = rne8_f64(v);
+    md = rne8_f64(v - hd);
+    const double p = hd + md;
+    if ((double)(float)p != p) md = rne8_f64((double)(float)v - hd);
+}
 template <int NB, bool P2 = false>   // NB = M / 16 at compile time: straight-line code, so every operand load is issued ahead of the MFMA chain
 __global__ __launch_bounds__(64) void k_trsm_pack(const double* __restrict__ A, int64_t lda, const double* __restrict__ RT, int64_t ldt,
                                                   int64_t K, double* __restrict__ P_out, int64_t ldpo,
@@ -159,28 +174,31 @@ __global__ __launch_bounds__(64) void k_trsm_pack(const double* __restrict__ A, 
     if (pk3) {
         for (int idx = lane; idx < 2 * M; idx += 64) {   // item = 8 rows (group g) of column col
             const int g = idx / M, col = idx - g * M;
-            f32x8 x;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = (float)sP[(8 * g + e) * ldsp + col];
             bf16x8 h, m, l;
-            split3(x, h, m, l);
+            if (P2) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    double hd, md;
+                    two_plane_f64(sP[(8 * g + e) * ldsp + col], hd, md);
+                    h[e] = (__bf16)(float)hd;
+                    m[e] = (__bf16)(float)md;
+                    if (P_out) P_out[(i0 + 8 * g + e) * ldpo + col] = hd + md;
+                }
+            } else {
+                f32x8 x;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) x[e] = (float)sP[(8 * g + e) * ldsp + col];
+                split3(x, h, m, l);
+            }
             const int64_t c = i0 >> 5, tile = c * NTtot + (col >> 4);
             const int ln = (col & 15) + 16 * (int)(((i0 & 31) + 8 * g) >> 3);
             pk3[(tile * 3 + 0) * 64 + ln] = h;
             pk3[(tile * 3 + 1) * 64 + ln] = m;
-            if (P2) {
-                if (P_out) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) P_out[(i0 + 8 * g + e) * ldpo + col] = (double)(float)h[e] + (double)(float)m[e];
-                }
-            } else
-            pk3[(tile * 3 + 2) * 64 + ln] = l;
+            if (!P2) pk3[(tile * 3 + 2) * 64 + ln] = l;
             if ((K & 31) == 16 && i0 + 16 == K) {   // half-empty last chunk: zero operand groups for the rows that do not exist
                 bf16x8 z; for (int e = 0; e < 8; ++e) z[e] = (__bf16)0.0f;
 #pragma unroll
                 for (int pl = 0; pl < (P2 ? 2 : 3); ++pl) pk3[(tile * 3 + pl) * 64 + ln + 32] = z;
-                if (P2 && P_out) {   // (those rows do not exist in P_out)
-                }
             }
         }
     }

@@ -206,8 +206,10 @@ bool op_ipca_merge(Dev*, int64_t dp, double n_a, double* M2_a, const double* mea
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.
-// p_planes = 2: P_out may be ROUNDED to the sum of its two leading bf16 pieces (in P_out itself and in the product's operand) where
-// that saves a piece product; 3: P_out is the re-based iterate to fp64 / fp32 accuracy.
+// p_planes = 2 (fp32 data, split-product mode): where the factor is applied in RT form (L <= 140, M a multiple of 16 <= 144) P_out IS
+// ROUNDED to the sum of its two leading bf16 pieces -- both rounded from the fp64 value: |P_out - A R^-1| <= 2^-17 |A R^-1| -- in P_out
+// itself and in the product's operand, which saves a piece product; where the explicit inverse is formed (larger L or M) it is NOT
+// rounded and the product reads float32(P_out) on three planes.  3, fp64 data, the fp32-MFMA mode: the iterate to fp64 accuracy.
 void op_rebase_xp(Dev*, int dtype, const void* X, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* G, int64_t L,
                   int64_t ldg, double rel_tol, int* ndead, const double* A, int64_t M, int64_t lda, double* T, int64_t ldt,
                   double* P_out, int64_t ldpo, void* Z, int64_t ldz, int p_planes = 2, bool steering = false);
@@ -223,9 +225,18 @@ bool op_power_pass(Dev*, int dtype, const void* X, int64_t n, int64_t K, int64_t
                    void* Z, int64_t ldz, double* Y, int64_t ldy, bool steering = false);
 // The FIRST fused pass of a fit with the means pass folded in (single rank, fp32, centring; L < N: a padding column is free):
 // mu64 / muT come back as the column means of X (d real columns of K), *tv as sum (X - mean)^2, and Y = Xc^T (Xc P) about that
-// mean -- X is read once, not twice: the kernel centres about the means of a row SAMPLE, gathers the exact column sums and the sum
-// of squares about that provisional centre in the same pass, and a one-workgroup kernel moves Y, the means and the variance to the
-// true centre (a rank-one correction of relative size (delta / sigma)^2).  ssq_scratch: one device double.  False: nothing done.
+// mean -- X is read once, not twice: the kernel centres about the means mu0 of a row SAMPLE (every (n / 4096)-th row, 4096 of them),
+// gathers the column sums and the sum of squares about that provisional centre in the same pass, and a one-workgroup kernel moves Y,
+// the means and the variance to the true centre (a rank-one correction of relative size (delta / sigma)^2).
+// THE CONTRACT of the folded sums (tests/rebase_cases.py, table C, holds the device and the host simulation to it): they are the sums of
+// the operand product 2 reads, accumulated in fp32 inside a workgroup's slab and in fp64 across slabs.  In the steering form (k_pow3f,
+// PETAL_OPT_STEERING on: the default) that operand is fl32(x - mu0) ROUNDED TO TWO bf16 PLANES, so with a_f = mean_i |x_if - mu0_f|
+//     |mu64_f - mean_f| <= 2^-17 a_f + 2^-24 (rows per workgroup) a_f
+// and on columns of few distinct values (binary, counts) the first term is a BIAS that does not shrink with n: equal values round
+// alike.  With PETAL_OPT_STEERING off (k_pow3<.., MEANS>: three planes re-add to fl32(x - mu0)) the first term is absent.  Neither
+// is "exact"; both are far below the 1e-5 of a column's spread a fit is held to.  *tv = sum fl32(x - mu0)^2 - n |delta|^2 with the
+// squares taken BEFORE the rounding and added per lane in fp32 over all stages of a workgroup: its error grows with the rows per
+// workgroup (DESIGN.md section 4 has the bound and the measured figures).  ssq_scratch: one device double.  False: nothing done.
 bool op_power_pass_means(Dev*, int dtype, const void* X, int64_t n, int64_t K, int64_t d, int64_t ldx, double n_total, const double* P,
                          int64_t N, int64_t ldp, int64_t L, double* Y, int64_t ldy, double* mu64, void* muT, double* ssq_scratch, double* tv);
 // the same behind one re-basing step (arguments as op_rebase_xp, p_planes = 2): P_out = A R^-1 rounded, then the fused pass with it

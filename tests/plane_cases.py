@@ -180,6 +180,20 @@ _ELEMENT_MUTANTS = MUTANTS[:9]      # (those that act on one element's terms alo
 
 
 # ------------------------------------------------------------------------------------------- one product and its certificate
+def piece_sums(au, av, nu, nv):
+    """(S, D, T) of out = U^T V from the magnitudes au / av and the non-zero indicators nu / nv of the operands' three pieces (float64,
+    t x a and t x b each): S = sum |kept piece products|, D = sum |dropped piece products|, T = the number of non-zero kept ones"""
+    S = au[0].T @ (av[0] + av[1] + av[2]) + au[1].T @ (av[0] + av[1]) + au[2].T @ av[0]
+    D = au[1].T @ av[2] + au[2].T @ (av[1] + av[2])
+    T = nu[0].T @ (nv[0] + nv[1] + nv[2]) + nu[1].T @ (nv[0] + nv[1]) + nu[2].T @ nv[0]
+    return S, D, T
+
+
+def bounded_class_bound(S, T):
+    """the derived bound of the bounded class: the three dropped pieces of weight 2^-24 and T terms of worst-case fp32 accumulation"""
+    return (3.0 + T) * 2.0 ** -24 * S
+
+
 class Product:
     """out[a, b] = sum_t U[t, a] V[t, b] (+ bias[b]) by the kept piece products of U on pu planes and V on pv planes.  U (T x A) and
     V (T x B) hold only the t that matter (tlab: their original indices; alab: the original indices of the a axis).  kaxis: the axis of
@@ -204,9 +218,7 @@ class Product:
         au, av = [np.abs(p).astype(f8) for p in up], [np.abs(p).astype(f8) for p in vp]
         nu, nv = [(p != 0).astype(f8) for p in up], [(p != 0).astype(f8) for p in vp]
         ref = ur.astype(f8).T @ vr.astype(f8)
-        S = au[0].T @ (av[0] + av[1] + av[2]) + au[1].T @ (av[0] + av[1]) + au[2].T @ av[0]
-        D = au[1].T @ av[2] + au[2].T @ (av[1] + av[2])
-        T = nu[0].T @ (nv[0] + nv[1] + nv[2]) + nu[1].T @ (nv[0] + nv[1]) + nu[2].T @ nv[0]
+        S, D, T = piece_sums(au, av, nu, nv)
         # q[a, b] = the smallest granularity among the element's non-zero terms (every piece of an operand is a multiple of the
         # operand's own lowest set bit): a (min, x) product, one t at a time over the columns that t reaches
         gu, gv = gran(ur), gran(vr)
@@ -223,7 +235,7 @@ class Product:
             q = np.minimum(q, gran(b)[None, :])
         exact = (D == 0) & (S * (1 + 1e-12) < 2.0 ** 24 * q)
         assert 2 * np.count_nonzero(exact) >= exact.size, f"{self.name}: fewer than half of the elements are in the exact class"
-        self._a = {"ref": ref, "S": S, "T": T, "q": q, "exact": exact, "bound": (3.0 + T) * 2.0 ** -24 * S, "up": up, "vp": vp, "ur": ur, "vr": vr}
+        self._a = {"ref": ref, "S": S, "T": T, "q": q, "exact": exact, "bound": bounded_class_bound(S, T), "up": up, "vp": vp, "ur": ur, "vr": vr}
         return self._a
 
     def ref_longdouble(self, ai, bi):
