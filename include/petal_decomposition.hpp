@@ -25,6 +25,7 @@
 #include "petal_hip_segments.h"
 #include "petal_hip_sparse.h"
 #include "petal_hip_ipca.h"
+#include "petal_hip_wide.h"
 
 namespace petal_decomposition {
 
@@ -141,6 +142,15 @@ class Context {
         throw DecompositionError(rc == PETAL_INVALID_INPUT ? DecompositionError::InvalidInput : DecompositionError::LinalgError, msg);
     }
     static Context& global() { static Context c; return c; }
+    // petal_ctx_set_option / petal_ctx_get_option with a PETAL_OPT_* number.  Added for PETAL_OPT_PCA_DUAL / PETAL_OPT_PCA_DUAL_FALLBACK
+    // (petal_hip_wide.h), but GENERAL: every option of petal_hip.h and its extension headers goes through the same pair, as in the Python
+    // Context.  An extension beyond the crate, which has no options.
+    void set_option(int option, double value) { check(petal_ctx_set_option(ctx_, option, value)); }
+    double get_option(int option) const {
+        double v = 0;
+        if (petal_ctx_get_option(ctx_, option, &v) != PETAL_OK) throw DecompositionError(DecompositionError::InvalidInput, "unknown ctx option");
+        return v;
+    }
 
   private:
     petal_ctx* ctx_ = nullptr;
@@ -238,6 +248,14 @@ struct PcaState {  // src/pca.rs:41-51 / 317-329
 };
 }  // namespace detail
 
+// Facts of the last exact Pca fit on a ctx (petal_hip_wide.h: an extension beyond the crate): dual = the n x n row-Gram route of wide
+// data (not sharded, n < d, d > 2048; PETAL_OPT_PCA_DUAL forces or forbids it), kernel = k_row_gram ran, the order of the eigenproblem,
+// the feature chunks of the row-Gram launch.
+struct PcaRoute {
+    bool dual = false, kernel = false;
+    int64_t order = 0, chunks = 0;
+};
+
 template <class A>
 class Pca {  // src/pca.rs:41-232
   public:
@@ -265,6 +283,14 @@ class Pca {  // src/pca.rs:41-232
     std::vector<A> reconstruction_error(const Array2<A>& input) const { return st_.reconstruction_error(input); }
     std::vector<A> hotelling_t2(const Array2<A>& input) const { return st_.hotelling_t2(input); }
     std::vector<A> score_samples(const Array2<A>& input) const { return st_.score_samples(input); }
+    // extension beyond the crate (petal_hip_wide.h): which route the last exact fit on this model's ctx took
+    PcaRoute last_route() const {
+        int64_t v[4] = {0, 0, 0, 0};
+        st_.context().check(petal_pca_last_route(st_.context().get(), v));
+        PcaRoute r;
+        r.dual = v[0] != 0; r.kernel = v[1] != 0; r.order = v[2]; r.chunks = v[3];
+        return r;
+    }
 
   private:
     void inner_fit(const Array2<A>& input, Array2<A>* y) {

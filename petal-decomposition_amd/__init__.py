@@ -31,7 +31,8 @@ GEMM_SPLIT_BF16X3, GEMM_FP32_MFMA, GEMM_SPLIT_BF16X3_EXACT = 0, 1, 2
 OPTIONS = {"two_plane_operands": 0, "two_plane_omega": 1, "two_plane_iterate": 2, "steering_passes": 3, "fused_pass": 4,
            "fused_pass_min_rows": 5, "verdict_threshold": 6, "means_fold_rows": 7, "gram_split": 8, "gram_split_hook": 9,
            "d2h_kernel": 10, "row_pad": 11, "eigh_jacobi": 12, "poison": 13, "force_collective": 14, "steering_hook": 15,
-           "ipca_fallback": 32}   # (32: PETAL_OPT_IPCA_FALLBACK, include/petal_hip_ipca.h -- a test aid)
+           "ipca_fallback": 32,   # (32: PETAL_OPT_IPCA_FALLBACK, include/petal_hip_ipca.h -- a test aid)
+           "pca_dual": 33, "pca_dual_fallback": 34}   # (PETAL_OPT_PCA_DUAL, PETAL_OPT_PCA_DUAL_FALLBACK: include/petal_hip_wide.h)
 ICA_TEXTBOOK, ICA_REFERENCE_LITERAL = 0, 1
 # the contrast function of the FastICA iteration: bits 4-7 of the same `mode` argument (include/petal_hip.h); EXP and CUBE are an
 # extension beyond the crate, whose only contrast is logcosh
@@ -186,6 +187,12 @@ ABI_IPCA = [
 ]
 IPCA_KERNEL_MAX_D = 1024   # PETAL_IPCA_KERNEL_MAX_D
 
+# every symbol include/petal_hip_wide.h declares (exact Pca on wide data: the dual route's facts and its row Gram matrix by itself)
+ABI_WIDE = [
+    ("petal_pca_last_route", C.c_int, [_P, _L]),
+    ("petal_row_gram", C.c_int, [_P, _M, _D, _D, _L]),
+]
+
 
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
@@ -203,7 +210,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -212,7 +219,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -591,6 +598,21 @@ def csr_gemm(x: "CsrMatrix", p, transposed: bool = False, a=None, s=None):
     return out
 
 
+def row_gram(x, centre=None, ctx: Optional["Context"] = None, want_info: bool = False):
+    """Test aid (``petal_row_gram``, include/petal_hip_wide.h): the float64 row Gram matrix ``(x - centre) @ (x - centre).T`` of exact
+    Pca's dual route, ``x`` widened to float64 before ``centre`` (d float64 values, or None) is subtracted.  ``x``: numpy or a
+    ``torch.cuda`` tensor, any strides.  ``want_info``: also returns ``{"kernel": k_row_gram ran, "chunks": feature chunks}``."""
+    keep = []
+    mx = describe(x, keep)
+    ctx = ctx or default_context()
+    cen = None if centre is None else _host(centre, PETAL_F64, (mx.cols,))
+    out = np.zeros((mx.rows, mx.rows))
+    info = (C.c_int64 * 2)()
+    ctx.check(ctx.lib.petal_row_gram(ctx._h, C.byref(mx), cen.ctypes.data_as(_D) if cen is not None else None, out.ctypes.data_as(_D),
+                                     info))
+    return (out, {"kernel": int(info[0]), "chunks": int(info[1])}) if want_info else out
+
+
 # ------------------------------------------------------------------------------------------------
 class _PcaModel:
     """State shared by Pca and RandomizedPca (src/pca.rs:41-51, 317-329)."""
@@ -774,6 +796,15 @@ class Pca(_PcaModel):
 
     def fit_transform(self, x):
         return self._inner_fit(x, True)
+
+    def last_route(self) -> dict:
+        """``petal_pca_last_route`` (include/petal_hip_wide.h): facts of the last ``Pca`` fit on this model's ctx -- ``route`` (0 the
+        d x d Gram route, 1 the dual route of wide data), ``kernel`` (k_row_gram ran), ``order`` of the eigenproblem, feature ``chunks``."""
+        ctx = self._ctx()
+        out = (C.c_int64 * 4)()
+        if ctx.lib.petal_pca_last_route(ctx._h, out) != PETAL_OK:
+            raise InvalidInput("petal_pca_last_route failed")
+        return {"route": int(out[0]), "kernel": int(out[1]), "order": int(out[2]), "chunks": int(out[3])}
 
 
 def _lazy_field(name):

@@ -1056,12 +1056,161 @@ void rpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, int64_t n_oversamp
 }
 
 // ---------------------------------------------------------------------------------------------
+// Exact Pca on WIDE data (include/petal_hip_wide.h): the dual of the Gram route.  For n < d the n x n ROW Gram
+// matrix K = Xc Xc^T has U itself for eigenvectors and sigma^2 for eigenvalues, its trace is the total variance, and the components
+// are V^T = Sigma^-1 U^T Xc: two passes over X and an eigenproblem of order n instead of two d x d buffers and one of order d.
+// A device-op layer without the row-Gram kernel (the host simulation), an X that does not allow its 16-byte loads and
+// PETAL_OPT_PCA_DUAL_FALLBACK build the same K and the components from op_cvt_to_f64 and op_dgemm.
+__attribute__((weak)) bool op_row_gram(Dev*, int, const void*, int64_t, int64_t, int64_t, const double*, double*, int64_t, int64_t*) {
+    return false;
+}
+namespace {
+constexpr int64_t PCA_DUAL_MIN_D = 2048;   // the auto rule: n < d and d above this (no narrower exact fit changes its route)
+bool pca_dual_applies(const petal_ctx& c, int64_t n_total, int64_t d) {
+    if (sharded(c) || c.pca_dual < 0) return false;   // (K needs row pairs across ranks)
+    return c.pca_dual > 0 || (n_total < d && d > PCA_DUAL_MIN_D);
+}
+// K (n x n, ldk; nothing outside that block is written) about `centre` (device fp64, dp values; nullable).  wide: the fallback's centred
+// fp64 copy of X (leading dimension X.ld), kept for the components' product.
+struct RowGram { bool kernel = false; int64_t chunks = 0; DBuf wide; };
+RowGram row_gram_into(petal_ctx& c, const DevMat& X, const double* centre, double* K, int64_t ldk) {
+    RowGram g;
+    if (!c.pca_dual_fallback) {
+        // (the one launch of a dual fit under TAG_ATB: with profiling on, stats.atb_ms is k_row_gram's own time)
+        dev_set_tag(c.dev, TAG_ATB);
+        g.kernel = op_row_gram(c.dev, X.dtype, X.p, X.n, X.dp, X.ld, centre, K, ldk, &g.chunks);
+        dev_set_tag(c.dev, TAG_NONE);
+    }
+    if (g.kernel) return g;
+    g.chunks = 0;
+    const int64_t n = X.n, dp = X.dp, count = (n - 1) * X.ld + dp;   // (to the end of the last row: a zero-copy input ends there)
+    g.wide = DBuf(c.dev, sizeof(double) * size_t(count));
+    op_cvt_to_f64(c.dev, X.dtype, g.wide.f64(), X.p, count);
+    if (centre) {   // Xw -= 1 c^T: a K = 1 rank-one update, widened first and centred in fp64 like the kernel
+        const std::vector<double> h1(size_t(n), 1.0);
+        DBuf ones(c.dev, sizeof(double) * size_t(n));
+        dev_h2d(c.dev, ones.p, h1.data(), ones.bytes);
+        op_dgemm(c.dev, false, false, n, dp, 1, -1.0, ones.f64(), 1, centre, dp, 1.0, g.wide.f64(), X.ld);
+    }
+    op_dgemm(c.dev, false, true, n, n, dp, 1.0, g.wide.f64(), X.ld, g.wide.f64(), X.ld, 0.0, K, ldk);
+    return g;
+}
+
+void pca_fit_dual(petal_ctx& c, const FitInput& in, int64_t k, bool centering, const PcaOutputs& out) {
+    const DevMat& X = in.X;
+    const int dt = X.dtype;
+    const int64_t n = X.n, d = X.d, dp = X.dp, np = round_up(n, 16), kp = round_up(std::max<int64_t>(k, 1), 16);
+    const size_t esz = dtype_size(dt);
+    DBuf mu64, muT;
+    column_means(c, X, double(n), centering, mu64, muT);
+    DBuf K(c.dev, sizeof(double) * np * np), V(c.dev, sizeof(double) * np * np), lam(c.dev, sizeof(double) * np);
+    DBuf sig(c.dev, sizeof(double) * np), inv(c.dev, sizeof(double) * np), diag(c.dev, sizeof(double) * np);
+    dev_memset(c.dev, K.p, 0, K.bytes);   // (the eigen-solvers read the zero padding)
+    RowGram g = row_gram_into(c, X, centering ? mu64.f64() : nullptr, K.f64(), np);
+    c.pca_route[0] = 1; c.pca_route[1] = g.kernel ? 1 : 0; c.pca_route[2] = n; c.pca_route[3] = g.chunks;
+    // total_variance = trace K, read before the eigenproblem: non-finite input (the crate's gesvd: info != 0 -> "did not converge",
+    // linalg.rs:84) leaves here instead of sending a matrix of NaNs through the solvers
+    std::vector<double> hdiag(np), hs(np), hmu(dp);
+    dev_copy2d(c.dev, diag.p, sizeof(double), K.p, (np + 1) * sizeof(double), sizeof(double), size_t(np), 2);
+    dev_d2h(c.dev, hdiag.data(), diag.p, diag.bytes);
+    dev_sync(c.dev);
+    double tvar = 0;
+    for (int64_t i = 0; i < n; ++i) tvar += hdiag[i];
+    if (!std::isfinite(tvar)) linalg_error("did not converge");
+    gram_eigen(c, dt, K, n, np, k, diag, V, lam, nullptr);
+    op_sigma_inv(c.dev, lam.f64(), sig.f64(), inv.f64(), np, dt == F32 ? 1e-6 : 1e-10);
+    // Centred rows sum to zero: K 1 = 0 and rank(Xc) <= n - 1 BY STRUCTURE.  The n-th eigenvalue is then the rounding of K, eps64
+    // lam_1 in size -- a "singular value" of 1e-8 sigma_1 that the threshold cannot tell from data -- so its inverse is cleared
+    // here: the component comes back as a zero row like every one at or below the threshold.
+    if (centering && k >= n) dev_memset(c.dev, inv.f64() + (n - 1), 0, sizeof(double));
+    // svd_flip's signs from U = the eigenvectors themselves (pca.rs:223): the k columns whose sign reaches an output
+    const std::vector<double> sg = flip_signs(c, F64, V.p, n, k, np, 0);
+    // rows of V^T: v_j = Xc^T u_j / sigma_j, one more pass over X with B = U_k Sigma^-1 (n x kp)
+    DBuf compd(c.dev, esz * size_t(std::max<int64_t>(k, 1)) * d), P(c.dev, sizeof(double) * n * kp), Vt(c.dev, sizeof(double) * dp * kp);
+    op_scale_pad_cols(c.dev, V.f64(), np, inv.f64(), n, std::min(k, n), kp, P.f64());
+    if (k > 0 && !g.kernel) {
+        op_dgemm(c.dev, true, false, dp, kp, n, 1.0, g.wide.f64(), X.ld, P.f64(), kp, 0.0, Vt.f64(), kp);
+    } else if (k > 0 && dt == F64) {
+        op_gemm_atb(c.dev, F64, X.p, X.ld, dp, muT.p, P.p, kp, kp, nullptr, n, Vt.f64(), kp, true);
+    } else if (k > 0) {
+        // op_gemm_atb takes B in the data's type: float32(B) alone would put 2^-24 sigma_1 / sigma_j into component j.  B = hi + lo,
+        // two float32 matrices that carry 48 bits of it; the two products (fp64 throughout) are added.  One more pass over X, n d
+        // elements against the n^2 d / 2 products of K.
+        const int64_t cnt = n * kp;
+        DBuf hi(c.dev, esz * cnt), lo(c.dev, esz * cnt), w(c.dev, sizeof(double) * cnt), Vt2(c.dev, Vt.bytes);
+        op_cvt_from_f64(c.dev, F32, hi.p, P.f64(), cnt);
+        op_cvt_to_f64(c.dev, F32, w.f64(), hi.p, cnt);
+        op_dscal(c.dev, w.f64(), cnt, -1.0);
+        op_daxpy(c.dev, cnt, 1.0, P.f64(), w.f64());   // w = B - hi, exact
+        op_cvt_from_f64(c.dev, F32, lo.p, w.f64(), cnt);
+        op_gemm_atb(c.dev, F32, X.p, X.ld, dp, muT.p, hi.p, kp, kp, nullptr, n, Vt.f64(), kp, true);
+        op_gemm_atb(c.dev, F32, X.p, X.ld, dp, muT.p, lo.p, kp, kp, nullptr, n, Vt2.f64(), kp, true);
+        op_daxpy(c.dev, dp * kp, 1.0, Vt2.f64(), Vt.f64());
+    }
+    op_transpose_out(c.dev, dt, Vt.f64(), kp, d, k, compd.p);
+    DBuf U;   // fit_transform: U[:, :k] in the data's type (write_pca_outputs applies sign and sigma)
+    if (out.y_out) {
+        const std::vector<double> h1(size_t(np), 1.0);
+        DBuf ones(c.dev, sizeof(double) * np), Uw(c.dev, sizeof(double) * n * kp);
+        dev_h2d(c.dev, ones.p, h1.data(), ones.bytes);
+        op_scale_pad_cols(c.dev, V.f64(), np, ones.f64(), n, std::min(k, n), kp, Uw.f64());
+        U = DBuf(c.dev, esz * size_t(n) * kp);
+        op_cvt_from_f64(c.dev, dt, U.p, Uw.f64(), n * kp);
+    }
+    {
+        void* dsts[3] = {hs.data(), hmu.data(), out.components};
+        const void* srcs[3] = {sig.p, mu64.p, compd.p};
+        const size_t lens[3] = {sig.bytes, sizeof(double) * size_t(dp), k > 0 ? esz * size_t(k) * d : 0};
+        dev_d2h_multi(c.dev, 3, dsts, srcs, lens);
+    }
+    dev_sync(c.dev);
+    write_pca_outputs(c, out, dt, k, d, out.components, sg.data(), hs.data(), hmu.data(), tvar, U.p, n, kp);
+}
+}  // namespace
+
+void row_gram(petal_ctx& c, const petal_matrix& x, const double* centre, double* out, int64_t* info2) {
+    check_matrix(x, "input");
+    if (info2) info2[0] = info2[1] = 0;
+    if (sharded(c)) invalid_input("row_gram: a sharded ctx is not supported in this version");
+    const int64_t n = x.rows, d = x.cols;
+    if (n == 0) return;
+    if (!out) invalid_input("out must not be null");
+    if (d == 0) { std::fill(out, out + n * n, 0.0); return; }
+    const DevMat X = ingest(c, x);
+    DBuf cen;
+    if (centre) {
+        std::vector<double> h(size_t(X.dp), 0.0);
+        std::copy(centre, centre + d, h.begin());
+        cen = DBuf(c.dev, sizeof(double) * X.dp);
+        dev_h2d(c.dev, cen.p, h.data(), cen.bytes);
+    }
+    // K is formed inside a guard: an odd pitch, a row more, every byte 0xFF beforehand.  What lies outside the n x n block must come
+    // back untouched.
+    const int64_t ldk = n + 3, rows = n + 1;
+    DBuf K(c.dev, sizeof(double) * size_t(rows) * ldk);
+    dev_memset(c.dev, K.p, 0xFF, K.bytes);
+    const RowGram g = row_gram_into(c, X, centre ? cen.f64() : nullptr, K.f64(), ldk);
+    std::vector<double> h(size_t(rows) * ldk);
+    dev_d2h(c.dev, h.data(), K.p, K.bytes);
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < rows; ++i)
+        for (int64_t j = (i < n ? n : 0); j < ldk; ++j) {
+            uint64_t bits = 0;
+            std::memcpy(&bits, &h[size_t(i) * ldk + j], 8);
+            if (bits != ~uint64_t(0)) device_error("row_gram wrote outside the n x n block");
+        }
+    for (int64_t i = 0; i < n; ++i) std::copy(h.begin() + i * ldk, h.begin() + i * ldk + n, out + i * n);
+    if (info2) { info2[0] = g.kernel ? 1 : 0; info2[1] = g.chunks; }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Pca::inner_fit (pca.rs:195-231).  The reference asks LAPACK for the full n x n U; only its first
 // min(n,d) columns are ever read (svd_flip zips U columns with V^T rows; transform_with_u takes k),
 // so the thin factorisation is computed: eigen-decomposition of the d x d Gram matrix in fp64.
 void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, void* components, void* means,
              void* singular, void* total_variance, const petal_matrix* y_out) {
     const Timer timer = start_fit(c, x);
+    for (int64_t& v : c.pca_route) v = 0;
     if (k < 0) invalid_input("negative parameter");
     const int dt = x.dtype;
     const int64_t d = x.cols;
@@ -1075,6 +1224,12 @@ void pca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, bool centering, voi
         return;
     }
     if (!sharded(c)) in.X = ingest(c, x);
+    if (pca_dual_applies(c, n_total, d)) {   // wide data: the n x n row Gram matrix instead of the d x d one
+        pca_fit_dual(c, in, k, centering, {components, means, singular, total_variance, y_out});
+        finish_stats(c, timer);
+        return;
+    }
+    c.pca_route[2] = d;
     const DevMat& X = in.X;
     const int64_t n = X.n, dp = X.dp;
     const size_t esz = dtype_size(dt);

@@ -9,6 +9,7 @@
 #include "../../include/petal_hip_segments.h"
 #include "../../include/petal_hip_sparse.h"
 #include "../../include/petal_hip_ipca.h"
+#include "../../include/petal_hip_wide.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -141,6 +142,12 @@ int petal_ctx_set_option(petal_ctx* ctx, int option, double value) {
     return guarded(ctx, [&] {
         if (option == PETAL_OPT_FORCE_COLLECTIVE) { ctx->force_collective = value != 0; return; }
         if (option == PETAL_OPT_IPCA_FALLBACK) { ctx->ipca_fallback = value != 0; return; }
+        if (option == PETAL_OPT_PCA_DUAL) {
+            if (!(value == value)) invalid_input("unknown ctx option or NaN value");
+            ctx->pca_dual = value > 0 ? 1 : (value < 0 ? -1 : 0);
+            return;
+        }
+        if (option == PETAL_OPT_PCA_DUAL_FALLBACK) { ctx->pca_dual_fallback = value != 0; return; }
         if (option < 0 || option >= OPT_COUNT || !(value == value)) invalid_input("unknown ctx option or NaN value");
         dev_set_option(ctx->dev, option, value);
     });
@@ -150,6 +157,8 @@ int petal_ctx_get_option(const petal_ctx* ctx, int option, double* value) {
     if (!ctx || !value) return PETAL_INVALID_INPUT;
     if (option == PETAL_OPT_FORCE_COLLECTIVE) { *value = ctx->force_collective ? 1.0 : 0.0; return PETAL_OK; }
     if (option == PETAL_OPT_IPCA_FALLBACK) { *value = ctx->ipca_fallback ? 1.0 : 0.0; return PETAL_OK; }
+    if (option == PETAL_OPT_PCA_DUAL) { *value = double(ctx->pca_dual); return PETAL_OK; }
+    if (option == PETAL_OPT_PCA_DUAL_FALLBACK) { *value = ctx->pca_dual_fallback ? 1.0 : 0.0; return PETAL_OK; }
     if (option < 0 || option >= OPT_COUNT) return PETAL_INVALID_INPUT;
     *value = dev_option(ctx->dev, option);
     return PETAL_OK;
@@ -321,6 +330,19 @@ int petal_ipca_set_state(petal_ctx* ctx, petal_ipca* h, double n, const double* 
     return guarded(ctx, [&] {
         need(h, "handle");
         ipca_set_state(*ctx, *h, n, mean_d, m2_dxd);
+    });
+}
+
+// ---- include/petal_hip_wide.h: exact Pca on wide data --------------------------------------------------------------------------------
+int petal_pca_last_route(petal_ctx* ctx, int64_t* out4) {
+    if (!ctx || !out4) return PETAL_INVALID_INPUT;
+    for (int i = 0; i < 4; ++i) out4[i] = ctx->pca_route[i];
+    return PETAL_OK;
+}
+int petal_row_gram(petal_ctx* ctx, const petal_matrix* x, const double* centre, double* out, int64_t* info2) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        row_gram(*ctx, *x, centre, out, info2);
     });
 }
 

@@ -19,6 +19,9 @@ struct petal_ctx {
     int rank = 0, world = 1;
     int profiling = 0;
     bool ipca_fallback = false;      // PETAL_OPT_IPCA_FALLBACK (include/petal_hip_ipca.h): a test aid
+    int pca_dual = 0;                // PETAL_OPT_PCA_DUAL (include/petal_hip_wide.h): 0 the auto rule, 1 always (non-sharded), -1 never
+    bool pca_dual_fallback = false;  // PETAL_OPT_PCA_DUAL_FALLBACK: a test aid
+    int64_t pca_route[4] = {0, 0, 0, 0};   // petal_pca_last_route: route, kernel, order of the eigenproblem, feature chunks
     bool force_collective = false;   // PETAL_OPT_FORCE_COLLECTIVE (default: env PETAL_FORCE_COLLECTIVE at petal_ctx_create)
     petal_stats stats{};
     void* rccl = nullptr;  // the built-in RCCL communicator (rccl.cpp), when petal_ctx_init_rccl installed it
@@ -146,6 +149,8 @@ void rpca_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, int64_t n_oversam
 void transform_csr(petal_ctx& c, const petal_csr& x, const void* components, const void* means, int64_t k, int64_t d, bool centering,
                    const petal_matrix& y_out, int64_t* kernel_path);
 void csr_gemm(petal_ctx& c, const petal_csr& x, bool transposed, const double* P, int64_t N, const double* a, const double* s, double* out);
+// include/petal_hip_wide.h: the row Gram matrix of exact Pca's dual route by itself (a test aid)
+void row_gram(petal_ctx& c, const petal_matrix& x, const double* centre, double* out, int64_t* info2);
 // include/petal_hip_ipca.h: IncrementalPca
 petal_ipca* ipca_create(petal_ctx& c, int64_t d, int32_t dtype, bool centering);
 void ipca_destroy(petal_ipca* h);

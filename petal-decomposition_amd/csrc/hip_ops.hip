@@ -593,4 +593,5 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #include "kernels/k_pca_segments.inc"   // segmented Pca: one workgroup per row segment (k_pca_segments), k_seg_project, their launchers
 #include "kernels/k_spmm.inc"   // sparse (CSR) x dense products of RandomizedPca on sparse data (k_spmm, k_spmm_combine, k_csr_rowstats), their launchers
 #include "kernels/k_ipca.inc"   // IncrementalPca: the per-batch fp64 Gram + column sums about a fixed centre (k_gram_stream), the statistic's update (k_ipca_merge)
+#include "kernels/k_row_gram.inc"   // exact Pca on wide data: the row Gram matrix over the feature axis (k_row_gram), its fixed-order slab sum (k_row_gram_sum)
 }  // namespace petal

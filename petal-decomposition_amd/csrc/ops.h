@@ -203,6 +203,16 @@ bool op_ipca_accumulate(Dev*, int dtype, const void* X, int64_t m, int64_t dp, i
 // mean_out must not be mean_a, and M2_a not M2_b.
 bool op_ipca_merge(Dev*, int64_t dp, double n_a, double* M2_a, const double* mean_a, double* mean_out, double n_b, const double* M2_b,
                    const double* mean_b);
+// Exact Pca's dual route on wide data (include/petal_hip_wide.h; an extension beyond the crate).  The ROW Gram matrix
+//     K[i][i'] (n x n fp64, ldk; both triangles written, nothing outside the leading n x n block) = sum_j (x_ij - c_j)(x_i'j - c_j)
+// of X (n rows x dp columns in dtype, ldx; dp a multiple of 16 whose padding columns hold zeros, as ingest leaves them) about `centre`
+// (DEVICE fp64, dp values, zero in the padding; nullable = centring off).  x is widened to fp64 BEFORE the subtraction, every product
+// and sum is fp64.  The feature axis is cut into *chunks (nullable) pieces whose slabs a second launch adds in a fixed order: no
+// atomics, the same input gives the same bytes.  Returns "this layer did the work": false, NOTHING done, where X does not allow
+// 16-byte loads along its rows or the layer lacks the op -- algo.cpp's weak default returns false and the caller builds K from
+// op_cvt_to_f64 and op_dgemm.
+bool op_row_gram(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64_t ldx, const double* centre, double* K, int64_t ldk,
+                 int64_t* chunks);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.

@@ -7,11 +7,13 @@ mod ffi_ipca;
 mod ffi_score;
 mod ffi_segments;
 mod ffi_sparse;
+mod ffi_wide;
 mod ica;
 mod pca;
 
 pub use ica::{Contrast, FastIca, FastIcaBuilder};
-pub use pca::{CsrMatrix, IncrementalPca, Pca, PcaBuilder, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
+pub use ffi_wide::{PETAL_OPT_PCA_DUAL, PETAL_OPT_PCA_DUAL_FALLBACK};
+pub use pca::{CsrMatrix, IncrementalPca, Pca, PcaBuilder, PcaRoute, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
 
 use ndarray::{ArrayBase, Data, Ix2};
 use std::ffi::CStr;

@@ -1,5 +1,5 @@
 //! `Pca` (`src/pca.rs:41-231` of the reference) and `RandomizedPca` (`src/pca.rs:317-663`) over the C ABI.
-use crate::{ffi, ffi_ipca, ffi_score, ffi_segments, ffi_sparse, view, with_ctx, DecompositionError, HipScalar};
+use crate::{ffi, ffi_ipca, ffi_score, ffi_segments, ffi_sparse, ffi_wide, view, with_ctx, DecompositionError, HipScalar};
 use ndarray::{Array1, Array2, Array3, ArrayBase, Data, Ix2};
 use rand::Rng;
 use rand_distr::StandardNormal;
@@ -8,6 +8,16 @@ use std::os::raw::c_void;
 
 const N_OVERSAMPLE: usize = 10; // src/pca.rs:679
 const N_ITER: i64 = 7; // src/pca.rs:680
+
+/// Facts of the last exact `Pca` fit of this process (include/petal_hip_wide.h): `dual` = the n x n row-Gram route of wide data
+/// (n < d, d > 2048) was taken, `kernel` = k_row_gram ran, `order` of the eigenproblem, feature `chunks` of the row-Gram launch.
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct PcaRoute {
+    pub dual: bool,
+    pub kernel: bool,
+    pub order: i64,
+    pub chunks: i64,
+}
 
 /// Exact PCA.  Field names follow the reference so serialized models interchange.
 #[cfg_attr(feature = "serde", derive(serde::Serialize, serde::Deserialize))]
@@ -46,6 +56,13 @@ impl<A: HipScalar> Pca<A> {
     }
     pub fn inverse_transform<S: Data<Elem = A>>(&self, input: &ArrayBase<S, Ix2>) -> Result<Array2<A>, DecompositionError> {
         inverse_transform(input, &self.components, &self.means, self.centering)
+    }
+
+    /// Which route the last exact fit took (include/petal_hip_wide.h; an extension beyond the crate).
+    pub fn last_route() -> Result<PcaRoute, DecompositionError> {
+        let mut v = [0i64; 4];
+        with_ctx(|ctx| unsafe { ffi_wide::petal_pca_last_route(ctx, v.as_mut_ptr()) }, || ())?;
+        Ok(PcaRoute { dual: v[0] != 0, kernel: v[1] != 0, order: v[2], chunks: v[3] })
     }
 
     // ---- scores of rows against the fitted model: an extension beyond the crate (include/petal_hip_score.h) ----
