@@ -26,6 +26,7 @@
 #include "petal_hip_sparse.h"
 #include "petal_hip_ipca.h"
 #include "petal_hip_wide.h"
+#include "petal_hip_kpca.h"
 
 namespace petal_decomposition {
 
@@ -478,6 +479,78 @@ class IncrementalPca {
     detail::PcaState<A> st_;
     petal_ipca* h_ = nullptr;
     bool dirty_ = false;
+};
+
+// Kernel PCA (petal_hip_kpca.h: an extension beyond the crate; scikit-learn's KernelPCA).  kernel = PETAL_KERNEL_*; gamma <= 0 means
+// 1 / d.  fit_transform = V sqrt(lambda); transform is one fused pass whose m x n kernel matrix never touches memory.  The fitted
+// model lives with its ctx (destroy the model before the Context) and keeps its own device copy of the training rows.
+struct KernelPcaInfo {
+    int64_t n = 0, d = 0, k = 0, order = 0;
+    bool fit_kernel = false;        // k_kmap ran on the fit's map (false: the fallback built K~)
+    int transform_kernel = -1;      // k_kapply ran on the last transform (1 / 0; -1 before the first)
+    int kernel = 0;
+    bool topk_solver = false;       // the top-k subspace iteration delivered the eigenpairs (false: the full eigen-solver of order n ran)
+};
+
+template <class A>
+class KernelPca {
+  public:
+    explicit KernelPca(int64_t n_components, int kernel = PETAL_KERNEL_LINEAR, double gamma = 0.0, int degree = 3, double coef0 = 1.0,
+                       Context* ctx = nullptr)
+        : k_(n_components), ctx_(ctx) {
+        spec_.kernel = kernel; spec_.degree = degree; spec_.gamma = gamma; spec_.coef0 = coef0;
+    }
+    KernelPca(const KernelPca&) = delete;
+    KernelPca& operator=(const KernelPca&) = delete;
+    KernelPca(KernelPca&& o) noexcept : k_(o.k_), spec_(o.spec_), ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    ~KernelPca() { petal_kpca_destroy(h_); }
+    KernelPca& fit(const Array2<A>& input) { inner_fit(input, nullptr); return *this; }
+    Array2<A> fit_transform(const Array2<A>& input) {
+        Array2<A> y(input.nrows(), k_);
+        inner_fit(input, &y);
+        return y;
+    }
+    Array2<A> transform(const Array2<A>& input) {
+        Array2<A> y(input.nrows(), k_);
+        petal_matrix mx = input.view(), my = y.view();
+        context().check(petal_kpca_transform(context().get(), handle(), &mx, &my));
+        return y;
+    }
+    int64_t n_components() const { return k_; }
+    // the k leading eigenvalues of the centred kernel matrix, as computed (descending)
+    std::vector<double> eigenvalues() const {
+        std::vector<double> lam(size_t(k_), 0.0);
+        if (petal_kpca_get(handle(), lam.data(), nullptr, nullptr) != PETAL_OK)
+            throw DecompositionError(DecompositionError::InvalidInput, "petal_kpca_get failed");
+        return lam;
+    }
+    KernelPcaInfo info() const {
+        int64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (petal_kpca_get(handle(), nullptr, nullptr, v) != PETAL_OK)
+            throw DecompositionError(DecompositionError::InvalidInput, "petal_kpca_get failed");
+        KernelPcaInfo r;
+        r.n = v[0]; r.d = v[1]; r.k = v[2]; r.fit_kernel = v[3] != 0; r.transform_kernel = int(v[4]); r.order = v[5]; r.kernel = int(v[6]); r.topk_solver = v[7] != 0;
+        return r;
+    }
+
+  private:
+    Context& context() const { return ctx_ ? *ctx_ : Context::global(); }
+    petal_kpca* handle() const {
+        if (!h_) throw DecompositionError(DecompositionError::InvalidInput, "the model has not been fitted");
+        return h_;
+    }
+    void inner_fit(const Array2<A>& input, Array2<A>* y) {
+        petal_matrix mx = input.view(), my{};
+        if (y) my = y->view();
+        petal_kpca* h = nullptr;
+        context().check(petal_kpca_fit(context().get(), &mx, k_, &spec_, &h, y ? &my : nullptr));
+        petal_kpca_destroy(h_);
+        h_ = h;
+    }
+    int64_t k_;
+    petal_kernel_spec spec_{};
+    Context* ctx_;
+    petal_kpca* h_ = nullptr;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

@@ -32,7 +32,8 @@ OPTIONS = {"two_plane_operands": 0, "two_plane_omega": 1, "two_plane_iterate": 2
            "fused_pass_min_rows": 5, "verdict_threshold": 6, "means_fold_rows": 7, "gram_split": 8, "gram_split_hook": 9,
            "d2h_kernel": 10, "row_pad": 11, "eigh_jacobi": 12, "poison": 13, "force_collective": 14, "steering_hook": 15,
            "ipca_fallback": 32,   # (32: PETAL_OPT_IPCA_FALLBACK, include/petal_hip_ipca.h -- a test aid)
-           "pca_dual": 33, "pca_dual_fallback": 34}   # (PETAL_OPT_PCA_DUAL, PETAL_OPT_PCA_DUAL_FALLBACK: include/petal_hip_wide.h)
+           "pca_dual": 33, "pca_dual_fallback": 34,   # (PETAL_OPT_PCA_DUAL, PETAL_OPT_PCA_DUAL_FALLBACK: include/petal_hip_wide.h)
+           "kpca_fallback": 36}   # (PETAL_OPT_KPCA_FALLBACK, include/petal_hip_kpca.h -- a test aid)
 ICA_TEXTBOOK, ICA_REFERENCE_LITERAL = 0, 1
 # the contrast function of the FastICA iteration: bits 4-7 of the same `mode` argument (include/petal_hip.h); EXP and CUBE are an
 # extension beyond the crate, whose only contrast is logcosh
@@ -194,6 +195,21 @@ ABI_WIDE = [
 ]
 
 
+# every symbol include/petal_hip_kpca.h declares (KernelPca and its fused pass by itself)
+class petal_kernel_spec(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("degree", C.c_int32), ("gamma", C.c_double), ("coef0", C.c_double)]
+
+
+_KS = C.POINTER(petal_kernel_spec)
+KERNELS = {"linear": 0, "poly": 1, "rbf": 2, "sigmoid": 3, "cosine": 4}   # PETAL_KERNEL_*
+ABI_KPCA = [
+    ("petal_kpca_fit", C.c_int, [_P, _M, C.c_int64, _KS, C.POINTER(C.c_void_p), _M]),
+    ("petal_kpca_destroy", None, [_P]),
+    ("petal_kpca_transform", C.c_int, [_P, _P, _M, _M]),
+    ("petal_kpca_get", C.c_int, [_P, _D, _D, _L]),
+    ("petal_kernel_apply", C.c_int, [_P, _M, _M, _KS, _D, C.c_int64, _D, _D, _L]),
+]
+
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
     file name, so a process that first loads the system HIP runtime (through this library) and then imports
@@ -210,7 +226,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -219,7 +235,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -315,10 +331,11 @@ class Context:
         self.rank, self.world_size = 0, 1
         self._csr = weakref.WeakSet()   # the sparse matrices resident with this ctx: released before it
         self._ipca = weakref.WeakSet()  # ... and the IncrementalPca statistics
+        self._kpca = weakref.WeakSet()  # ... and the fitted KernelPca models
 
     def close(self):
         if getattr(self, "_h", None):
-            for m in list(getattr(self, "_csr", ())) + list(getattr(self, "_ipca", ())):
+            for m in list(getattr(self, "_csr", ())) + list(getattr(self, "_ipca", ())) + list(getattr(self, "_kpca", ())):
                 m.close()
             self.lib.petal_ctx_destroy(self._h)
             self._h = None
@@ -611,6 +628,133 @@ def row_gram(x, centre=None, ctx: Optional["Context"] = None, want_info: bool = 
     ctx.check(ctx.lib.petal_row_gram(ctx._h, C.byref(mx), cen.ctypes.data_as(_D) if cen is not None else None, out.ctypes.data_as(_D),
                                      info))
     return (out, {"kernel": int(info[0]), "chunks": int(info[1])}) if want_info else out
+
+
+def _kernel_spec(kernel, gamma, degree, coef0) -> petal_kernel_spec:
+    if kernel not in KERNELS:
+        raise InvalidInput(f"unknown kernel {kernel!r} (one of {', '.join(KERNELS)})")
+    return petal_kernel_spec(KERNELS[kernel], int(degree), 0.0 if gamma is None else float(gamma), float(coef0))
+
+
+def kernel_apply(xq, xt, a, kernel="linear", gamma=None, degree=3, coef0=1.0, centre=None, ctx: Optional["Context"] = None,
+                 want_info: bool = False):
+    """Test aid (``petal_kernel_apply``, include/petal_hip_kpca.h): ``phi((xq - centre) @ (xt - centre).T) @ a`` in float64, the fused
+    pass of ``KernelPca.transform`` by itself -- no double centring, no epilogue.  ``xq`` (m x d), ``xt`` (n x d): numpy or
+    ``torch.cuda``, the same dtype, any strides; ``a``: n x cols float64; ``centre``: d float64 values or None.  ``want_info``: also
+    returns ``{"kernel": k_kapply ran}``."""
+    keep = []
+    mq, mt = describe(xq, keep), describe(xt, keep)
+    ctx = ctx or default_context()
+    spec = _kernel_spec(kernel, gamma, degree, coef0)
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != mt.rows:
+        raise InvalidInput(f"a should have {mt.rows} rows")
+    a = np.ascontiguousarray(a)
+    cen = None if centre is None else _host(centre, PETAL_F64, (mt.cols,))
+    out = np.zeros((mq.rows, a.shape[1]))
+    info = (C.c_int64 * 1)()
+    ctx.check(ctx.lib.petal_kernel_apply(ctx._h, C.byref(mq), C.byref(mt), C.byref(spec), a.ctypes.data_as(_D), a.shape[1],
+                                         cen.ctypes.data_as(_D) if cen is not None else None, out.ctypes.data_as(_D), info))
+    return (out, {"kernel": int(info[0])}) if want_info else out
+
+
+class KernelPca:
+    """Kernel PCA (``petal_kpca``, include/petal_hip_kpca.h; an extension beyond the crate, DESIGN.md sections 4 and 7) -- scikit-learn's
+    ``KernelPCA`` with the kernels ``linear``, ``poly``, ``rbf``, ``sigmoid`` and ``cosine``.  ``gamma=None`` (or <= 0) means 1 / d.
+    ``fit_transform`` = V sqrt(lambda); ``transform`` is one fused pass over the query rows whose m x n kernel matrix never touches
+    memory.  Everything is float64 inside; outputs are rounded once to the data's type.  A component at or below the relative threshold
+    (1e-6 float32, 1e-10 float64, on sqrt(lambda)) is a zero column of both outputs.  The fitted model lives with its ctx and keeps its
+    own device copy of the training rows."""
+
+    def __init__(self, n_components: int, kernel: str = "linear", gamma=None, degree: int = 3, coef0: float = 1.0,
+                 ctx: Optional[Context] = None):
+        self._k = int(n_components)
+        self.kernel, self.gamma, self.degree, self.coef0 = kernel, gamma, int(degree), float(coef0)
+        self.ctx = ctx
+        self._h = None
+
+    def _ctx(self) -> Context:
+        if self.ctx is None:
+            self.ctx = default_context()
+        return self.ctx
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self.ctx.lib.petal_kpca_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise InvalidInput("the model has not been fitted (or its ctx was closed)")
+        return self._h
+
+    def n_components(self):
+        return self._k
+
+    def _inner_fit(self, x, want_y: bool):
+        keep = []
+        mx = describe(x, keep)
+        ctx = self._ctx()
+        spec = _kernel_spec(self.kernel, self.gamma, self.degree, self.coef0)
+        y, my = None, None
+        if want_y:
+            y = _alloc_like(x, mx.rows, self._k, mx.dtype)
+            my = describe(y, keep)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.petal_kpca_fit(ctx._h, C.byref(mx), self._k, C.byref(spec), C.byref(h), C.byref(my) if my is not None else None))
+        self.close()
+        self._h = h
+        ctx._kpca.add(self)
+        return y
+
+    def fit(self, x):
+        self._inner_fit(x, False)
+        return self
+
+    def fit_transform(self, x):
+        return self._inner_fit(x, True)
+
+    def transform(self, x):
+        keep = []
+        mx = describe(x, keep)
+        ctx = self._ctx()
+        y = _alloc_like(x, mx.rows, self._k, mx.dtype)
+        my = describe(y, keep)
+        ctx.check(ctx.lib.petal_kpca_transform(ctx._h, self._handle(), C.byref(mx), C.byref(my)))
+        return y
+
+    def _get(self, lam=None, vec=None):
+        h = self._handle()   # (first: an unfitted model may have no ctx yet)
+        out = (C.c_int64 * 8)()
+        if self._ctx().lib.petal_kpca_get(h, lam.ctypes.data_as(_D) if lam is not None else None,
+                                       vec.ctypes.data_as(_D) if vec is not None else None, out) != PETAL_OK:
+            raise InvalidInput("petal_kpca_get failed")
+        return out
+
+    def eigenvalues(self):
+        """The k leading eigenvalues of the centred kernel matrix, float64, as computed (descending)."""
+        lam = np.zeros(self._k)
+        self._get(lam=lam)
+        return lam
+
+    def scaled_eigenvectors(self):
+        """V lambda^(-1/2), n x k float64, signs applied; a zero column where the component is undetermined."""
+        vec = np.zeros((self.info()["n"], self._k))
+        self._get(vec=vec)
+        return vec
+
+    def info(self) -> dict:
+        """n, d, k, ``fit_kernel`` (k_kmap ran on the fit's map), ``transform_kernel`` (k_kapply ran on the last transform; -1 before
+        the first), ``order`` of the eigenproblem, kernel, ``topk_solver`` (1: the top-k subspace iteration delivered the eigenpairs; 0: the
+        full eigen-solver of order n ran -- the slower fit)."""
+        keys = ("n", "d", "k", "fit_kernel", "transform_kernel", "order", "kernel", "topk_solver")
+        return dict(zip(keys, (int(v) for v in self._get())))
 
 
 # ------------------------------------------------------------------------------------------------

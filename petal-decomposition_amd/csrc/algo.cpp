@@ -12,6 +12,7 @@
 #include "ctx.h"
 #include "../../include/petal_hip_sparse.h"
 #include "../../include/petal_hip_ipca.h"
+#include "../../include/petal_hip_kpca.h"
 
 namespace petal {
 
@@ -1073,9 +1074,9 @@ bool pca_dual_applies(const petal_ctx& c, int64_t n_total, int64_t d) {
 // K (n x n, ldk; nothing outside that block is written) about `centre` (device fp64, dp values; nullable).  wide: the fallback's centred
 // fp64 copy of X (leading dimension X.ld), kept for the components' product.
 struct RowGram { bool kernel = false; int64_t chunks = 0; DBuf wide; };
-RowGram row_gram_into(petal_ctx& c, const DevMat& X, const double* centre, double* K, int64_t ldk) {
+RowGram row_gram_into(petal_ctx& c, const DevMat& X, const double* centre, double* K, int64_t ldk, bool force_fallback = false) {
     RowGram g;
-    if (!c.pca_dual_fallback) {
+    if (!c.pca_dual_fallback && !force_fallback) {
         // (the one launch of a dual fit under TAG_ATB: with profiling on, stats.atb_ms is k_row_gram's own time)
         dev_set_tag(c.dev, TAG_ATB);
         g.kernel = op_row_gram(c.dev, X.dtype, X.p, X.n, X.dp, X.ld, centre, K, ldk, &g.chunks);
@@ -1201,6 +1202,342 @@ void row_gram(petal_ctx& c, const petal_matrix& x, const double* centre, double*
         }
     for (int64_t i = 0; i < n; ++i) std::copy(h.begin() + i * ldk, h.begin() + i * ldk + n, out + i * n);
     if (info2) { info2[0] = g.kernel ? 1 : 0; info2[1] = g.chunks; }
+}
+
+// ---------------------------------------------------------------------------------------------
+// KernelPca (include/petal_hip_kpca.h; DESIGN.md sections 4 and 7).  The fit is exact Pca's dual route with an element-wise map between
+// the row Gram matrix and the eigenproblem: G = (X - c)(X - c)^T, K = phi(G), K~ = K centred twice, top k eigenpairs, svd_flip's signs
+// from V.  transform is ONE fused pass phi(Xq Xt^T) A' with A' = [V lambda^(-1/2) | 1] (k_kapply) and an epilogue on its k + 1 columns.
+// A device-op layer without the kernels (the host simulation), a matrix that does not allow their 16-byte loads and
+// PETAL_OPT_KPCA_FALLBACK build the same statements from op_cvt_to_f64, op_dgemm and a phi loop on the host over a read-back copy.
+__attribute__((weak)) bool op_kpca_map(Dev*, int, double, double, int, double*, int64_t, int64_t, const double*, double*, double*) { return false; }
+__attribute__((weak)) bool op_kernel_apply(Dev*, int, const void*, int64_t, int64_t, const void*, int64_t, int64_t, int64_t, const double*,
+                                           const double*, int, double, double, int, const double*, int64_t, int64_t, double*, int64_t) {
+    return false;
+}
+__attribute__((weak)) bool op_kpca_finish(Dev*, int, const double*, int64_t, int64_t, int64_t, const double*, const double*, double,
+                                          const double*, void*, int64_t) {
+    return false;
+}
+namespace {
+void check_output(const petal_matrix& out, int dt, int64_t rows, int64_t cols);   // (with the segmented entries below)
+double host_phi(const KernelSpec& s, double g, double na, double nb) {
+    switch (s.kernel) {
+        case PETAL_KERNEL_POLY: {
+            const double b = s.gamma * g + s.coef0;
+            double v = b;
+            for (int t = 1; t < s.degree; ++t) v *= b;
+            return v;
+        }
+        case PETAL_KERNEL_RBF: return std::exp(-s.gamma * std::max(na + nb - 2.0 * g, 0.0));
+        case PETAL_KERNEL_SIGMOID: return std::tanh(s.gamma * g + s.coef0);
+        case PETAL_KERNEL_COSINE: {
+            const double den = std::sqrt(na) * std::sqrt(nb);
+            return den > 0.0 ? g / den : 0.0;
+        }
+        default: return g;
+    }
+}
+bool kernel_needs_norms(int kernel) { return kernel == PETAL_KERNEL_RBF || kernel == PETAL_KERNEL_COSINE; }
+KernelSpec resolve_spec(const KernelSpec& s, int64_t d) {
+    if (s.kernel < PETAL_KERNEL_LINEAR || s.kernel > PETAL_KERNEL_COSINE) invalid_input("unknown kernel");
+    if (s.degree < 1) invalid_input("degree should be at least 1");
+    if (!std::isfinite(s.coef0) || std::isinf(s.gamma)) invalid_input("kernel parameters should be finite");
+    KernelSpec r = s;
+    if (!(s.gamma > 0)) r.gamma = 1.0 / double(std::max<int64_t>(d, 1));   // (unset, <= 0 or NaN: 1 / d)
+    return r;
+}
+DBuf device_ones(petal_ctx& c, int64_t count) {
+    const std::vector<double> h1(size_t(count), 1.0);
+    DBuf ones(c.dev, sizeof(double) * size_t(count));
+    dev_h2d(c.dev, ones.p, h1.data(), ones.bytes);
+    return ones;
+}
+// W (rows x dp fp64, leading dimension ld like its source) = the rows of X widened and centred about cen (device, dp)
+DBuf widened_centred(petal_ctx& c, int dt, const void* X, int64_t rows, int64_t dp, int64_t ld, const double* cen, const DBuf& ones) {
+    const int64_t count = (rows - 1) * ld + dp;   // (to the end of the last row: a zero-copy input ends there)
+    DBuf W(c.dev, sizeof(double) * size_t(count));
+    op_cvt_to_f64(c.dev, dt, W.f64(), X, count);
+    op_dgemm(c.dev, false, false, rows, dp, 1, -1.0, ones.f64(), 1, cen, dp, 1.0, W.f64(), ld);
+    return W;
+}
+void host_row_norms(const std::vector<double>& w, int64_t rows, int64_t dp, int64_t ld, std::vector<double>& nrm) {
+    nrm.assign(size_t(rows), 0.0);
+    for (int64_t i = 0; i < rows; ++i) {
+        double s = 0;
+        for (int64_t j = 0; j < dp; ++j) s += w[size_t(i) * ld + j] * w[size_t(i) * ld + j];
+        nrm[i] = s;
+    }
+}
+constexpr int64_t KPCA_FALLBACK_BLOCK = int64_t(1) << 22;   // doubles of the score block a fallback step holds (32 MiB)
+
+// out (m x cols fp64, ldo; nothing outside that block is written) = phi((Xq - cen)(Xt - cen)^T) A: the fused pass where the layer has
+// it, else the same statement in row blocks.  cen: device, dp (never null); nt (nullable): device, n; A: device, round_up(n, 32) x lda,
+// zero outside n x cols.  Returns "k_kapply ran".
+bool kernel_apply_into(petal_ctx& c, const KernelSpec& s, const void* xt, int64_t n, int64_t ldt, const DevMat& Xq, const double* cen,
+                       const double* nt, const double* A, int64_t lda, int64_t cols, double* out, int64_t ldo) {
+    const int dt = Xq.dtype;
+    const int64_t m = Xq.n, dp = Xq.dp;
+    if (!c.kpca_fallback) {
+        // (the one launch of a transform under TAG_XP: with profiling on, stats.xp_ms is k_kapply's own time)
+        dev_set_tag(c.dev, TAG_XP);
+        const bool ran = op_kernel_apply(c.dev, dt, xt, n, ldt, Xq.p, m, Xq.ld, dp, cen, nt, s.kernel, s.gamma, s.coef0, s.degree, A, lda, cols,
+                                         out, ldo);
+        dev_set_tag(c.dev, TAG_NONE);
+        if (ran) return true;
+    }
+    const bool norms = kernel_needs_norms(s.kernel);
+    const int64_t B = std::max<int64_t>(1, std::min(m, KPCA_FALLBACK_BLOCK / n));
+    const DBuf ones = device_ones(c, std::max(n, B));
+    const DBuf Wt = widened_centred(c, dt, xt, n, dp, ldt, cen, ones);
+    std::vector<double> hnt, hnq, hw, hs(size_t(B) * n);
+    if (norms && nt) {
+        hnt.resize(size_t(n));
+        dev_d2h(c.dev, hnt.data(), nt, sizeof(double) * size_t(n));
+        dev_sync(c.dev);
+    } else if (norms) {
+        hw.resize(size_t((n - 1) * ldt + dp));
+        dev_d2h(c.dev, hw.data(), Wt.p, sizeof(double) * hw.size());
+        dev_sync(c.dev);
+        host_row_norms(hw, n, dp, ldt, hnt);
+    }
+    DBuf S(c.dev, sizeof(double) * size_t(B) * n);
+    const size_t esz = dtype_size(dt);
+    for (int64_t r0 = 0; r0 < m; r0 += B) {
+        const int64_t b = std::min(B, m - r0);
+        const DBuf Wq = widened_centred(c, dt, static_cast<const char*>(Xq.p) + size_t(r0) * Xq.ld * esz, b, dp, Xq.ld, cen, ones);
+        op_dgemm(c.dev, false, true, b, n, dp, 1.0, Wq.f64(), Xq.ld, Wt.f64(), ldt, 0.0, S.f64(), n);
+        dev_d2h(c.dev, hs.data(), S.p, sizeof(double) * size_t(b) * n);
+        if (norms) {
+            hw.resize(size_t((b - 1) * Xq.ld + dp));
+            dev_d2h(c.dev, hw.data(), Wq.p, sizeof(double) * hw.size());
+        }
+        dev_sync(c.dev);
+        if (norms) host_row_norms(hw, b, dp, Xq.ld, hnq);
+        for (int64_t i = 0; i < b; ++i)
+            for (int64_t j = 0; j < n; ++j)
+                hs[size_t(i) * n + j] = host_phi(s, hs[size_t(i) * n + j], norms ? hnq[i] : 0.0, norms ? hnt[j] : 0.0);
+        dev_h2d(c.dev, S.p, hs.data(), sizeof(double) * size_t(b) * n);
+        op_dgemm(c.dev, false, false, b, cols, n, 1.0, S.f64(), n, A, lda, 0.0, out + r0 * ldo, ldo);
+    }
+    return false;
+}
+
+// the leading n x n block of K (ldk): G on entry, K~ on return; rbar (n) / tbar (1): device.  Returns "k_kmap ran".
+bool kpca_map_into(petal_ctx& c, const KernelSpec& s, double* K, int64_t n, int64_t ldk, const double* diag, double* rbar, double* tbar) {
+    if (!c.kpca_fallback && op_kpca_map(c.dev, s.kernel, s.gamma, s.coef0, s.degree, K, n, ldk, diag, rbar, tbar)) return true;
+    std::vector<double> hk(size_t(n) * n), hd(n, 0.0), hr(size_t(n) + 1, 0.0);
+    dev_copy2d(c.dev, hk.data(), sizeof(double) * n, K, sizeof(double) * ldk, sizeof(double) * n, size_t(n), 1);
+    dev_d2h(c.dev, hd.data(), diag, sizeof(double) * size_t(n));
+    dev_sync(c.dev);
+    double t = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        double rs = 0;
+        for (int64_t j = 0; j < n; ++j) {
+            const double v = host_phi(s, hk[size_t(i) * n + j], hd[i], hd[j]);
+            hk[size_t(i) * n + j] = v;
+            rs += v;
+        }
+        hr[i] = rs / double(n);
+        t += hr[i];
+    }
+    hr[n] = t / double(n);
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < n; ++j) hk[size_t(i) * n + j] = ((hk[size_t(i) * n + j] - hr[i]) - hr[j]) + hr[n];
+    dev_copy2d(c.dev, K, sizeof(double) * ldk, hk.data(), sizeof(double) * n, sizeof(double) * n, size_t(n), 0);
+    dev_h2d(c.dev, rbar, hr.data(), sizeof(double) * size_t(n));
+    dev_h2d(c.dev, tbar, &hr[n], sizeof(double));
+    dev_sync(c.dev);
+    return false;
+}
+void kpca_usable(const petal_ctx& c, const petal_kpca& h) {
+    if (h.owner != &c) invalid_input("the KernelPca handle belongs to another ctx");
+}
+}  // namespace
+
+void kpca_destroy(petal_kpca* h) {
+    Dev* dv = h->owner->dev;
+    if (h->xt) dev_free(dv, h->xt);
+    if (h->cen) dev_free(dv, h->cen);
+    if (h->diag) dev_free(dv, h->diag);
+    if (h->a) dev_free(dv, h->a);
+    if (h->epi) dev_free(dv, h->epi);
+    delete h;
+}
+
+petal_kpca* kpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const KernelSpec& spec, const petal_matrix* y_out) {
+    const Timer timer = start_fit(c, x);
+    if (k < 0) invalid_input("negative parameter");
+    if (sharded(c)) invalid_input("KernelPca: a sharded ctx is not supported in this version");
+    const int dt = x.dtype;
+    const int64_t n = x.rows, d = x.cols;
+    if (n == 0 || d == 0) invalid_input("KernelPca: the input has no rows or no columns");
+    if (n < k) invalid_input("every dimension should be at least " + std::to_string(k));   // (d < k is legal: K is n x n)
+    if (n > (int64_t(1) << 15)) invalid_input("KernelPca: too many rows (the kernel matrix is n x n)");
+    const KernelSpec s = resolve_spec(spec, d);
+    if (y_out) check_output(*y_out, dt, n, k);
+    const size_t esz = dtype_size(dt);
+    const DevMat X = ingest(c, x);
+    const int64_t dp = X.dp, np = round_up(n, 16), np32 = round_up(n, 32), lda = round_up(k + 1, 64);
+    // the model's own copy of the training rows (a zero-copy tensor stays the caller's)
+    DBuf xt(c.dev, esz * size_t(n) * dp), cen, diag(c.dev, sizeof(double) * np), A(c.dev, sizeof(double) * size_t(np32) * lda);
+    DBuf epi(c.dev, sizeof(double) * size_t(2 * lda + 1 + n));
+    dev_copy2d(c.dev, xt.p, size_t(dp) * esz, X.p, size_t(X.ld) * esz, size_t(dp) * esz, size_t(n), 2);
+    if (s.kernel == PETAL_KERNEL_RBF) {
+        DBuf muT;
+        column_means(c, X, double(n), true, cen, muT);
+    } else {
+        cen = DBuf(c.dev, sizeof(double) * dp);
+        dev_memset(c.dev, cen.p, 0, cen.bytes);
+    }
+    DBuf K(c.dev, sizeof(double) * np * np), V(c.dev, sizeof(double) * np * np), lam(c.dev, sizeof(double) * np);
+    DBuf sig(c.dev, sizeof(double) * np), inv(c.dev, sizeof(double) * np), dk(c.dev, sizeof(double) * np);
+    dev_memset(c.dev, K.p, 0, K.bytes);   // (the eigen-solvers read the zero padding)
+    row_gram_into(c, X, s.kernel == PETAL_KERNEL_RBF ? cen.f64() : nullptr, K.f64(), np, c.kpca_fallback);
+    dev_copy2d(c.dev, diag.p, sizeof(double), K.p, (np + 1) * sizeof(double), sizeof(double), size_t(np), 2);
+    double *ra = epi.f64(), *oa = ra + lda, *tbar = oa + lda, *rbar = tbar + 1;
+    const bool mapped = kpca_map_into(c, s, K.f64(), n, np, diag.f64(), rbar, tbar);
+    // non-finite input leaves here ("did not converge", as the dual route): the trace of K~ and -- tanh and exp map an infinity to a
+    // finite number -- the trace of G, read before the eigenproblem instead of sending a matrix of NaNs through the solvers
+    std::vector<double> hdg(np), hdk(np);
+    dev_copy2d(c.dev, dk.p, sizeof(double), K.p, (np + 1) * sizeof(double), sizeof(double), size_t(np), 2);
+    dev_d2h(c.dev, hdg.data(), diag.p, diag.bytes);
+    dev_d2h(c.dev, hdk.data(), dk.p, dk.bytes);
+    dev_sync(c.dev);
+    double tg = 0, tk = 0;
+    for (int64_t i = 0; i < n; ++i) { tg += hdg[i]; tk += hdk[i]; }
+    if (!std::isfinite(tg) || !std::isfinite(tk)) linalg_error("did not converge");
+    const bool topk = gram_eigen(c, dt, K, n, np, k, dk, V, lam, nullptr).topk;
+    op_sigma_inv(c.dev, lam.f64(), sig.f64(), inv.f64(), np, dt == F32 ? 1e-6 : 1e-10);
+    // K~ 1 = 0 BY STRUCTURE: the n-th eigenvalue is the rounding of K~ and its component a zero column, whatever its computed size
+    if (k >= n) dev_memset(c.dev, inv.f64() + (n - 1), 0, sizeof(double));
+    const std::vector<double> sg = flip_signs(c, F64, V.p, n, k, np, 0);
+    const int64_t kk = std::max<int64_t>(k, 1);
+    std::vector<double> hv(size_t(n) * kk, 0.0), hsig(np), hinv(np), hlam(np), ha(size_t(np32) * lda, 0.0);
+    double htbar = 0;
+    if (k > 0) dev_copy2d(c.dev, hv.data(), sizeof(double) * k, V.p, sizeof(double) * np, sizeof(double) * k, size_t(n), 1);
+    dev_d2h(c.dev, hsig.data(), sig.p, sig.bytes);
+    dev_d2h(c.dev, hinv.data(), inv.p, inv.bytes);
+    dev_d2h(c.dev, hlam.data(), lam.p, lam.bytes);
+    dev_d2h(c.dev, &htbar, tbar, sizeof(double));
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < n; ++i) {
+        for (int64_t j = 0; j < k; ++j) ha[size_t(i) * lda + j] = hv[size_t(i) * k + j] * sg[j] * hinv[j];
+        ha[size_t(i) * lda + k] = 1.0;
+    }
+    dev_h2d(c.dev, A.p, ha.data(), A.bytes);
+    // rbar^T A' and 1^T A' (zero in exact arithmetic: K~ 1 = 0; computed anyway), once per fit
+    const DBuf ones = device_ones(c, n);
+    op_dgemm(c.dev, true, false, 1, lda, n, 1.0, rbar, 1, A.f64(), lda, 0.0, ra, lda);
+    op_dgemm(c.dev, true, false, 1, lda, n, 1.0, ones.f64(), 1, A.f64(), lda, 0.0, oa, lda);
+    if (y_out && k > 0) {   // fit_transform = V sqrt(lambda), a zero column where the component is undetermined; rounded once
+        std::vector<double> hy(size_t(n) * k);
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t j = 0; j < k; ++j) hy[size_t(i) * k + j] = hinv[j] != 0.0 ? hv[size_t(i) * k + j] * sg[j] * hsig[j] : 0.0;
+        DBuf yd(c.dev, sizeof(double) * size_t(n) * k), yt(c.dev, esz * size_t(n) * k);
+        dev_h2d(c.dev, yd.p, hy.data(), yd.bytes);
+        op_cvt_from_f64(c.dev, dt, yt.p, yd.f64(), n * k);
+        emit(c, dt, yt.p, n, k, k, *y_out);
+    }
+    std::unique_ptr<petal_kpca> h(new petal_kpca());
+    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->lda = lda; h->dtype = dt;
+    h->kernel = s.kernel; h->degree = s.degree; h->gamma = s.gamma; h->coef0 = s.coef0;
+    h->fit_kernel = mapped ? 1 : 0; h->order = n; h->topk = topk ? 1 : 0; h->tbar = htbar;
+    h->lam.assign(hlam.begin(), hlam.begin() + k);
+    finish_stats(c, timer);
+    h->xt = xt.p; xt.p = nullptr;
+    h->cen = cen.f64(); cen.p = nullptr;
+    h->diag = diag.f64(); diag.p = nullptr;
+    h->a = A.f64(); A.p = nullptr;
+    h->epi = epi.f64(); epi.p = nullptr;
+    return h.release();
+}
+
+void kpca_transform(petal_ctx& c, petal_kpca& h, const petal_matrix& x, const petal_matrix& y_out) {
+    kpca_usable(c, h);
+    const Timer timer = start_fit(c, x);
+    if (x.dtype != h.dtype) invalid_input("input dtype differs from the KernelPca model's dtype");
+    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    const int dt = h.dtype;
+    const int64_t m = x.rows, k = h.k, n = h.n, lda = h.lda;
+    check_output(y_out, dt, m, k);
+    if (m == 0 || k == 0) { finish_stats(c, timer); return; }
+    const DevMat X = ingest(c, x);
+    const int64_t ldo = k + 1;
+    const KernelSpec s{h.kernel, h.degree, h.gamma, h.coef0};
+    DBuf O(c.dev, sizeof(double) * size_t(m) * ldo), Y(c.dev, dtype_size(dt) * size_t(m) * k);
+    const bool ran = kernel_apply_into(c, s, h.xt, n, h.dp, X, h.cen, h.diag, h.a, lda, k + 1, O.f64(), ldo);
+    h.last_kernel = ran ? 1 : 0;
+    const double *ra = h.epi, *oa = h.epi + lda, *tbar = oa + lda;
+    if (c.kpca_fallback || !op_kpca_finish(c.dev, dt, O.f64(), ldo, m, k, ra, oa, double(n), tbar, Y.p, k)) {
+        // Y = O[:, :k] + 1 (tbar oa - ra)^T - (O[:, k] / n) oa^T by two rank-one updates
+        DBuf Yd(c.dev, sizeof(double) * size_t(m) * k), w(c.dev, sizeof(double) * size_t(k));
+        const DBuf ones = device_ones(c, m);
+        dev_copy2d(c.dev, Yd.p, sizeof(double) * k, O.p, sizeof(double) * ldo, sizeof(double) * k, size_t(m), 2);
+        dev_d2d(c.dev, w.p, ra, w.bytes);
+        op_dscal(c.dev, w.f64(), k, -1.0);
+        op_daxpy(c.dev, k, h.tbar, oa, w.f64());
+        op_dgemm(c.dev, false, false, m, k, 1, 1.0, ones.f64(), 1, w.f64(), k, 1.0, Yd.f64(), k);
+        op_dgemm(c.dev, false, false, m, k, 1, -1.0 / double(n), O.f64() + k, ldo, oa, k, 1.0, Yd.f64(), k);
+        op_cvt_from_f64(c.dev, dt, Y.p, Yd.f64(), m * k);
+    }
+    emit(c, dt, Y.p, m, k, k, y_out);
+    finish_stats(c, timer);
+}
+
+void kpca_get(const petal_kpca& h, double* eigenvalues, double* scaled_vectors, int64_t* info8) {
+    if (eigenvalues) std::copy(h.lam.begin(), h.lam.end(), eigenvalues);
+    if (scaled_vectors && h.k > 0) {
+        Dev* dv = h.owner->dev;
+        dev_copy2d(dv, scaled_vectors, sizeof(double) * h.k, h.a, sizeof(double) * h.lda, sizeof(double) * h.k, size_t(h.n), 1);
+        dev_sync(dv);
+    }
+    if (info8) {
+        const int64_t v[8] = {h.n, h.d, h.k, h.fit_kernel, h.last_kernel, h.order, h.kernel, h.topk};
+        std::copy(v, v + 8, info8);
+    }
+}
+
+void kernel_apply(petal_ctx& c, const petal_matrix& xq, const petal_matrix& xt, const KernelSpec& spec, const double* a, int64_t cols,
+                  const double* centre, double* out, int64_t* info1) {
+    check_matrix(xq, "xq");
+    check_matrix(xt, "xt");
+    if (info1) info1[0] = 0;
+    if (sharded(c)) invalid_input("kernel_apply: a sharded ctx is not supported in this version");
+    if (xq.dtype != xt.dtype) invalid_input("xq and xt should have the same dtype");
+    if (xq.cols != xt.cols) invalid_input("# of columns should be " + std::to_string(xt.cols));
+    if (cols < 0) invalid_input("negative parameter");
+    const int64_t m = xq.rows, n = xt.rows, d = xt.cols;
+    const KernelSpec s = resolve_spec(spec, d);
+    if (m == 0 || cols == 0) return;
+    if (!out || !a) invalid_input("a and out must not be null");
+    if (n == 0) { std::fill(out, out + m * cols, 0.0); return; }
+    if (d == 0) invalid_input("kernel_apply: the input has no columns");
+    const DevMat Xq = ingest(c, xq), Xt = ingest(c, xt);
+    const int64_t dp = Xt.dp, np32 = round_up(n, 32), lda = round_up(cols, 64);
+    std::vector<double> hc(size_t(dp), 0.0), ha(size_t(np32) * lda, 0.0);
+    if (centre) std::copy(centre, centre + d, hc.begin());
+    for (int64_t i = 0; i < n; ++i) std::copy(a + i * cols, a + (i + 1) * cols, ha.begin() + i * lda);
+    DBuf cen(c.dev, sizeof(double) * dp), A(c.dev, sizeof(double) * ha.size());
+    dev_h2d(c.dev, cen.p, hc.data(), cen.bytes);
+    dev_h2d(c.dev, A.p, ha.data(), A.bytes);
+    // the result is formed inside a guard: an odd pitch, a row more, every byte 0xFF beforehand.  What lies outside the m x cols block
+    // must come back untouched.
+    const int64_t ldo = cols + 3, rows = m + 1;
+    DBuf O(c.dev, sizeof(double) * size_t(rows) * ldo);
+    dev_memset(c.dev, O.p, 0xFF, O.bytes);
+    const bool ran = kernel_apply_into(c, s, Xt.p, n, Xt.ld, Xq, cen.f64(), nullptr, A.f64(), lda, cols, O.f64(), ldo);
+    std::vector<double> h(size_t(rows) * ldo);
+    dev_d2h(c.dev, h.data(), O.p, O.bytes);
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < rows; ++i)
+        for (int64_t j = (i < m ? cols : 0); j < ldo; ++j) {
+            uint64_t bits = 0;
+            std::memcpy(&bits, &h[size_t(i) * ldo + j], 8);
+            if (bits != ~uint64_t(0)) device_error("kernel_apply wrote outside the m x cols block");
+        }
+    for (int64_t i = 0; i < m; ++i) std::copy(h.begin() + i * ldo, h.begin() + i * ldo + cols, out + i * cols);
+    if (info1) info1[0] = ran ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------

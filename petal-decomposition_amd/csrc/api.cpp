@@ -10,6 +10,7 @@
 #include "../../include/petal_hip_sparse.h"
 #include "../../include/petal_hip_ipca.h"
 #include "../../include/petal_hip_wide.h"
+#include "../../include/petal_hip_kpca.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -148,6 +149,7 @@ int petal_ctx_set_option(petal_ctx* ctx, int option, double value) {
             return;
         }
         if (option == PETAL_OPT_PCA_DUAL_FALLBACK) { ctx->pca_dual_fallback = value != 0; return; }
+        if (option == PETAL_OPT_KPCA_FALLBACK) { ctx->kpca_fallback = value != 0; return; }
         if (option < 0 || option >= OPT_COUNT || !(value == value)) invalid_input("unknown ctx option or NaN value");
         dev_set_option(ctx->dev, option, value);
     });
@@ -159,6 +161,7 @@ int petal_ctx_get_option(const petal_ctx* ctx, int option, double* value) {
     if (option == PETAL_OPT_IPCA_FALLBACK) { *value = ctx->ipca_fallback ? 1.0 : 0.0; return PETAL_OK; }
     if (option == PETAL_OPT_PCA_DUAL) { *value = double(ctx->pca_dual); return PETAL_OK; }
     if (option == PETAL_OPT_PCA_DUAL_FALLBACK) { *value = ctx->pca_dual_fallback ? 1.0 : 0.0; return PETAL_OK; }
+    if (option == PETAL_OPT_KPCA_FALLBACK) { *value = ctx->kpca_fallback ? 1.0 : 0.0; return PETAL_OK; }
     if (option < 0 || option >= OPT_COUNT) return PETAL_INVALID_INPUT;
     *value = dev_option(ctx->dev, option);
     return PETAL_OK;
@@ -343,6 +346,46 @@ int petal_row_gram(petal_ctx* ctx, const petal_matrix* x, const double* centre, 
     return guarded(ctx, [&] {
         need(x, "x");
         row_gram(*ctx, *x, centre, out, info2);
+    });
+}
+
+// ---- include/petal_hip_kpca.h: KernelPca ---------------------------------------------------------------------------------------------
+int petal_kpca_fit(petal_ctx* ctx, const petal_matrix* x, int64_t k, const petal_kernel_spec* spec, petal_kpca** out,
+                   const petal_matrix* y_out) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(spec, "spec");
+        need(out, "out");
+        *out = kpca_fit(*ctx, *x, k, KernelSpec{spec->kernel, spec->degree, spec->gamma, spec->coef0}, y_out);
+    });
+}
+void petal_kpca_destroy(petal_kpca* h) {
+    if (!h) return;
+    try {
+        DeviceScope scope(h->owner->dev);
+        kpca_destroy(h);
+    } catch (...) {}
+}
+int petal_kpca_transform(petal_ctx* ctx, petal_kpca* h, const petal_matrix* x, const petal_matrix* y_out) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        need(x, "x");
+        need(y_out, "y_out");
+        kpca_transform(*ctx, *h, *x, *y_out);
+    });
+}
+int petal_kpca_get(const petal_kpca* h, double* eigenvalues, double* scaled_vectors, int64_t* info8) {
+    if (!h) return PETAL_INVALID_INPUT;
+    return guarded(h->owner, [&] { kpca_get(*h, eigenvalues, scaled_vectors, info8); });
+}
+int petal_kernel_apply(petal_ctx* ctx, const petal_matrix* xq, const petal_matrix* xt, const petal_kernel_spec* spec, const double* a,
+                       int64_t cols, const double* centre, double* out, int64_t* info1) {
+    return guarded(ctx, [&] {
+        need(xq, "xq");
+        need(xt, "xt");
+        need(spec, "spec");
+        kernel_apply(*ctx, *xq, *xt, KernelSpec{spec->kernel, spec->degree, spec->gamma, spec->coef0}, a, cols, centre, out, info1);
     });
 }
 

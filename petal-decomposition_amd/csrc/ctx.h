@@ -22,6 +22,7 @@ struct petal_ctx {
     int pca_dual = 0;                // PETAL_OPT_PCA_DUAL (include/petal_hip_wide.h): 0 the auto rule, 1 always (non-sharded), -1 never
     bool pca_dual_fallback = false;  // PETAL_OPT_PCA_DUAL_FALLBACK: a test aid
     int64_t pca_route[4] = {0, 0, 0, 0};   // petal_pca_last_route: route, kernel, order of the eigenproblem, feature chunks
+    bool kpca_fallback = false;      // PETAL_OPT_KPCA_FALLBACK (include/petal_hip_kpca.h): a test aid
     bool force_collective = false;   // PETAL_OPT_FORCE_COLLECTIVE (default: env PETAL_FORCE_COLLECTIVE at petal_ctx_create)
     petal_stats stats{};
     void* rccl = nullptr;  // the built-in RCCL communicator (rccl.cpp), when petal_ctx_init_rccl installed it
@@ -60,6 +61,22 @@ struct petal_ipca {
     int64_t batches = 0, kernel_batches = 0, merges = 0;
     double* mean = nullptr;              // device fp64, dp (zero when centering is off)
     double* m2 = nullptr;                // device fp64, dp x dp, symmetric, both triangles
+};
+
+// include/petal_hip_kpca.h: a fitted KernelPca, resident with its ctx
+struct petal_kpca {
+    petal_ctx* owner = nullptr;
+    int64_t n = 0, d = 0, dp = 0, k = 0, lda = 0;
+    int dtype = 0, kernel = 0, degree = 3;
+    double gamma = 0, coef0 = 1;         // as resolved at the fit (gamma <= 0 -> 1 / d)
+    int64_t fit_kernel = 0, last_kernel = -1, order = 0, topk = 0;   // topk: gram_eigen's top-k subspace iteration delivered the eigenpairs (0: the full eigen-solver ran)
+    void* xt = nullptr;                  // device, n x dp in dtype (ld = dp): the model's OWN copy of the training rows
+    double* cen = nullptr;               // device fp64, dp: the centre c (zeros unless rbf)
+    double* diag = nullptr;              // device fp64, n: diag(G) = |x_i - c|^2
+    double* a = nullptr;                 // device fp64, round_up(n, 32) x lda: A' = [V lambda^(-1/2) | 1], zero padded
+    double* epi = nullptr;               // device fp64, n + 1 + 2 lda: [rbar | tbar | rbar^T A' | 1^T A']
+    double tbar = 0;
+    std::vector<double> lam;             // k eigenvalues, as computed
 };
 
 namespace petal {
@@ -151,6 +168,14 @@ void transform_csr(petal_ctx& c, const petal_csr& x, const void* components, con
 void csr_gemm(petal_ctx& c, const petal_csr& x, bool transposed, const double* P, int64_t N, const double* a, const double* s, double* out);
 // include/petal_hip_wide.h: the row Gram matrix of exact Pca's dual route by itself (a test aid)
 void row_gram(petal_ctx& c, const petal_matrix& x, const double* centre, double* out, int64_t* info2);
+// include/petal_hip_kpca.h: KernelPca
+struct KernelSpec { int kernel; int degree; double gamma, coef0; };
+petal_kpca* kpca_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const KernelSpec& spec, const petal_matrix* y_out);
+void kpca_destroy(petal_kpca* h);
+void kpca_transform(petal_ctx& c, petal_kpca& h, const petal_matrix& x, const petal_matrix& y_out);
+void kpca_get(const petal_kpca& h, double* eigenvalues, double* scaled_vectors, int64_t* info8);
+void kernel_apply(petal_ctx& c, const petal_matrix& xq, const petal_matrix& xt, const KernelSpec& spec, const double* a, int64_t cols,
+                  const double* centre, double* out, int64_t* info1);
 // include/petal_hip_ipca.h: IncrementalPca
 petal_ipca* ipca_create(petal_ctx& c, int64_t d, int32_t dtype, bool centering);
 void ipca_destroy(petal_ipca* h);

@@ -213,6 +213,28 @@ bool op_ipca_merge(Dev*, int64_t dp, double n_a, double* M2_a, const double* mea
 // op_cvt_to_f64 and op_dgemm.
 bool op_row_gram(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64_t ldx, const double* centre, double* K, int64_t ldk,
                  int64_t* chunks);
+// KernelPca (include/petal_hip_kpca.h; an extension beyond the crate).  kernel = PETAL_KERNEL_* with (gamma, coef0, degree) already
+// resolved.  Each returns "this layer did the work": false, NOTHING done, where a matrix does not allow 16-byte loads along its rows or
+// the layer lacks the op -- algo.cpp's weak defaults return false and the caller builds the same statement from op_cvt_to_f64, op_dgemm
+// and a phi loop on the host.
+// The fit's map: the leading n x n block of K (ldk; nothing outside it is written) holds the row Gram matrix G on entry and
+//     K~_ij = phi(G_ij, diag_i, diag_j) - rbar_i - rbar_j + tbar
+// on return; diag (n, DEVICE) = the diagonal of G set aside by the caller, rbar (n) / tbar (1) receive the column means and the grand
+// mean of K.  The row sums are formed in a fixed order: no atomics.
+bool op_kpca_map(Dev*, int kernel, double gamma, double coef0, int degree, double* K, int64_t n, int64_t ldk, const double* diag,
+                 double* rbar, double* tbar);
+// The fused pass: out (m x cols fp64, ldo; nothing outside that block is written) = phi((Xq - c)(Xt - c)^T) A.  Xt: n x dp, ldt; Xq:
+// m x dp, ldq; both in dtype, dp a multiple of 16 whose padding columns hold zeros.  centre: DEVICE fp64, dp values (zeros: no centring;
+// never null).  nt (nullable: formed here): DEVICE fp64, n values |xt_i - c|^2, read by rbf and cosine.  A: DEVICE fp64 with
+// round_up(n, 32) readable rows and lda >= round_up(cols, 64), ZERO outside the leading n x cols block.  The m x n matrix in between
+// never touches memory; every product and sum is fp64, in an order the shape alone fixes.
+bool op_kernel_apply(Dev*, int dtype, const void* Xt, int64_t n, int64_t ldt, const void* Xq, int64_t m, int64_t ldq, int64_t dp,
+                     const double* centre, const double* nt, int kernel, double gamma, double coef0, int degree, const double* A, int64_t lda,
+                     int64_t cols, double* out, int64_t ldo);
+// transform's epilogue: Y (m x k in dtype, ldy) = O_ij - ra_j - (O_ik / n - *tbar) oa_j from the fused pass's output O (m x >= k + 1
+// fp64, ldo; column k = the row sums of Kq); ra, oa, tbar: DEVICE fp64.  Rounded once to dtype.
+bool op_kpca_finish(Dev*, int dtype, const double* O, int64_t ldo, int64_t m, int64_t k, const double* ra, const double* oa, double n,
+                    const double* tbar, void* Y, int64_t ldy);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.
