@@ -27,6 +27,7 @@
 #include "petal_hip_ipca.h"
 #include "petal_hip_wide.h"
 #include "petal_hip_kpca.h"
+#include "petal_hip_nmf.h"
 
 namespace petal_decomposition {
 
@@ -551,6 +552,107 @@ class KernelPca {
     petal_kernel_spec spec_{};
     Context* ctx_;
     petal_kpca* h_ = nullptr;
+};
+
+// Non-negative matrix factorisation X ~ W H (petal_hip_nmf.h: an extension beyond the crate; scikit-learn's NMF(solver="mu",
+// beta_loss="frobenius")).  alpha_w, alpha_h (negative: the same as alpha_w) and l1_ratio are scikit-learn's penalties.  fit(x) draws
+// W0 and H0 from Pcg(seed); fit(x, w0, h0) starts from the caller's.  tol > 0 stops at a check every 10th iteration; transform runs
+// exactly max_iter W-updates in one pass over its input.  The fitted model lives with its ctx (destroy the model before the Context).
+struct NmfInfo {
+    int64_t n = 0, d = 0, k = 0, n_iter = 0;
+    bool fit_kernel = false;        // k_nmf_pass ran in the fit (false: the composed path)
+    int transform_kernel = -1;      // the same for the last transform (1 / 0; -1 before the first)
+};
+
+template <class A>
+class Nmf {
+  public:
+    explicit Nmf(int64_t n_components, int64_t max_iter = 200, double tol = 1e-4, uint64_t seed = 0, double alpha_w = 0.0,
+                 double alpha_h = -1.0, double l1_ratio = 0.0, Context* ctx = nullptr)
+        : k_(n_components), max_iter_(max_iter), tol_(tol), seed_(seed), alpha_w_(alpha_w), alpha_h_(alpha_h < 0 ? alpha_w : alpha_h),
+          l1_ratio_(l1_ratio), ctx_(ctx) {}
+    Nmf(const Nmf&) = delete;
+    Nmf& operator=(const Nmf&) = delete;
+    Nmf(Nmf&& o) noexcept
+        : k_(o.k_), max_iter_(o.max_iter_), tol_(o.tol_), seed_(o.seed_), alpha_w_(o.alpha_w_), alpha_h_(o.alpha_h_), l1_ratio_(o.l1_ratio_),
+          ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    ~Nmf() { petal_nmf_destroy(h_); }
+    Nmf& fit(const Array2<A>& input) { inner_fit(input, nullptr, nullptr, nullptr); return *this; }
+    Nmf& fit(const Array2<A>& input, const Array2<A>& w0, const Array2<A>& h0) { inner_fit(input, &w0, &h0, nullptr); return *this; }
+    Array2<A> fit_transform(const Array2<A>& input) {
+        Array2<A> w(input.nrows(), k_);
+        inner_fit(input, nullptr, nullptr, &w);
+        return w;
+    }
+    Array2<A> fit_transform(const Array2<A>& input, const Array2<A>& w0, const Array2<A>& h0) {
+        Array2<A> w(input.nrows(), k_);
+        inner_fit(input, &w0, &h0, &w);
+        return w;
+    }
+    Array2<A> transform(const Array2<A>& input) {
+        Array2<A> w(input.nrows(), k_);
+        petal_matrix mx = input.view(), mw = w.view();
+        context().check(petal_nmf_transform(context().get(), handle(), &mx, &mw));
+        return w;
+    }
+    Array2<A> inverse_transform(const Array2<A>& w) {
+        Array2<A> x(w.nrows(), info().d);
+        petal_matrix mw = w.view(), mx = x.view();
+        context().check(petal_nmf_inverse_transform(context().get(), handle(), &mw, &mx));
+        return x;
+    }
+    int64_t n_components() const { return k_; }
+    // H, k x d, float64
+    Array2<double> components() const {
+        const NmfInfo in = info();
+        Array2<double> h(in.k, in.d);
+        if (petal_nmf_get(handle(), h.data.data(), nullptr, nullptr) != PETAL_OK)
+            throw DecompositionError(DecompositionError::InvalidInput, "petal_nmf_get failed");
+        return h;
+    }
+    int64_t n_iter() const { return info().n_iter; }
+    double reconstruction_err() const {
+        double e[2] = {0, 0};
+        if (petal_nmf_get(handle(), nullptr, nullptr, e) != PETAL_OK)
+            throw DecompositionError(DecompositionError::InvalidInput, "petal_nmf_get failed");
+        return e[0];
+    }
+    NmfInfo info() const {
+        int64_t v[6] = {0, 0, 0, 0, 0, 0};
+        if (petal_nmf_get(handle(), nullptr, v, nullptr) != PETAL_OK)
+            throw DecompositionError(DecompositionError::InvalidInput, "petal_nmf_get failed");
+        NmfInfo r;
+        r.n = v[0]; r.d = v[1]; r.k = v[2]; r.n_iter = v[3]; r.fit_kernel = v[4] != 0; r.transform_kernel = int(v[5]);
+        return r;
+    }
+
+  private:
+    Context& context() const { return ctx_ ? *ctx_ : Context::global(); }
+    petal_nmf* handle() const {
+        if (!h_) throw DecompositionError(DecompositionError::InvalidInput, "the model has not been fitted");
+        return h_;
+    }
+    void inner_fit(const Array2<A>& input, const Array2<A>* w0, const Array2<A>* h0, Array2<A>* w) {
+        petal_matrix mx = input.view(), m0{}, m1{}, mw{};
+        if (w0) { m0 = w0->view(); m1 = h0->view(); }
+        if (w) mw = w->view();
+        const double n = double(input.nrows()), d = double(input.ncols());
+        petal_nmf_spec spec{};
+        spec.max_iter = max_iter_; spec.tol = tol_;
+        spec.l1_w = d * alpha_w_ * l1_ratio_; spec.l2_w = d * alpha_w_ * (1.0 - l1_ratio_);
+        spec.l1_h = n * alpha_h_ * l1_ratio_; spec.l2_h = n * alpha_h_ * (1.0 - l1_ratio_);
+        petal_nmf* h = nullptr;
+        context().check(petal_nmf_fit(context().get(), &mx, k_, &spec, w0 ? &m0 : nullptr, w0 ? &m1 : nullptr, int64_t(seed_), &h,
+                                      w ? &mw : nullptr));
+        petal_nmf_destroy(h_);
+        h_ = h;
+    }
+    int64_t k_, max_iter_;
+    double tol_;
+    uint64_t seed_;
+    double alpha_w_, alpha_h_, l1_ratio_;
+    Context* ctx_;
+    petal_nmf* h_ = nullptr;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

@@ -33,7 +33,8 @@ OPTIONS = {"two_plane_operands": 0, "two_plane_omega": 1, "two_plane_iterate": 2
            "d2h_kernel": 10, "row_pad": 11, "eigh_jacobi": 12, "poison": 13, "force_collective": 14, "steering_hook": 15,
            "ipca_fallback": 32,   # (32: PETAL_OPT_IPCA_FALLBACK, include/petal_hip_ipca.h -- a test aid)
            "pca_dual": 33, "pca_dual_fallback": 34,   # (PETAL_OPT_PCA_DUAL, PETAL_OPT_PCA_DUAL_FALLBACK: include/petal_hip_wide.h)
-           "kpca_fallback": 36}   # (PETAL_OPT_KPCA_FALLBACK, include/petal_hip_kpca.h -- a test aid)
+           "kpca_fallback": 36,   # (PETAL_OPT_KPCA_FALLBACK, include/petal_hip_kpca.h -- a test aid)
+           "nmf_fallback": 38}   # (PETAL_OPT_NMF_FALLBACK, include/petal_hip_nmf.h -- a test aid; 37 stays unknown)
 ICA_TEXTBOOK, ICA_REFERENCE_LITERAL = 0, 1
 # the contrast function of the FastICA iteration: bits 4-7 of the same `mode` argument (include/petal_hip.h); EXP and CUBE are an
 # extension beyond the crate, whose only contrast is logcosh
@@ -210,6 +211,23 @@ ABI_KPCA = [
     ("petal_kernel_apply", C.c_int, [_P, _M, _M, _KS, _D, C.c_int64, _D, _D, _L]),
 ]
 
+# every symbol include/petal_hip_nmf.h declares (Nmf and its fused pass by itself)
+class petal_nmf_spec(C.Structure):
+    _fields_ = [("max_iter", C.c_int64), ("tol", C.c_double), ("l1_w", C.c_double), ("l2_w", C.c_double), ("l1_h", C.c_double),
+                ("l2_h", C.c_double)]
+
+
+_NS = C.POINTER(petal_nmf_spec)
+ABI_NMF = [
+    ("petal_nmf_fit", C.c_int, [_P, _M, C.c_int64, _NS, _M, _M, C.c_int64, C.POINTER(C.c_void_p), _M]),
+    ("petal_nmf_destroy", None, [_P]),
+    ("petal_nmf_transform", C.c_int, [_P, _P, _M, _M]),
+    ("petal_nmf_inverse_transform", C.c_int, [_P, _P, _M, _M]),
+    ("petal_nmf_get", C.c_int, [_P, _D, _L, _D]),
+    ("petal_nmf_pass", C.c_int, [_P, _M, C.c_int64, _D, _D, _NS, C.c_int64, _D, _D, _D, _L]),
+]
+
+
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
     file name, so a process that first loads the system HIP runtime (through this library) and then imports
@@ -226,7 +244,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -235,7 +253,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -332,10 +350,12 @@ class Context:
         self._csr = weakref.WeakSet()   # the sparse matrices resident with this ctx: released before it
         self._ipca = weakref.WeakSet()  # ... and the IncrementalPca statistics
         self._kpca = weakref.WeakSet()  # ... and the fitted KernelPca models
+        self._nmf = weakref.WeakSet()   # ... and the fitted Nmf models
 
     def close(self):
         if getattr(self, "_h", None):
-            for m in list(getattr(self, "_csr", ())) + list(getattr(self, "_ipca", ())) + list(getattr(self, "_kpca", ())):
+            for m in list(getattr(self, "_csr", ())) + list(getattr(self, "_ipca", ())) + list(getattr(self, "_kpca", ())) + \
+                    list(getattr(self, "_nmf", ())):
                 m.close()
             self.lib.petal_ctx_destroy(self._h)
             self._h = None
@@ -755,6 +775,176 @@ class KernelPca:
         full eigen-solver of order n ran -- the slower fit)."""
         keys = ("n", "d", "k", "fit_kernel", "transform_kernel", "order", "kernel", "topk_solver")
         return dict(zip(keys, (int(v) for v in self._get())))
+
+
+def _nmf_spec(max_iter, tol, l1_w, l2_w, l1_h=0.0, l2_h=0.0) -> petal_nmf_spec:
+    return petal_nmf_spec(int(max_iter), float(tol), float(l1_w), float(l2_w), float(l1_h), float(l2_h))
+
+
+def nmf_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, want_ab=True, ctx: Optional["Context"] = None, want_info: bool = False):
+    """Test aid (``petal_nmf_pass``, include/petal_hip_nmf.h): the fused pass of an ``Nmf`` iteration by itself, in float64.  ``x``
+    (n x d): numpy or ``torch.cuda``, any strides; ``w`` (n x k), ``h`` (k x d): float64.  Z = x h^T once, then ``inner_iters`` times
+    D = W (h h^T) + l1_w + l2_w W, D[D == 0] = 2^-23, W <- W o Z / D.  Returns ``(w_new, a, b)`` with a = w_new^T x and
+    b = w_new^T w_new (``want_ab=False``: ``w_new`` alone).  ``want_info``: also ``{"kernel": k_nmf_pass ran}``."""
+    keep = []
+    mx = describe(x, keep)
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+    h = np.ascontiguousarray(np.asarray(h, dtype=np.float64))
+    if w.ndim != 2 or h.ndim != 2 or w.shape[0] != mx.rows or h.shape != (w.shape[1], mx.cols):
+        raise InvalidInput(f"w should be {mx.rows} x k and h k x {mx.cols}")
+    k = w.shape[1]
+    spec = _nmf_spec(1, 0.0, l1_w, l2_w)
+    wo = np.zeros((mx.rows, k))
+    a = np.zeros((k, mx.cols)) if want_ab else None
+    b = np.zeros((k, k)) if want_ab else None
+    info = (C.c_int64 * 1)()
+    ctx.check(ctx.lib.petal_nmf_pass(ctx._h, C.byref(mx), k, w.ctypes.data_as(_D), h.ctypes.data_as(_D), C.byref(spec), int(inner_iters),
+                                     wo.ctypes.data_as(_D), a.ctypes.data_as(_D) if want_ab else None,
+                                     b.ctypes.data_as(_D) if want_ab else None, info))
+    out = (wo, a, b) if want_ab else wo
+    return (out, {"kernel": int(info[0])}) if want_info else out
+
+
+class Nmf:
+    """Non-negative matrix factorisation X ~ W H (``petal_nmf``, include/petal_hip_nmf.h; an extension beyond the crate, DESIGN.md
+    sections 4 and 7) -- scikit-learn's ``NMF(solver="mu", beta_loss="frobenius")``.  ``init="random"`` draws W0 and H0 from
+    ``Pcg(seed)``; ``init="custom"`` takes them from ``fit_transform(x, W=..., H=...)``.  ``alpha_W``, ``alpha_H`` ("same": alpha_W)
+    and ``l1_ratio`` are scikit-learn's penalties.  ``tol > 0`` stops at a check every 10th iteration; ``transform`` runs exactly
+    ``max_iter`` W-updates in one pass over its input.  Everything is float64 inside; outputs are rounded once to the data's type.
+    The fitted model lives with its ctx."""
+
+    def __init__(self, n_components: int, max_iter: int = 200, tol: float = 1e-4, init: str = "random", seed: int = 0,
+                 alpha_W: float = 0.0, alpha_H="same", l1_ratio: float = 0.0, ctx: Optional[Context] = None):
+        if init not in ("random", "custom"):
+            raise InvalidInput(f"unknown init {init!r} (random or custom)")
+        self._k = int(n_components)
+        self.max_iter, self.tol, self.init, self.seed = int(max_iter), float(tol), init, int(seed)
+        self.alpha_W, self.alpha_H, self.l1_ratio = float(alpha_W), alpha_H, float(l1_ratio)
+        self.ctx = ctx
+        self._h = None
+
+    def _ctx(self) -> Context:
+        if self.ctx is None:
+            self.ctx = default_context()
+        return self.ctx
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self.ctx.lib.petal_nmf_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise InvalidInput("the model has not been fitted (or its ctx was closed)")
+        return self._h
+
+    def n_components(self):
+        return self._k
+
+    def _spec(self, n, d) -> petal_nmf_spec:
+        a_w = self.alpha_W
+        a_h = a_w if isinstance(self.alpha_H, str) else float(self.alpha_H)
+        if isinstance(self.alpha_H, str) and self.alpha_H != "same":
+            raise InvalidInput("alpha_H should be a number or 'same'")
+        rho = self.l1_ratio
+        return _nmf_spec(self.max_iter, self.tol, d * a_w * rho, d * a_w * (1.0 - rho), n * a_h * rho, n * a_h * (1.0 - rho))
+
+    def _inner_fit(self, x, W, H, want_w: bool):
+        keep = []
+        mx = describe(x, keep)
+        ctx = self._ctx()
+        spec = self._spec(mx.rows, mx.cols)
+        mw = mh = None
+        if self.init == "custom":
+            if W is None or H is None:
+                raise InvalidInput("init='custom' needs W and H")
+            dt = _np_dtype(mx.dtype)
+            mw = describe(W if _is_torch(W) else np.asarray(W, dtype=dt), keep)
+            mh = describe(H if _is_torch(H) else np.asarray(H, dtype=dt), keep)
+        elif W is not None or H is not None:
+            raise InvalidInput("W and H are read with init='custom' only")
+        w, mo = None, None
+        if want_w:
+            w = _alloc_like(x, mx.rows, self._k, mx.dtype)
+            mo = describe(w, keep)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.petal_nmf_fit(ctx._h, C.byref(mx), self._k, C.byref(spec), C.byref(mw) if mw is not None else None,
+                                        C.byref(mh) if mh is not None else None, C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h),
+                                        C.byref(mo) if mo is not None else None))
+        self.close()
+        self._h = h
+        ctx._nmf.add(self)
+        return w
+
+    def fit(self, x, W=None, H=None):
+        self._inner_fit(x, W, H, False)
+        return self
+
+    def fit_transform(self, x, W=None, H=None):
+        return self._inner_fit(x, W, H, True)
+
+    def transform(self, x):
+        keep = []
+        mx = describe(x, keep)
+        ctx = self._ctx()
+        w = _alloc_like(x, mx.rows, self._k, mx.dtype)
+        mo = describe(w, keep)
+        ctx.check(ctx.lib.petal_nmf_transform(ctx._h, self._handle(), C.byref(mx), C.byref(mo)))
+        return w
+
+    def inverse_transform(self, w):
+        keep = []
+        mw = describe(w, keep)
+        ctx = self._ctx()
+        x = _alloc_like(w, mw.rows, self.info()["d"], mw.dtype)
+        mo = describe(x, keep)
+        ctx.check(ctx.lib.petal_nmf_inverse_transform(ctx._h, self._handle(), C.byref(mw), C.byref(mo)))
+        return x
+
+    def _get(self, comp=None, err=None):
+        h = self._handle()   # (first: an unfitted model may have no ctx yet)
+        out = (C.c_int64 * 6)()
+        if self._ctx().lib.petal_nmf_get(h, comp.ctypes.data_as(_D) if comp is not None else None, out,
+                                      err.ctypes.data_as(_D) if err is not None else None) != PETAL_OK:
+            raise InvalidInput("petal_nmf_get failed")
+        return out
+
+    def info(self) -> dict:
+        """n, d, k, ``n_iter``, ``fit_kernel`` (k_nmf_pass ran in the fit; 0: the composed path), ``transform_kernel`` (the same for
+        the last transform; -1 before the first)."""
+        keys = ("n", "d", "k", "n_iter", "fit_kernel", "transform_kernel")
+        return dict(zip(keys, (int(v) for v in self._get())))
+
+    @property
+    def components(self):
+        """H, k x d float64."""
+        i = self.info()
+        comp = np.zeros((i["k"], i["d"]))
+        self._get(comp=comp)
+        return comp
+
+    @property
+    def n_iter(self) -> int:
+        return self.info()["n_iter"]
+
+    @property
+    def reconstruction_err(self) -> float:
+        err = np.zeros(2)
+        self._get(err=err)
+        return float(err[0])
+
+    @property
+    def err_init(self) -> float:
+        err = np.zeros(2)
+        self._get(err=err)
+        return float(err[1])
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1541,6 +1541,425 @@ void kernel_apply(petal_ctx& c, const petal_matrix& xq, const petal_matrix& xt, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Nmf (include/petal_hip_nmf.h; DESIGN.md sections 4 and 7): multiplicative updates for the Frobenius loss.  An iteration is ONE fused
+// pass over X (k_nmf_pass through op_nmf_pass: Z = X H^T, the W rule, A = W^T X and B = W^T W with the new W) and the H side on k x d
+// operands (op_nmf_hupdate).  W (n x kp), H and A (kp x dp), H H^T and B (kp x kp) live on the device in fp64, zero in the padding.  A
+// device-op layer without the kernels (the host simulation), a shape outside their envelope and PETAL_OPT_NMF_FALLBACK build the same
+// statements from op_cvt_to_f64, op_dgemm and an element-wise step on the host over read-back copies, X in row blocks of bounded size.
+__attribute__((weak)) bool op_nmf_scan(Dev*, int, const void*, int64_t, int64_t, int64_t, double*) { return false; }
+__attribute__((weak)) bool op_nmf_pass(Dev*, int, const void*, int64_t, int64_t, int64_t, const double*, const double*, int64_t, int64_t, double*,
+                                       bool, double, double, double, int64_t, double*, double*) {
+    return false;
+}
+__attribute__((weak)) bool op_nmf_hupdate(Dev*, int64_t, int64_t, const double*, const double*, double*, double*, double, double, double*) {
+    return false;
+}
+namespace {
+constexpr double NMF_EPS = 1.1920928955078125e-07;            // 2^-23 for both data types
+constexpr int64_t NMF_FALLBACK_BLOCK = int64_t(1) << 22;      // doubles of the widened block of X a composed step holds (32 MiB)
+
+// rand_pcg::Mcg128Xsl64 + rand_distr::StandardNormal (256-layer Ziggurat): the stream of petal_decomposition.hpp's Pcg and of pcg.py
+class NmfPcg {
+  public:
+    explicit NmfPcg(uint64_t state) : state_((unsigned __int128)state | 1) {}
+    double standard_normal() {
+        static const Tables t;
+        for (;;) {
+            const uint64_t bits = next_u64();
+            const int i = int(bits & 0xff);
+            const double u = double(int64_t(bits >> 12)) * (2.0 / 4503599627370496.0) - 1.0;
+            const double x = u * t.x[i];
+            if (std::fabs(x) < t.x[i + 1]) return x;
+            if (i == 0) {
+                double xx = 1.0, yy = 0.0;
+                while (-2.0 * yy < xx * xx) {
+                    xx = std::log(open01()) / Tables::R;
+                    yy = std::log(open01());
+                }
+                return u < 0 ? xx - Tables::R : Tables::R - xx;
+            }
+            if (t.f[i + 1] + (t.f[i] - t.f[i + 1]) * (double(next_u64() >> 11) * (1.0 / 9007199254740992.0)) < std::exp(-0.5 * x * x)) return x;
+        }
+    }
+
+  private:
+    struct Tables {
+        static constexpr double R = 3.654152885361009;
+        double x[257], f[257];
+        Tables() {
+            const double v = 0.00492867323399;
+            x[0] = v / std::exp(-0.5 * R * R);
+            x[1] = R;
+            for (int i = 2; i < 256; ++i) x[i] = std::sqrt(-2.0 * std::log(v / x[i - 1] + std::exp(-0.5 * x[i - 1] * x[i - 1])));
+            x[256] = 0.0;
+            for (int i = 0; i < 257; ++i) f[i] = std::exp(-0.5 * x[i] * x[i]);
+        }
+    };
+    uint64_t next_u64() {
+        state_ *= (((unsigned __int128)0x2360ED051FC65DA4ull) << 64) | 0x4385DF649FCCF645ull;
+        const unsigned rot = unsigned(state_ >> 122);
+        const uint64_t x = uint64_t(state_ >> 64) ^ uint64_t(state_);
+        return (x >> rot) | (x << ((64 - rot) & 63));
+    }
+    double open01() { return double(next_u64() >> 12) * (1.0 / 4503599627370496.0) + (1.0 / 9007199254740992.0); }
+    unsigned __int128 state_;
+};
+
+// the one look at a matrix in front of a fit or a transform: sum, sum of squares, "a negative entry", "a NaN or an infinity"
+struct NmfScan { double sum = 0, sumsq = 0; bool negative = false, bad = false; };
+NmfScan nmf_scan(petal_ctx& c, const DevMat& X) {
+    NmfScan r;
+    if (X.n == 0) return r;
+    if (!c.nmf_fallback) {
+        DBuf o(c.dev, sizeof(double) * 4);
+        if (op_nmf_scan(c.dev, X.dtype, X.p, X.n, X.dp, X.ld, o.f64())) {
+            double h[4];
+            dev_d2h(c.dev, h, o.p, sizeof(h));
+            dev_sync(c.dev);
+            r.sum = h[0]; r.sumsq = h[1]; r.negative = h[2] < 0.0; r.bad = h[3] != 0.0;
+            return r;
+        }
+    }
+    const int64_t B = std::max<int64_t>(1, std::min(X.n, NMF_FALLBACK_BLOCK / X.ld));
+    const size_t esz = dtype_size(X.dtype);
+    DBuf Xb(c.dev, sizeof(double) * size_t((B - 1) * X.ld + X.dp));
+    std::vector<double> hx(size_t((B - 1) * X.ld + X.dp));
+    for (int64_t r0 = 0; r0 < X.n; r0 += B) {
+        const int64_t b = std::min(B, X.n - r0), count = (b - 1) * X.ld + X.dp;
+        op_cvt_to_f64(c.dev, X.dtype, Xb.f64(), static_cast<const char*>(X.p) + size_t(r0) * X.ld * esz, count);
+        dev_d2h(c.dev, hx.data(), Xb.p, sizeof(double) * size_t(count));
+        dev_sync(c.dev);
+        for (int64_t i = 0; i < b; ++i)
+            for (int64_t j = 0; j < X.dp; ++j) {
+                const double v = hx[size_t(i) * X.ld + j];
+                r.sum += v;
+                r.sumsq += v * v;
+                if (v < 0.0) r.negative = true;
+                if (!(v - v == 0.0)) r.bad = true;
+            }
+    }
+    return r;
+}
+void nmf_reject(const NmfScan& s) {
+    if (s.bad) linalg_error("did not converge");
+    if (s.negative) invalid_input("negative values in data");
+}
+
+// The pass (ops.h, op_nmf_pass): the kernel where the layer has it, else the same statement in row blocks.  Returns "k_nmf_pass ran".
+bool nmf_pass_into(petal_ctx& c, const DevMat& X, const double* H, const double* HHt, int64_t k, int64_t kp, double* W, bool from_const,
+                   double wconst, double l1, double l2, int64_t inner, double* A, double* B) {
+    const int64_t n = X.n, dp = X.dp, ld = X.ld;
+    if (!c.nmf_fallback) {
+        // (the one launch of an iteration under TAG_POW: with profiling on, stats.pow_ms is k_nmf_pass's own time)
+        dev_set_tag(c.dev, TAG_POW);
+        const bool ran = op_nmf_pass(c.dev, X.dtype, X.p, n, dp, ld, H, HHt, k, kp, W, from_const, wconst, l1, l2, inner, A, B);
+        dev_set_tag(c.dev, TAG_NONE);
+        if (ran) return true;
+    }
+    const int64_t Bk = std::max<int64_t>(1, std::min(n, NMF_FALLBACK_BLOCK / ld));
+    const size_t esz = dtype_size(X.dtype);
+    DBuf Xb(c.dev, sizeof(double) * size_t((Bk - 1) * ld + dp)), Z(c.dev, sizeof(double) * size_t(Bk) * kp), D(c.dev, sizeof(double) * size_t(Bk) * kp);
+    std::vector<double> hz(size_t(Bk) * kp), hd(size_t(Bk) * kp), hw(size_t(Bk) * kp);
+    if (A) {
+        dev_memset(c.dev, A, 0, sizeof(double) * size_t(kp) * dp);
+        dev_memset(c.dev, B, 0, sizeof(double) * size_t(kp) * kp);
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += Bk) {
+        const int64_t b = std::min(Bk, n - r0);
+        double* Wb = W + r0 * kp;
+        op_cvt_to_f64(c.dev, X.dtype, Xb.f64(), static_cast<const char*>(X.p) + size_t(r0) * ld * esz, (b - 1) * ld + dp);
+        if (from_const) {
+            for (int64_t i = 0; i < b; ++i)
+                for (int64_t j = 0; j < kp; ++j) hw[size_t(i) * kp + j] = j < k ? wconst : 0.0;
+            dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
+        }
+        if (inner > 0) {
+            op_dgemm(c.dev, false, true, b, kp, dp, 1.0, Xb.f64(), ld, H, dp, 0.0, Z.f64(), kp);
+            dev_d2h(c.dev, hz.data(), Z.p, sizeof(double) * size_t(b) * kp);
+        }
+        for (int64_t it = 0; it < inner; ++it) {
+            op_dgemm(c.dev, false, false, b, kp, kp, 1.0, Wb, kp, HHt, kp, 0.0, D.f64(), kp);
+            dev_d2h(c.dev, hd.data(), D.p, sizeof(double) * size_t(b) * kp);
+            dev_d2h(c.dev, hw.data(), Wb, sizeof(double) * size_t(b) * kp);
+            dev_sync(c.dev);
+            for (int64_t idx = 0; idx < b * kp; ++idx) {
+                double den = (hd[idx] + l1) + l2 * hw[idx];
+                if (den == 0.0) den = NMF_EPS;
+                hw[idx] = hw[idx] * (hz[idx] / den);
+            }
+            dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
+        }
+        if (A) {   // the blocks' contributions are added in block order
+            op_dgemm(c.dev, true, false, kp, dp, b, 1.0, Wb, kp, Xb.f64(), ld, 1.0, A, dp);
+            op_dgemm(c.dev, true, false, kp, kp, b, 1.0, Wb, kp, Wb, kp, 1.0, B, kp);
+        }
+    }
+    dev_sync(c.dev);
+    return false;
+}
+
+// host: HHt = H H^T and the two inner products { <A, H>, <B, HHt> } of the loss
+void nmf_host_gram_dots(const std::vector<double>& a, const std::vector<double>& b, const std::vector<double>& h, int64_t kp, int64_t dp,
+                        std::vector<double>& hht, double dots[2]) {
+    hht.assign(size_t(kp) * kp, 0.0);
+    for (int64_t i = 0; i < kp; ++i)
+        for (int64_t j = 0; j < kp; ++j) {
+            double s = 0;
+            for (int64_t f = 0; f < dp; ++f) s += h[size_t(i) * dp + f] * h[size_t(j) * dp + f];
+            hht[size_t(i) * kp + j] = s;
+        }
+    dots[0] = dots[1] = 0.0;
+    for (size_t idx = 0; idx < a.size(); ++idx) dots[0] += a[idx] * h[idx];
+    for (size_t idx = 0; idx < b.size(); ++idx) dots[1] += b[idx] * hht[idx];
+}
+
+// The H side of an iteration (ops.h, op_nmf_hupdate); dots: DEVICE, two doubles.  Returns "the layer's kernels ran".
+bool nmf_hupdate_into(petal_ctx& c, int64_t kp, int64_t dp, const double* A, const double* B, double* H, double* HHt, double l1, double l2,
+                      double* dots) {
+    if (!c.nmf_fallback && op_nmf_hupdate(c.dev, kp, dp, A, B, H, HHt, l1, l2, dots)) return true;
+    std::vector<double> a(size_t(kp) * dp), b(size_t(kp) * kp), h(size_t(kp) * dp), hn(size_t(kp) * dp), hht;
+    dev_d2h(c.dev, a.data(), A, sizeof(double) * a.size());
+    dev_d2h(c.dev, b.data(), B, sizeof(double) * b.size());
+    dev_d2h(c.dev, h.data(), H, sizeof(double) * h.size());
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < kp; ++i)
+        for (int64_t f = 0; f < dp; ++f) {
+            double e = 0;
+            for (int64_t j = 0; j < kp; ++j) e += b[size_t(i) * kp + j] * h[size_t(j) * dp + f];
+            const double hv = h[size_t(i) * dp + f];
+            double den = (e + l1) + l2 * hv;
+            if (den == 0.0) den = NMF_EPS;
+            hn[size_t(i) * dp + f] = hv * (a[size_t(i) * dp + f] / den);
+        }
+    double hd[2];
+    nmf_host_gram_dots(a, b, hn, kp, dp, hht, hd);
+    dev_h2d(c.dev, H, hn.data(), sizeof(double) * hn.size());
+    dev_h2d(c.dev, HHt, hht.data(), sizeof(double) * hht.size());
+    dev_h2d(c.dev, dots, hd, sizeof(hd));
+    return false;
+}
+
+double nmf_loss(double nx2, const double dots[2]) { return std::sqrt(std::max(0.0, (nx2 - 2.0 * dots[0]) + dots[1])); }
+
+void nmf_check_spec(const NmfSpec& s) {
+    if (s.max_iter < 1) invalid_input("max_iter should be at least 1");
+    if (!(s.tol >= 0) || !(s.l1_w >= 0) || !(s.l2_w >= 0) || !(s.l1_h >= 0) || !(s.l2_h >= 0) || std::isinf(s.tol) || std::isinf(s.l1_w) ||
+        std::isinf(s.l2_w) || std::isinf(s.l1_h) || std::isinf(s.l2_h))
+        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+}
+void nmf_usable(const petal_ctx& c, const petal_nmf& h) {
+    if (h.owner != &c) invalid_input("the Nmf handle belongs to another ctx");
+}
+// W (n x kp fp64) rounded once to dtype into the caller's n x k matrix
+void nmf_emit_w(petal_ctx& c, int dt, const double* W, int64_t n, int64_t k, int64_t kp, const petal_matrix& out) {
+    DBuf wt(c.dev, dtype_size(dt) * size_t(n) * kp);
+    op_cvt_from_f64(c.dev, dt, wt.p, W, n * kp);
+    emit(c, dt, wt.p, n, k, kp, out);
+}
+}  // namespace
+
+void nmf_destroy(petal_nmf* h) {
+    Dev* dv = h->owner->dev;
+    if (h->h) dev_free(dv, h->h);
+    if (h->hht) dev_free(dv, h->hht);
+    delete h;
+}
+
+petal_nmf* nmf_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                   int64_t seed, const petal_matrix* w_out) {
+    const Timer timer = start_fit(c, x);
+    if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
+    const int dt = x.dtype;
+    const int64_t n = x.rows, d = x.cols;
+    if (n == 0 || d == 0) invalid_input("Nmf: the input has no rows or no columns");
+    if (k < 1) invalid_input("Nmf: the number of components should be at least 1");
+    if (std::min(n, d) < k) invalid_input("every dimension should be at least " + std::to_string(k));
+    nmf_check_spec(spec);
+    if ((w0 == nullptr) != (h0 == nullptr)) invalid_input("Nmf: w0 and h0 should both be given or both be null");
+    if (w0) {
+        check_matrix(*w0, "w0");
+        check_matrix(*h0, "h0");
+        if (w0->dtype != dt || h0->dtype != dt) invalid_input("w0 and h0 should have the input's dtype");
+        if (w0->rows != n || w0->cols != k) invalid_input("w0 should be n x k");
+        if (h0->rows != k) invalid_input("h0 should be k x d");
+        if (h0->cols != d) invalid_input("# of columns should be " + std::to_string(d));
+    }
+    if (w_out) check_output(*w_out, dt, n, k);
+    const DevMat X = ingest(c, x);
+    const NmfScan sx = nmf_scan(c, X);
+    nmf_reject(sx);
+    const int64_t dp = X.dp, kp = nmf_padded_k(k);
+    DBuf W(c.dev, sizeof(double) * size_t(n) * kp), H(c.dev, sizeof(double) * size_t(kp) * dp), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
+    DBuf A(c.dev, sizeof(double) * size_t(kp) * dp), B(c.dev, sizeof(double) * size_t(kp) * kp), dots(c.dev, sizeof(double) * 2);
+    if (w0) {
+        const DevMat W0 = ingest(c, *w0), H0 = ingest(c, *h0);
+        nmf_reject(nmf_scan(c, W0));
+        nmf_reject(nmf_scan(c, H0));
+        op_pad_to_f64(c.dev, dt, W.f64(), n, kp, W0.p, n, k, W0.ld);
+        op_pad_to_f64(c.dev, dt, H.f64(), kp, dp, H0.p, k, d, H0.ld);
+        dev_sync(c.dev);   // (W0 / H0 go back to the pool behind the two kernels)
+    } else {
+        // avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first, then H0, both in row-major order
+        const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
+        NmfPcg rng(static_cast<uint64_t>(seed));
+        std::vector<double> hw(size_t(n) * kp, 0.0), hh(size_t(kp) * dp, 0.0);
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t j = 0; j < k; ++j) hw[size_t(i) * kp + j] = std::fabs(avg * rng.standard_normal());
+        for (int64_t i = 0; i < k; ++i)
+            for (int64_t j = 0; j < d; ++j) hh[size_t(i) * dp + j] = std::fabs(avg * rng.standard_normal());
+        dev_h2d(c.dev, W.p, hw.data(), W.bytes);
+        dev_h2d(c.dev, H.p, hh.data(), H.bytes);
+    }
+    op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
+    // the loss at the start: A = W^T X and B = W^T W from a pass that leaves W alone
+    bool kernel = nmf_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 0, A.f64(), B.f64());
+    double hd[2];
+    {
+        std::vector<double> a(size_t(kp) * dp), b(size_t(kp) * kp), h(size_t(kp) * dp), hht;
+        dev_d2h(c.dev, a.data(), A.p, A.bytes);
+        dev_d2h(c.dev, b.data(), B.p, B.bytes);
+        dev_d2h(c.dev, h.data(), H.p, H.bytes);
+        dev_sync(c.dev);
+        nmf_host_gram_dots(a, b, h, kp, dp, hht, hd);
+    }
+    const double err_init = nmf_loss(sx.sumsq, hd);
+    double err_prev = err_init, err = err_init;
+    int64_t n_iter = spec.max_iter;
+    bool read = false;   // `err` is the loss of the iteration just run
+    for (int64_t it = 1; it <= spec.max_iter; ++it) {
+        kernel = nmf_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 1, A.f64(), B.f64()) && kernel;
+        nmf_hupdate_into(c, kp, dp, A.f64(), B.f64(), H.f64(), HHt.f64(), spec.l1_h, spec.l2_h, dots.f64());
+        read = false;
+        if (spec.tol > 0 && it % 10 == 0) {
+            dev_d2h(c.dev, hd, dots.p, sizeof(hd));
+            dev_sync(c.dev);
+            err = nmf_loss(sx.sumsq, hd);
+            read = true;
+            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
+            err_prev = err;
+        }
+    }
+    if (!read) {
+        dev_d2h(c.dev, hd, dots.p, sizeof(hd));
+        dev_sync(c.dev);
+        err = nmf_loss(sx.sumsq, hd);
+    }
+    if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, kp, *w_out);
+    std::unique_ptr<petal_nmf> h(new petal_nmf());
+    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
+    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = kernel ? 1 : 0; h->err = err; h->err_init = err_init;
+    finish_stats(c, timer);
+    h->h = H.f64(); H.p = nullptr;
+    h->hht = HHt.f64(); HHt.p = nullptr;
+    return h.release();
+}
+
+void nmf_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
+    nmf_usable(c, h);
+    const Timer timer = start_fit(c, x);
+    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
+    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    const int64_t m = x.rows;
+    check_output(w_out, h.dtype, m, h.k);
+    if (m == 0) { finish_stats(c, timer); return; }
+    const DevMat X = ingest(c, x);
+    const NmfScan sx = nmf_scan(c, X);
+    nmf_reject(sx);
+    const double w0 = std::sqrt(sx.sum / (double(m) * double(h.d)) / double(h.k));
+    DBuf W(c.dev, sizeof(double) * size_t(m) * h.kp);
+    const bool ran = nmf_pass_into(c, X, h.h, h.hht, h.k, h.kp, W.f64(), true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr);
+    h.last_kernel = ran ? 1 : 0;
+    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, h.kp, w_out);
+    finish_stats(c, timer);
+}
+
+void nmf_inverse_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& w, const petal_matrix& x_out) {
+    nmf_usable(c, h);
+    const Timer timer = start_fit(c, w);
+    if (w.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
+    if (w.cols != h.k) invalid_input("# of columns should be " + std::to_string(h.k));
+    const int64_t m = w.rows, dp = h.dp, kp = h.kp;
+    check_output(x_out, h.dtype, m, h.d);
+    if (m == 0) { finish_stats(c, timer); return; }
+    const DevMat Wm = ingest(c, w);
+    const size_t esz = dtype_size(h.dtype);
+    // W H in row blocks of bounded size: the fp64 product of a block is rounded once into the output's own dtype
+    const int64_t Bk = std::max<int64_t>(1, std::min(m, NMF_FALLBACK_BLOCK / dp));
+    DBuf Wd(c.dev, sizeof(double) * size_t(Bk) * kp), Xd(c.dev, sizeof(double) * size_t(Bk) * dp), Xt(c.dev, esz * size_t(m) * dp);
+    for (int64_t r0 = 0; r0 < m; r0 += Bk) {
+        const int64_t b = std::min(Bk, m - r0);
+        op_pad_to_f64(c.dev, h.dtype, Wd.f64(), b, kp, static_cast<const char*>(Wm.p) + size_t(r0) * Wm.ld * esz, b, h.k, Wm.ld);
+        op_dgemm(c.dev, false, false, b, dp, kp, 1.0, Wd.f64(), kp, h.h, dp, 0.0, Xd.f64(), dp);
+        op_cvt_from_f64(c.dev, h.dtype, static_cast<char*>(Xt.p) + size_t(r0) * dp * esz, Xd.f64(), b * dp);
+    }
+    emit(c, h.dtype, Xt.p, m, h.d, dp, x_out);
+    finish_stats(c, timer);
+}
+
+void nmf_get(const petal_nmf& h, double* components, int64_t* info6, double* err2) {
+    if (components) {
+        Dev* dv = h.owner->dev;
+        dev_copy2d(dv, components, sizeof(double) * h.d, h.h, sizeof(double) * h.dp, sizeof(double) * h.d, size_t(h.k), 1);
+        dev_sync(dv);
+    }
+    if (info6) {
+        const int64_t v[6] = {h.n, h.d, h.k, h.n_iter, h.fit_kernel, h.last_kernel};
+        std::copy(v, v + 6, info6);
+    }
+    if (err2) { err2[0] = h.err; err2[1] = h.err_init; }
+}
+
+void nmf_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* hh, const NmfSpec& spec, int64_t inner,
+              double* w_out, double* a_out, double* b_out, int64_t* info1) {
+    check_matrix(x, "x");
+    if (info1) info1[0] = 0;
+    if (sharded(c)) invalid_input("nmf_pass: a sharded ctx is not supported in this version");
+    const int64_t n = x.rows, d = x.cols;
+    if (n == 0 || d == 0) invalid_input("nmf_pass: the input has no rows or no columns");
+    if (k < 1) invalid_input("nmf_pass: the number of components should be at least 1");
+    if (inner < 0) invalid_input("negative parameter");
+    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0)) invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    if ((a_out == nullptr) != (b_out == nullptr)) invalid_input("a_out and b_out should both be given or both be null");
+    const DevMat X = ingest(c, x);
+    nmf_reject(nmf_scan(c, X));
+    const int64_t dp = X.dp, kp = nmf_padded_k(k);
+    std::vector<double> hw(size_t(n) * kp, 0.0), hp(size_t(kp) * dp, 0.0);
+    for (int64_t i = 0; i < n; ++i) std::copy(w_in + i * k, w_in + (i + 1) * k, hw.begin() + i * kp);
+    for (int64_t i = 0; i < k; ++i) std::copy(hh + i * d, hh + (i + 1) * d, hp.begin() + i * dp);
+    // W is formed inside a guard: a row in front and a row behind, every byte 0xFF beforehand.  The guard rows must come back
+    // untouched and the padding columns of W as zeros.
+    DBuf G(c.dev, sizeof(double) * size_t(n + 2) * kp), H(c.dev, sizeof(double) * hp.size()), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
+    DBuf A, B;
+    if (a_out) {
+        A = DBuf(c.dev, sizeof(double) * size_t(kp) * dp);
+        B = DBuf(c.dev, sizeof(double) * size_t(kp) * kp);
+    }
+    double* W = G.f64() + kp;
+    dev_memset(c.dev, G.p, 0xFF, G.bytes);
+    dev_h2d(c.dev, W, hw.data(), sizeof(double) * hw.size());
+    dev_h2d(c.dev, H.p, hp.data(), H.bytes);
+    op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
+    const bool ran = nmf_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W, false, 0.0, spec.l1_w, spec.l2_w, inner, A.f64(), B.f64());
+    std::vector<double> hg(size_t(n + 2) * kp);
+    dev_d2h(c.dev, hg.data(), G.p, G.bytes);
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < n + 2; ++i)
+        for (int64_t j = 0; j < kp; ++j) {
+            uint64_t bits = 0;
+            std::memcpy(&bits, &hg[size_t(i) * kp + j], 8);
+            const bool guard = i == 0 || i == n + 1;
+            if (guard ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_pass wrote outside the n x k block");
+        }
+    for (int64_t i = 0; i < n; ++i) std::copy(hg.begin() + (i + 1) * kp, hg.begin() + (i + 1) * kp + k, w_out + i * k);
+    if (a_out) {
+        dev_copy2d(c.dev, a_out, sizeof(double) * d, A.p, sizeof(double) * dp, sizeof(double) * d, size_t(k), 1);
+        dev_copy2d(c.dev, b_out, sizeof(double) * k, B.p, sizeof(double) * kp, sizeof(double) * k, size_t(k), 1);
+        dev_sync(c.dev);
+    }
+    if (info1) info1[0] = ran ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Pca::inner_fit (pca.rs:195-231).  The reference asks LAPACK for the full n x n U; only its first
 // min(n,d) columns are ever read (svd_flip zips U columns with V^T rows; transform_with_u takes k),
 // so the thin factorisation is computed: eigen-decomposition of the d x d Gram matrix in fp64.

@@ -11,6 +11,7 @@
 #include "../../include/petal_hip_ipca.h"
 #include "../../include/petal_hip_wide.h"
 #include "../../include/petal_hip_kpca.h"
+#include "../../include/petal_hip_nmf.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -150,6 +151,7 @@ int petal_ctx_set_option(petal_ctx* ctx, int option, double value) {
         }
         if (option == PETAL_OPT_PCA_DUAL_FALLBACK) { ctx->pca_dual_fallback = value != 0; return; }
         if (option == PETAL_OPT_KPCA_FALLBACK) { ctx->kpca_fallback = value != 0; return; }
+        if (option == PETAL_OPT_NMF_FALLBACK) { ctx->nmf_fallback = value != 0; return; }
         if (option < 0 || option >= OPT_COUNT || !(value == value)) invalid_input("unknown ctx option or NaN value");
         dev_set_option(ctx->dev, option, value);
     });
@@ -162,6 +164,7 @@ int petal_ctx_get_option(const petal_ctx* ctx, int option, double* value) {
     if (option == PETAL_OPT_PCA_DUAL) { *value = double(ctx->pca_dual); return PETAL_OK; }
     if (option == PETAL_OPT_PCA_DUAL_FALLBACK) { *value = ctx->pca_dual_fallback ? 1.0 : 0.0; return PETAL_OK; }
     if (option == PETAL_OPT_KPCA_FALLBACK) { *value = ctx->kpca_fallback ? 1.0 : 0.0; return PETAL_OK; }
+    if (option == PETAL_OPT_NMF_FALLBACK) { *value = ctx->nmf_fallback ? 1.0 : 0.0; return PETAL_OK; }
     if (option < 0 || option >= OPT_COUNT) return PETAL_INVALID_INPUT;
     *value = dev_option(ctx->dev, option);
     return PETAL_OK;
@@ -386,6 +389,59 @@ int petal_kernel_apply(petal_ctx* ctx, const petal_matrix* xq, const petal_matri
         need(xt, "xt");
         need(spec, "spec");
         kernel_apply(*ctx, *xq, *xt, KernelSpec{spec->kernel, spec->degree, spec->gamma, spec->coef0}, a, cols, centre, out, info1);
+    });
+}
+
+// ---- include/petal_hip_nmf.h: Nmf ---------------------------------------------------------------------------------------------------
+namespace {
+NmfSpec nmf_spec(const petal_nmf_spec& s) { return NmfSpec{s.max_iter, s.tol, s.l1_w, s.l2_w, s.l1_h, s.l2_h}; }
+}  // namespace
+int petal_nmf_fit(petal_ctx* ctx, const petal_matrix* x, int64_t k, const petal_nmf_spec* spec, const petal_matrix* w0, const petal_matrix* h0,
+                  int64_t seed, petal_nmf** out, const petal_matrix* w_out) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(spec, "spec");
+        need(out, "out");
+        *out = nmf_fit(*ctx, *x, k, nmf_spec(*spec), w0, h0, seed, w_out);
+    });
+}
+void petal_nmf_destroy(petal_nmf* h) {
+    if (!h) return;
+    try {
+        DeviceScope scope(h->owner->dev);
+        nmf_destroy(h);
+    } catch (...) {}
+}
+int petal_nmf_transform(petal_ctx* ctx, petal_nmf* h, const petal_matrix* x, const petal_matrix* w_out) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        need(x, "x");
+        need(w_out, "w_out");
+        nmf_transform(*ctx, *h, *x, *w_out);
+    });
+}
+int petal_nmf_inverse_transform(petal_ctx* ctx, petal_nmf* h, const petal_matrix* w, const petal_matrix* x_out) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        need(w, "w");
+        need(x_out, "x_out");
+        nmf_inverse_transform(*ctx, *h, *w, *x_out);
+    });
+}
+int petal_nmf_get(const petal_nmf* h, double* components, int64_t* info6, double* err2) {
+    if (!h) return PETAL_INVALID_INPUT;
+    return guarded(h->owner, [&] { nmf_get(*h, components, info6, err2); });
+}
+int petal_nmf_pass(petal_ctx* ctx, const petal_matrix* x, int64_t k, const double* w_in, const double* h, const petal_nmf_spec* spec, int64_t inner_iters,
+                   double* w_out, double* a_out, double* b_out, int64_t* info1) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(w_in, "w_in");
+        need(h, "h");
+        need(spec, "spec");
+        need(w_out, "w_out");
+        nmf_pass(*ctx, *x, k, w_in, h, nmf_spec(*spec), inner_iters, w_out, a_out, b_out, info1);
     });
 }
 

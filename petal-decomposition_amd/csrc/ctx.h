@@ -23,6 +23,7 @@ struct petal_ctx {
     bool pca_dual_fallback = false;  // PETAL_OPT_PCA_DUAL_FALLBACK: a test aid
     int64_t pca_route[4] = {0, 0, 0, 0};   // petal_pca_last_route: route, kernel, order of the eigenproblem, feature chunks
     bool kpca_fallback = false;      // PETAL_OPT_KPCA_FALLBACK (include/petal_hip_kpca.h): a test aid
+    bool nmf_fallback = false;       // PETAL_OPT_NMF_FALLBACK (include/petal_hip_nmf.h): a test aid
     bool force_collective = false;   // PETAL_OPT_FORCE_COLLECTIVE (default: env PETAL_FORCE_COLLECTIVE at petal_ctx_create)
     petal_stats stats{};
     void* rccl = nullptr;  // the built-in RCCL communicator (rccl.cpp), when petal_ctx_init_rccl installed it
@@ -77,6 +78,18 @@ struct petal_kpca {
     double* epi = nullptr;               // device fp64, n + 1 + 2 lda: [rbar | tbar | rbar^T A' | 1^T A']
     double tbar = 0;
     std::vector<double> lam;             // k eigenvalues, as computed
+};
+
+// include/petal_hip_nmf.h: a fitted Nmf, resident with its ctx
+struct petal_nmf {
+    petal_ctx* owner = nullptr;
+    int64_t n = 0, d = 0, dp = 0, k = 0, kp = 0, max_iter = 0, n_iter = 0;
+    int dtype = 0;
+    double l1_w = 0, l2_w = 0;
+    int64_t fit_kernel = 0, last_kernel = -1;
+    double err = 0, err_init = 0;
+    double* h = nullptr;                 // device fp64, kp x dp (ld dp): H, zero in the padding
+    double* hht = nullptr;               // device fp64, kp x kp: H H^T
 };
 
 namespace petal {
@@ -176,6 +189,16 @@ void kpca_transform(petal_ctx& c, petal_kpca& h, const petal_matrix& x, const pe
 void kpca_get(const petal_kpca& h, double* eigenvalues, double* scaled_vectors, int64_t* info8);
 void kernel_apply(petal_ctx& c, const petal_matrix& xq, const petal_matrix& xt, const KernelSpec& spec, const double* a, int64_t cols,
                   const double* centre, double* out, int64_t* info1);
+// include/petal_hip_nmf.h: Nmf
+struct NmfSpec { int64_t max_iter; double tol, l1_w, l2_w, l1_h, l2_h; };
+petal_nmf* nmf_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                   int64_t seed, const petal_matrix* w_out);
+void nmf_destroy(petal_nmf* h);
+void nmf_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out);
+void nmf_inverse_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& w, const petal_matrix& x_out);
+void nmf_get(const petal_nmf& h, double* components, int64_t* info6, double* err2);
+void nmf_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* h, const NmfSpec& spec, int64_t inner, double* w_out,
+              double* a_out, double* b_out, int64_t* info1);
 // include/petal_hip_ipca.h: IncrementalPca
 petal_ipca* ipca_create(petal_ctx& c, int64_t d, int32_t dtype, bool centering);
 void ipca_destroy(petal_ipca* h);

@@ -235,6 +235,23 @@ bool op_kernel_apply(Dev*, int dtype, const void* Xt, int64_t n, int64_t ldt, co
 // fp64, ldo; column k = the row sums of Kq); ra, oa, tbar: DEVICE fp64.  Rounded once to dtype.
 bool op_kpca_finish(Dev*, int dtype, const double* O, int64_t ldo, int64_t m, int64_t k, const double* ra, const double* oa, double n,
                     const double* tbar, void* Y, int64_t ldy);
+// Nmf (include/petal_hip_nmf.h; an extension beyond the crate): multiplicative updates for the Frobenius loss.  Device layouts, all
+// fp64: W n x kp, H and A kp x dp (leading dimension dp), H H^T and B kp x kp, kp = nmf_padded_k(k), ZERO in every padding row and
+// column.  Each returns "this layer did the work": false, NOTHING done, where the shape is outside the kernel's envelope (k > 64,
+// dp > 512), X does not allow 16-byte loads along its rows or the layer lacks the op -- algo.cpp's weak defaults return false and the
+// caller builds the same statement from op_cvt_to_f64, op_dgemm and an element-wise step on the host.
+inline int64_t nmf_padded_k(int64_t k) { return k <= 16 ? 16 : (k <= 32 ? 32 : (k + 15) / 16 * 16); }
+// out4 (DEVICE) = { sum x, sum x^2, min(x, 0), 1 if a NaN or an infinity was seen else 0 } over X (n x dp in dtype, ldx), fp64, a fixed order.
+bool op_nmf_scan(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64_t ldx, double* out4);
+// The fused pass: Z = X H^T once, then `inner` times  D = W HHt + l1 + l2 W, D[D == 0] = 2^-23, W <- W o Z / D  (W in place;
+// from_const: W starts as wconst in its k leading columns instead of its contents), then, where A and B are given (both or neither),
+// A = W^T X and B = W^T W with the W just written.  inner == 0: W is left alone.  X is read once from memory; no n x kp or n x dp
+// intermediate but W; every product and sum fp64 in an order the shape alone fixes; no atomics.
+bool op_nmf_pass(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64_t ldx, const double* H, const double* HHt, int64_t k, int64_t kp,
+                 double* W, bool from_const, double wconst, double l1, double l2, int64_t inner, double* A, double* B);
+// The H side of an iteration: E = B H + l1 + l2 H, E[E == 0] = 2^-23, H <- H o A / E, HHt = H H^T, dots2 (DEVICE) = { <A, H>, <B, HHt> }
+// with the new H (the two inner products of the loss).
+bool op_nmf_hupdate(Dev*, int64_t kp, int64_t dp, const double* A, const double* B, double* H, double* HHt, double l1, double l2, double* dots2);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.

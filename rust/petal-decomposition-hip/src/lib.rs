@@ -5,18 +5,22 @@
 mod ffi;
 mod ffi_ipca;
 mod ffi_kpca;
+mod ffi_nmf;
 mod ffi_score;
 mod ffi_segments;
 mod ffi_sparse;
 mod ffi_wide;
 mod ica;
 mod kpca;
+mod nmf;
 mod pca;
 
 pub use ica::{Contrast, FastIca, FastIcaBuilder};
 pub use ffi_kpca::PETAL_OPT_KPCA_FALLBACK;
+pub use ffi_nmf::PETAL_OPT_NMF_FALLBACK;
 pub use ffi_wide::{PETAL_OPT_PCA_DUAL, PETAL_OPT_PCA_DUAL_FALLBACK};
 pub use kpca::{Kernel, KernelPca, KernelPcaInfo};
+pub use nmf::{Nmf, NmfInfo, NmfParams};
 pub use pca::{CsrMatrix, IncrementalPca, Pca, PcaBuilder, PcaRoute, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
 
 use ndarray::{ArrayBase, Data, Ix2};

@@ -1,0 +1,133 @@
+//! `Nmf` over the C ABI (include/petal_hip_nmf.h; an extension beyond the crate): scikit-learn's `NMF(solver="mu",
+//! beta_loss="frobenius")`.  An iteration is one fused pass over the data; `transform` is one pass whatever `max_iter` is.  Everything
+//! is float64 inside; outputs are rounded once to `A`.
+use crate::ffi_nmf::{self, PetalNmf, PetalNmfSpec};
+use crate::{view, with_ctx, DecompositionError, HipScalar};
+use ndarray::{Array2, ArrayBase, Data, Ix2};
+use std::marker::PhantomData;
+
+/// The parameters of a fit; `alpha_h: None` means the same as `alpha_w` (scikit-learn's "same").
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub struct NmfParams {
+    pub max_iter: usize,
+    pub tol: f64,
+    pub seed: u64,
+    pub alpha_w: f64,
+    pub alpha_h: Option<f64>,
+    pub l1_ratio: f64,
+}
+
+impl Default for NmfParams {
+    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0 } }
+}
+
+/// { n, d, k, iterations run, k_nmf_pass ran in the fit, k_nmf_pass ran in the last transform (-1 before the first) }
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct NmfInfo {
+    pub n: i64,
+    pub d: i64,
+    pub k: i64,
+    pub n_iter: i64,
+    pub fit_kernel: bool,
+    pub transform_kernel: i64,
+}
+
+/// The fitted model lives on the device with the process's ctx.
+pub struct Nmf<A: HipScalar> {
+    raw: *mut PetalNmf,
+    k: usize,
+    params: NmfParams,
+    _a: PhantomData<A>,
+}
+unsafe impl<A: HipScalar> Send for Nmf<A> {}
+
+impl<A: HipScalar> Nmf<A> {
+    pub fn new(n_components: usize, params: NmfParams) -> Self { Self { raw: std::ptr::null_mut(), k: n_components, params, _a: PhantomData } }
+    pub fn n_components(&self) -> usize { self.k }
+
+    /// Random initialisation from `Pcg(seed)`.
+    pub fn fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>) -> Result<(), DecompositionError> { self.inner_fit(input, None, None) }
+    pub fn fit_transform<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>) -> Result<Array2<A>, DecompositionError> {
+        let mut w = Array2::<A>::default((input.nrows(), self.k));
+        self.inner_fit(input, None, Some(&mut w))?;
+        Ok(w)
+    }
+    /// Custom initialisation: `w0` (n x k) and `h0` (k x d).
+    pub fn fit_transform_from<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, w0: &Array2<A>, h0: &Array2<A>) -> Result<Array2<A>, DecompositionError> {
+        let mut w = Array2::<A>::default((input.nrows(), self.k));
+        self.inner_fit(input, Some((w0, h0)), Some(&mut w))?;
+        Ok(w)
+    }
+    pub fn transform<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>) -> Result<Array2<A>, DecompositionError> {
+        let raw = self.handle()?;
+        let mut w = Array2::<A>::default((input.nrows(), self.k));
+        let (x, wv) = (view(input), view(&w.view_mut()));
+        with_ctx(|ctx| unsafe { ffi_nmf::petal_nmf_transform(ctx, raw, &x, &wv) }, || ())?;
+        Ok(w)
+    }
+    pub fn inverse_transform<S: Data<Elem = A>>(&mut self, w: &ArrayBase<S, Ix2>) -> Result<Array2<A>, DecompositionError> {
+        let raw = self.handle()?;
+        let d = self.info()?.d as usize;
+        let mut x = Array2::<A>::default((w.nrows(), d));
+        let (wv, xv) = (view(w), view(&x.view_mut()));
+        with_ctx(|ctx| unsafe { ffi_nmf::petal_nmf_inverse_transform(ctx, raw, &wv, &xv) }, || ())?;
+        Ok(x)
+    }
+    /// H, k x d, float64.
+    pub fn components(&self) -> Result<Array2<f64>, DecompositionError> {
+        let raw = self.handle()?;
+        let d = self.info()?.d as usize;
+        let mut h = Array2::<f64>::zeros((self.k, d));
+        with_ctx(|_| unsafe { ffi_nmf::petal_nmf_get(raw, h.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut()) }, || ())?;
+        Ok(h)
+    }
+    pub fn reconstruction_err(&self) -> Result<f64, DecompositionError> {
+        let raw = self.handle()?;
+        let mut e = [0f64; 2];
+        with_ctx(|_| unsafe { ffi_nmf::petal_nmf_get(raw, std::ptr::null_mut(), std::ptr::null_mut(), e.as_mut_ptr()) }, || ())?;
+        Ok(e[0])
+    }
+    pub fn info(&self) -> Result<NmfInfo, DecompositionError> {
+        let raw = self.handle()?;
+        let mut v = [0i64; 6];
+        with_ctx(|_| unsafe { ffi_nmf::petal_nmf_get(raw, std::ptr::null_mut(), v.as_mut_ptr(), std::ptr::null_mut()) }, || ())?;
+        Ok(NmfInfo { n: v[0], d: v[1], k: v[2], n_iter: v[3], fit_kernel: v[4] != 0, transform_kernel: v[5] })
+    }
+
+    fn handle(&self) -> Result<*mut PetalNmf, DecompositionError> {
+        if self.raw.is_null() {
+            return Err(DecompositionError::InvalidInput("the model has not been fitted".into()));
+        }
+        Ok(self.raw)
+    }
+    fn inner_fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, init: Option<(&Array2<A>, &Array2<A>)>, w: Option<&mut Array2<A>>)
+        -> Result<(), DecompositionError> {
+        let x = view(input);
+        let wv = w.map(|w| view(&w.view_mut()));
+        let iv = init.map(|(w0, h0)| (view(w0), view(h0)));
+        let (n, d) = (input.nrows() as f64, input.ncols() as f64);
+        let p = self.params;
+        let (aw, ah, rho) = (p.alpha_w, p.alpha_h.unwrap_or(p.alpha_w), p.l1_ratio);
+        let spec = PetalNmfSpec {
+            max_iter: p.max_iter as i64, tol: p.tol,
+            l1_w: d * aw * rho, l2_w: d * aw * (1.0 - rho), l1_h: n * ah * rho, l2_h: n * ah * (1.0 - rho),
+        };
+        let mut raw = std::ptr::null_mut();
+        let (k, seed) = (self.k as i64, p.seed as i64);
+        with_ctx(
+            |ctx| unsafe {
+                ffi_nmf::petal_nmf_fit(ctx, &x, k, &spec, iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _),
+                                       iv.as_ref().map_or(std::ptr::null(), |m| &m.1 as *const _), seed, &mut raw,
+                                       wv.as_ref().map_or(std::ptr::null(), |m| m as *const _))
+            },
+            || (),
+        )?;
+        unsafe { ffi_nmf::petal_nmf_destroy(self.raw) };
+        self.raw = raw;
+        Ok(())
+    }
+}
+
+impl<A: HipScalar> Drop for Nmf<A> {
+    fn drop(&mut self) { unsafe { ffi_nmf::petal_nmf_destroy(self.raw) } }
+}
