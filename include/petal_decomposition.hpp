@@ -28,6 +28,7 @@
 #include "petal_hip_wide.h"
 #include "petal_hip_kpca.h"
 #include "petal_hip_nmf.h"
+#include "petal_hip_nmf_sparse.h"
 
 namespace petal_decomposition {
 
@@ -565,6 +566,9 @@ struct NmfInfo {
 };
 
 template <class A>
+class CsrMatrix;   // (declared below: Nmf takes it in place of an Array2, petal_hip_nmf_sparse.h)
+
+template <class A>
 class Nmf {
   public:
     explicit Nmf(int64_t n_components, int64_t max_iter = 200, double tol = 1e-4, uint64_t seed = 0, double alpha_w = 0.0,
@@ -601,6 +605,27 @@ class Nmf {
         context().check(petal_nmf_inverse_transform(context().get(), handle(), &mw, &mx));
         return x;
     }
+    // extension beyond the crate (petal_hip_nmf_sparse.h): sparse CSR input, never densified where the sweep kernel runs (at most 64
+    // components, a resident handle); otherwise the library densifies and runs the dense fit, bit for bit its result
+    Nmf& fit(const CsrMatrix<A>& input) { inner_fit_sparse(input, nullptr, nullptr, nullptr); return *this; }
+    Nmf& fit(const CsrMatrix<A>& input, const Array2<A>& w0, const Array2<A>& h0) { inner_fit_sparse(input, &w0, &h0, nullptr); return *this; }
+    Array2<A> fit_transform(const CsrMatrix<A>& input) {
+        Array2<A> w(input.nrows(), k_);
+        inner_fit_sparse(input, nullptr, nullptr, &w);
+        return w;
+    }
+    Array2<A> fit_transform(const CsrMatrix<A>& input, const Array2<A>& w0, const Array2<A>& h0) {
+        Array2<A> w(input.nrows(), k_);
+        inner_fit_sparse(input, &w0, &h0, &w);
+        return w;
+    }
+    Array2<A> transform(const CsrMatrix<A>& input) {
+        Array2<A> w(input.nrows(), k_);
+        petal_matrix mw = w.view();
+        context().check(petal_nmf_transform_csr(context().get(), handle(), input.get(), &mw, &kernel_path_));
+        return w;
+    }
+    int64_t kernel_path() const { return kernel_path_; }   // the last sparse call: 1 the sweep kernel, 0 the densifying fall-back
     int64_t n_components() const { return k_; }
     // H, k x d, float64
     Array2<double> components() const {
@@ -647,12 +672,28 @@ class Nmf {
         petal_nmf_destroy(h_);
         h_ = h;
     }
+    void inner_fit_sparse(const CsrMatrix<A>& input, const Array2<A>* w0, const Array2<A>* h0, Array2<A>* w) {
+        petal_matrix m0{}, m1{}, mw{};
+        if (w0) { m0 = w0->view(); m1 = h0->view(); }
+        if (w) mw = w->view();
+        const double n = double(input.nrows()), d = double(input.ncols());
+        petal_nmf_spec spec{};
+        spec.max_iter = max_iter_; spec.tol = tol_;
+        spec.l1_w = d * alpha_w_ * l1_ratio_; spec.l2_w = d * alpha_w_ * (1.0 - l1_ratio_);
+        spec.l1_h = n * alpha_h_ * l1_ratio_; spec.l2_h = n * alpha_h_ * (1.0 - l1_ratio_);
+        petal_nmf* h = nullptr;
+        context().check(petal_nmf_fit_csr(context().get(), input.get(), k_, &spec, w0 ? &m0 : nullptr, w0 ? &m1 : nullptr, int64_t(seed_), &h,
+                                          w ? &mw : nullptr, &kernel_path_));
+        petal_nmf_destroy(h_);
+        h_ = h;
+    }
     int64_t k_, max_iter_;
     double tol_;
     uint64_t seed_;
     double alpha_w_, alpha_h_, l1_ratio_;
     Context* ctx_;
     petal_nmf* h_ = nullptr;
+    int64_t kernel_path_ = 0;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

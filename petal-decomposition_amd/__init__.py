@@ -227,6 +227,13 @@ ABI_NMF = [
     ("petal_nmf_pass", C.c_int, [_P, _M, C.c_int64, _D, _D, _NS, C.c_int64, _D, _D, _D, _L]),
 ]
 
+# every symbol include/petal_hip_nmf_sparse.h declares (Nmf on sparse CSR data and its sweep by itself)
+ABI_NMF_SPARSE = [
+    ("petal_nmf_fit_csr", C.c_int, [_P, _P, C.c_int64, _NS, _M, _M, C.c_int64, C.POINTER(C.c_void_p), _M, _L]),
+    ("petal_nmf_transform_csr", C.c_int, [_P, _P, _P, _M, _L]),
+    ("petal_nmf_sweep_csr", C.c_int, [_P, _P, C.c_int, C.c_int64, _D, _D, _NS, C.c_int64, _D, _D, _D, _L]),
+]
+
 
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
@@ -244,7 +251,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h, petal_hip_nmf_sparse.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -253,7 +260,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF + ABI_NMF_SPARSE:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -806,9 +813,35 @@ def nmf_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, want_ab=True, ctx: Opti
     return (out, {"kernel": int(info[0])}) if want_info else out
 
 
+def nmf_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0, inner_iters=1, want_gram=True, want_info: bool = False):
+    """Test aid (``petal_nmf_sweep_csr``, include/petal_hip_nmf_sparse.h): one sweep of sparse ``Nmf`` by itself, in float64, over the
+    matrix (``transposed=False``: R x C = ``sx.shape``) or its transposed image.  ``g`` (R x k) is updated, ``f`` (C x k) gathered:
+    z_r = sum over the stored entries of row r of val f[idx], then ``inner_iters`` times D = g_r (f^T f) + l1 + l2 g_r,
+    D[D == 0] = 2^-23, g_r <- g_r o z_r / D.  Returns ``(g_new, gram, dot)`` with gram = g_new^T g_new and dot = sum_r <z_r, g_new_r>
+    (``want_gram=False``: ``g_new`` alone).  ``want_info``: also ``{"kernel": k_nmf_sweep ran}``."""
+    rows, inner = (sx.shape[1], sx.shape[0]) if transposed else sx.shape
+    g = np.ascontiguousarray(np.asarray(g, dtype=np.float64))
+    f = np.ascontiguousarray(np.asarray(f, dtype=np.float64))
+    if g.ndim != 2 or f.ndim != 2 or g.shape[0] != rows or f.shape != (inner, g.shape[1]):
+        raise InvalidInput(f"g should be {rows} x k and f {inner} x k")
+    k = g.shape[1]
+    spec = _nmf_spec(1, 0.0, l1, l2)
+    go = np.zeros((rows, k))
+    gram = np.zeros((k, k)) if want_gram else None
+    dot = np.zeros(1) if want_gram else None
+    info = (C.c_int64 * 1)()
+    ctx = sx.ctx
+    ctx.check(ctx.lib.petal_nmf_sweep_csr(ctx._h, sx._handle(), int(bool(transposed)), k, g.ctypes.data_as(_D), f.ctypes.data_as(_D),
+                                          C.byref(spec), int(inner_iters), go.ctypes.data_as(_D),
+                                          gram.ctypes.data_as(_D) if want_gram else None, dot.ctypes.data_as(_D) if want_gram else None, info))
+    out = (go, gram, float(dot[0])) if want_gram else go
+    return (out, {"kernel": int(info[0])}) if want_info else out
+
+
 class Nmf:
     """Non-negative matrix factorisation X ~ W H (``petal_nmf``, include/petal_hip_nmf.h; an extension beyond the crate, DESIGN.md
-    sections 4 and 7) -- scikit-learn's ``NMF(solver="mu", beta_loss="frobenius")``.  ``init="random"`` draws W0 and H0 from
+    sections 4 and 7) -- scikit-learn's ``NMF(solver="mu", beta_loss="frobenius")``.  ``fit``, ``fit_transform`` and ``transform``
+    also take a ``CsrMatrix`` or any object with ``.data / .indices / .indptr / .shape`` (include/petal_hip_nmf_sparse.h).  ``init="random"`` draws W0 and H0 from
     ``Pcg(seed)``; ``init="custom"`` takes them from ``fit_transform(x, W=..., H=...)``.  ``alpha_W``, ``alpha_H`` ("same": alpha_W)
     and ``l1_ratio`` are scikit-learn's penalties.  ``tol > 0`` stops at a check every 10th iteration; ``transform`` runs exactly
     ``max_iter`` W-updates in one pass over its input.  Everything is float64 inside; outputs are rounded once to the data's type.
@@ -823,6 +856,7 @@ class Nmf:
         self.alpha_W, self.alpha_H, self.l1_ratio = float(alpha_W), alpha_H, float(l1_ratio)
         self.ctx = ctx
         self._h = None
+        self.kernel_path = None   # the last fit / transform on sparse input: 1 the sweep kernel ran, 0 the call densified
 
     def _ctx(self) -> Context:
         if self.ctx is None:
@@ -856,20 +890,61 @@ class Nmf:
         rho = self.l1_ratio
         return _nmf_spec(self.max_iter, self.tol, d * a_w * rho, d * a_w * (1.0 - rho), n * a_h * rho, n * a_h * (1.0 - rho))
 
+    def _sparse(self, x):
+        """x as a CsrMatrix on this model's ctx, and whether it was made here (and is released when the call is over)."""
+        if isinstance(x, CsrMatrix):
+            if self.ctx is None:
+                self.ctx = x.ctx
+            return x, False
+        return CsrMatrix.from_scipy_like(x, ctx=self._ctx()), True
+
+    def _start(self, dtype_code, W, H, keep):
+        """(w0, h0) as petal_matrix descriptions (init="custom") or (None, None)"""
+        if self.init == "custom":
+            if W is None or H is None:
+                raise InvalidInput("init='custom' needs W and H")
+            dt = _np_dtype(dtype_code)
+            return (describe(W if _is_torch(W) else np.asarray(W, dtype=dt), keep),
+                    describe(H if _is_torch(H) else np.asarray(H, dtype=dt), keep))
+        if W is not None or H is not None:
+            raise InvalidInput("W and H are read with init='custom' only")
+        return None, None
+
+    def _inner_fit_sparse(self, x, W, H, want_w: bool):
+        """fit / fit_transform on sparse input (include/petal_hip_nmf_sparse.h): X is never densified where the sweep kernel runs;
+        ``kernel_path`` says whether it did (1) or the library densified and ran the dense fit (0)."""
+        sx, mine = self._sparse(x)
+        try:
+            ctx = self._ctx()
+            rows, cols = sx.shape
+            spec = self._spec(rows, cols)
+            keep = []
+            mw, mh = self._start(sx._dt, W, H, keep)
+            w, mo = None, None
+            if want_w:
+                w = np.empty((rows, self._k), dtype=_np_dtype(sx._dt))
+                mo = describe(w, keep)
+            h, path = C.c_void_p(), C.c_int64(0)
+            ctx.check(ctx.lib.petal_nmf_fit_csr(ctx._h, sx._handle(), self._k, C.byref(spec), C.byref(mw) if mw is not None else None,
+                                                C.byref(mh) if mh is not None else None, C.c_int64(self.seed & ((1 << 64) - 1)),
+                                                C.byref(h), C.byref(mo) if mo is not None else None, C.byref(path)))
+            self.close()
+            self._h = h
+            ctx._nmf.add(self)
+            self.kernel_path = int(path.value)
+            return w
+        finally:
+            if mine:
+                sx.close()
+
     def _inner_fit(self, x, W, H, want_w: bool):
+        if _is_sparse(x):
+            return self._inner_fit_sparse(x, W, H, want_w)
         keep = []
         mx = describe(x, keep)
         ctx = self._ctx()
         spec = self._spec(mx.rows, mx.cols)
-        mw = mh = None
-        if self.init == "custom":
-            if W is None or H is None:
-                raise InvalidInput("init='custom' needs W and H")
-            dt = _np_dtype(mx.dtype)
-            mw = describe(W if _is_torch(W) else np.asarray(W, dtype=dt), keep)
-            mh = describe(H if _is_torch(H) else np.asarray(H, dtype=dt), keep)
-        elif W is not None or H is not None:
-            raise InvalidInput("W and H are read with init='custom' only")
+        mw, mh = self._start(mx.dtype, W, H, keep)
         w, mo = None, None
         if want_w:
             w = _alloc_like(x, mx.rows, self._k, mx.dtype)
@@ -891,6 +966,23 @@ class Nmf:
         return self._inner_fit(x, W, H, True)
 
     def transform(self, x):
+        """``max_iter`` W-updates with H fixed; sparse input (a CsrMatrix or an object with .data / .indices / .indptr / .shape) goes
+        through the sparse sweep and sets ``kernel_path``."""
+        if _is_sparse(x):
+            self._handle()
+            sx, mine = self._sparse(x)
+            try:
+                ctx = self._ctx()
+                keep = []
+                w = np.empty((sx.shape[0], self._k), dtype=_np_dtype(sx._dt))
+                mo = describe(w, keep)
+                path = C.c_int64(0)
+                ctx.check(ctx.lib.petal_nmf_transform_csr(ctx._h, self._handle(), sx._handle(), C.byref(mo), C.byref(path)))
+                self.kernel_path = int(path.value)
+                return w
+            finally:
+                if mine:
+                    sx.close()
         keep = []
         mx = describe(x, keep)
         ctx = self._ctx()

@@ -1747,6 +1747,24 @@ void nmf_check_spec(const NmfSpec& s) {
         std::isinf(s.l2_w) || std::isinf(s.l1_h) || std::isinf(s.l2_h))
         invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
 }
+// the argument checks of a fit on an n x d input of type dt, dense or sparse
+void nmf_check_fit(int64_t n, int64_t d, int dt, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                   const petal_matrix* w_out) {
+    if (n == 0 || d == 0) invalid_input("Nmf: the input has no rows or no columns");
+    if (k < 1) invalid_input("Nmf: the number of components should be at least 1");
+    if (std::min(n, d) < k) invalid_input("every dimension should be at least " + std::to_string(k));
+    nmf_check_spec(spec);
+    if ((w0 == nullptr) != (h0 == nullptr)) invalid_input("Nmf: w0 and h0 should both be given or both be null");
+    if (w0) {
+        check_matrix(*w0, "w0");
+        check_matrix(*h0, "h0");
+        if (w0->dtype != dt || h0->dtype != dt) invalid_input("w0 and h0 should have the input's dtype");
+        if (w0->rows != n || w0->cols != k) invalid_input("w0 should be n x k");
+        if (h0->rows != k) invalid_input("h0 should be k x d");
+        if (h0->cols != d) invalid_input("# of columns should be " + std::to_string(d));
+    }
+    if (w_out) check_output(*w_out, dt, n, k);
+}
 void nmf_usable(const petal_ctx& c, const petal_nmf& h) {
     if (h.owner != &c) invalid_input("the Nmf handle belongs to another ctx");
 }
@@ -1771,20 +1789,7 @@ petal_nmf* nmf_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec
     if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
     const int dt = x.dtype;
     const int64_t n = x.rows, d = x.cols;
-    if (n == 0 || d == 0) invalid_input("Nmf: the input has no rows or no columns");
-    if (k < 1) invalid_input("Nmf: the number of components should be at least 1");
-    if (std::min(n, d) < k) invalid_input("every dimension should be at least " + std::to_string(k));
-    nmf_check_spec(spec);
-    if ((w0 == nullptr) != (h0 == nullptr)) invalid_input("Nmf: w0 and h0 should both be given or both be null");
-    if (w0) {
-        check_matrix(*w0, "w0");
-        check_matrix(*h0, "h0");
-        if (w0->dtype != dt || h0->dtype != dt) invalid_input("w0 and h0 should have the input's dtype");
-        if (w0->rows != n || w0->cols != k) invalid_input("w0 should be n x k");
-        if (h0->rows != k) invalid_input("h0 should be k x d");
-        if (h0->cols != d) invalid_input("# of columns should be " + std::to_string(d));
-    }
-    if (w_out) check_output(*w_out, dt, n, k);
+    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
     const DevMat X = ingest(c, x);
     const NmfScan sx = nmf_scan(c, X);
     nmf_reject(sx);
@@ -3557,6 +3562,306 @@ void csr_gemm(petal_ctx& c, const petal_csr& x, bool transposed, const double* P
     dev_sync(c.dev);
     for (int64_t r = 0; r < rows; ++r)
         for (int64_t j = 0; j < N; ++j) out[r * N + j] = get_elem(hO.data(), dt, r * NP + j);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Nmf on sparse CSR data (include/petal_hip_nmf_sparse.h; DESIGN.md sections 4 and 7).  An iteration is two sweeps of the same kernel
+// (op_nmf_sweep_csr): over the rows of X with G = W, F = H^T, S = H H^T, and over the rows of the transposed image with G = H^T, F = W,
+// S = W^T W; each leaves its G, G^T G and sum_r <z_r, g_r> on the device, so W^T X is never formed and the loss is read only at a check.
+// W (n x ks) and H^T (d x ks) live in fp64 in the sweep's own padding ks = 16, 32 or 64.  A handle that is not resident (a device-op
+// layer without the kernels), PETAL_OPT_NMF_FALLBACK and k > 64 densify and run the dense entries: bit for bit their results.
+__attribute__((weak)) bool op_nmf_sweep_csr(Dev*, int, const CsrImage&, int64_t, int64_t, const double*, double*, const double*, bool, double, double,
+                                            double, int64_t, double*) {
+    return false;
+}
+__attribute__((weak)) bool op_nmf_gram(Dev*, const double*, int64_t, int64_t, const double*, double*) { return false; }
+__attribute__((weak)) bool op_nmf_valscan(Dev*, int, const void*, int64_t, double*) { return false; }
+__attribute__((weak)) bool op_csr_densify(Dev*, int, const CsrImage&, void*, int64_t, int64_t) { return false; }
+
+namespace {
+constexpr double NMF_CSR_DENSIFY_LIMIT = 4294967296.0;   // bytes of the dense image the fall-back may form (2^32)
+
+bool nmf_csr_sweeps(const petal_ctx& c, const petal_csr& x, int64_t k) { return x.resident && !c.nmf_fallback && k <= 64; }
+
+// the one look at the stored values in front of a fit or a transform: they are checked one by one (a duplicate pair is not summed first)
+NmfScan nmf_csr_scan(petal_ctx& c, const petal_csr& x) {
+    NmfScan r;
+    if (x.nnz == 0) return r;
+    if (x.resident) {
+        DBuf o(c.dev, sizeof(double) * 4);
+        if (!op_nmf_valscan(c.dev, x.dtype, x.dev[0].val, x.nnz, o.f64())) device_error("Nmf: the device-op layer has no scan of the stored values");
+        double h[4];
+        dev_d2h(c.dev, h, o.p, sizeof(h));
+        dev_sync(c.dev);
+        r.sum = h[0]; r.sumsq = h[1]; r.negative = h[2] < 0.0; r.bad = h[3] != 0.0;
+        return r;
+    }
+    for (int64_t t = 0; t < x.nnz; ++t) {
+        const double v = get_elem(x.host[0].val.data(), x.dtype, t);
+        r.sum += v;
+        r.sumsq += v * v;
+        if (v < 0.0) r.negative = true;
+        if (!(v - v == 0.0)) r.bad = true;
+    }
+    return r;
+}
+
+// The dense image of a handle for the fall-back: a host array where the handle is not resident, else a device block filled by
+// op_csr_densify; `m` views it.
+struct NmfCsrDense {
+    std::vector<char> host;
+    DBuf dev;
+    petal_matrix m{};
+};
+void nmf_csr_densify(petal_ctx& c, const petal_csr& x, NmfCsrDense& out) {
+    const size_t esz = dtype_size(x.dtype);
+    if (double(x.rows) * double(x.cols) * double(esz) > NMF_CSR_DENSIFY_LIMIT)
+        invalid_input("Nmf: the sparse matrix is too large to densify (" + std::to_string(x.rows) + " x " + std::to_string(x.cols) +
+                      "); the sparse kernel takes at most 64 components and PETAL_OPT_NMF_FALLBACK must be off");
+    if (!x.resident) {
+        out.host = csr_densify(x);
+        out.m = csr_dense_view(x, out.host);
+        return;
+    }
+    out.dev = DBuf(c.dev, std::max<size_t>(16, esz * size_t(x.rows) * size_t(x.cols)));
+    if (x.rows > 0 && x.cols > 0 && !op_csr_densify(c.dev, x.dtype, x.dev[0], out.dev.p, x.cols, x.cols))
+        device_error("Nmf: the device-op layer cannot densify a resident sparse matrix");
+    out.m.data = out.dev.p; out.m.rows = x.rows; out.m.cols = x.cols; out.m.row_stride = x.cols; out.m.col_stride = 1;
+    out.m.dtype = x.dtype; out.m.space = PETAL_DEVICE;
+}
+
+// dst (cols x ks, row-major, zero padded) = the transpose of the k leading rows of src (ld lds)
+void nmf_transpose_in(const double* src, int64_t lds, int64_t k, int64_t cols, int64_t ks, std::vector<double>& dst) {
+    dst.assign(size_t(std::max<int64_t>(cols, 1)) * ks, 0.0);
+    for (int64_t i = 0; i < k; ++i)
+        for (int64_t j = 0; j < cols; ++j) dst[size_t(j) * ks + i] = src[size_t(i) * lds + j];
+}
+
+// one sweep under the hot-kernel tag; a layer that refuses here has refused nothing else
+void nmf_sweep_into(petal_ctx& c, const petal_csr& x, int t, int64_t k, int64_t ks, const double* F, double* G, const double* S, bool from_const,
+                    double gconst, double l1, double l2, int64_t inner, double* gram_dot) {
+    dev_set_tag(c.dev, TAG_POW);
+    const bool ran = op_nmf_sweep_csr(c.dev, x.dtype, x.dev[t], k, ks, F, G, S, from_const, gconst, l1, l2, inner, gram_dot);
+    dev_set_tag(c.dev, TAG_NONE);
+    if (!ran) device_error("Nmf: the device-op layer refused the sparse sweep");
+}
+}  // namespace
+
+petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                       int64_t seed, const petal_matrix* w_out, int64_t* kernel_path) {
+    csr_usable(c, x);
+    if (kernel_path) *kernel_path = 0;
+    const int dt = x.dtype;
+    const int64_t n = x.rows, d = x.cols;
+    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
+    const NmfScan sx = nmf_csr_scan(c, x);
+    nmf_reject(sx);
+    if (!nmf_csr_sweeps(c, x, k)) {
+        NmfCsrDense dense;
+        nmf_csr_densify(c, x, dense);
+        return nmf_fit(c, dense.m, k, spec, w0, h0, seed, w_out);
+    }
+    const Timer timer;
+    dev_reset_timing(c.dev);
+    c.stats = petal_stats{};
+    const int64_t ks = nmf_csr_padded_k(k), kk1 = ks * ks + 1;
+    DBuf W(c.dev, sizeof(double) * size_t(n) * ks), Ht(c.dev, sizeof(double) * size_t(d) * ks);
+    DBuf B(c.dev, sizeof(double) * size_t(kk1)), HHt(c.dev, sizeof(double) * size_t(kk1));   // each: the Gram matrix, then the sweep's dot
+    std::vector<double> hht;
+    if (w0) {
+        const DevMat W0 = ingest(c, *w0), H0 = ingest(c, *h0);
+        nmf_reject(nmf_scan(c, W0));
+        nmf_reject(nmf_scan(c, H0));
+        op_pad_to_f64(c.dev, dt, W.f64(), n, ks, W0.p, n, k, W0.ld);
+        DBuf Hd(c.dev, sizeof(double) * size_t(k) * d);
+        op_pad_to_f64(c.dev, dt, Hd.f64(), k, d, H0.p, k, d, H0.ld);
+        std::vector<double> hh(size_t(k) * d);
+        dev_d2h(c.dev, hh.data(), Hd.p, Hd.bytes);
+        dev_sync(c.dev);   // (W0 / H0 go back to the pool behind the kernels)
+        nmf_transpose_in(hh.data(), d, k, d, ks, hht);
+    } else {
+        // avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first, then H0, both in row-major order (nmf_fit's stream)
+        const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
+        NmfPcg rng(static_cast<uint64_t>(seed));
+        std::vector<double> hw(size_t(n) * ks, 0.0);
+        hht.assign(size_t(d) * ks, 0.0);
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t j = 0; j < k; ++j) hw[size_t(i) * ks + j] = std::fabs(avg * rng.standard_normal());
+        for (int64_t i = 0; i < k; ++i)
+            for (int64_t j = 0; j < d; ++j) hht[size_t(j) * ks + i] = std::fabs(avg * rng.standard_normal());
+        dev_h2d(c.dev, W.p, hw.data(), W.bytes);
+    }
+    dev_h2d(c.dev, Ht.p, hht.data(), Ht.bytes);
+    // the loss = sqrt(max(0, |X|^2 - 2 <W^T X, H> + <W^T W, H H^T>)) from the two Gram blocks as the sweeps left them
+    std::vector<double> hb(static_cast<size_t>(kk1)), hh2(static_cast<size_t>(kk1));
+    const auto read_loss = [&]() {
+        dev_d2h(c.dev, hb.data(), B.p, B.bytes);
+        dev_d2h(c.dev, hh2.data(), HHt.p, HHt.bytes);
+        dev_sync(c.dev);
+        double dots[2] = {hh2[size_t(ks * ks)], 0.0};
+        for (int64_t i = 0; i < ks * ks; ++i) dots[1] += hb[i] * hh2[i];
+        return nmf_loss(sx.sumsq, dots);
+    };
+    // the loss at the start: Gram(W0), and a column sweep that leaves H alone
+    if (!op_nmf_gram(c.dev, W.f64(), n, ks, nullptr, B.f64())) device_error("Nmf: the device-op layer refused the Gram product");
+    nmf_sweep_into(c, x, 1, k, ks, W.f64(), Ht.f64(), B.f64(), false, 0.0, spec.l1_h, spec.l2_h, 0, HHt.f64());
+    const double err_init = read_loss();
+    double err_prev = err_init, err = err_init;
+    int64_t n_iter = spec.max_iter;
+    bool read = false;   // `err` is the loss of the iteration just run
+    for (int64_t it = 1; it <= spec.max_iter; ++it) {
+        nmf_sweep_into(c, x, 0, k, ks, Ht.f64(), W.f64(), HHt.f64(), false, 0.0, spec.l1_w, spec.l2_w, 1, B.f64());
+        nmf_sweep_into(c, x, 1, k, ks, W.f64(), Ht.f64(), B.f64(), false, 0.0, spec.l1_h, spec.l2_h, 1, HHt.f64());
+        read = false;
+        if (spec.tol > 0 && it % 10 == 0) {
+            err = read_loss();
+            read = true;
+            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
+            err_prev = err;
+        }
+    }
+    if (!read) err = read_loss();
+    if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, ks, *w_out);
+    // the handle is an ordinary petal_nmf: H as kp x dp and H H^T as kp x kp in the dense entries' padding
+    const int64_t kp = nmf_padded_k(k), dp = round_up(d, 16);
+    dev_d2h(c.dev, hht.data(), Ht.p, Ht.bytes);
+    dev_sync(c.dev);
+    std::vector<double> hd(size_t(kp) * dp, 0.0), hg(size_t(kp) * kp, 0.0);
+    for (int64_t i = 0; i < k; ++i) {
+        for (int64_t j = 0; j < d; ++j) hd[size_t(i) * dp + j] = hht[size_t(j) * ks + i];
+        for (int64_t j = 0; j < k; ++j) hg[size_t(i) * kp + j] = hh2[size_t(i) * ks + j];
+    }
+    DBuf H(c.dev, sizeof(double) * hd.size()), G(c.dev, sizeof(double) * hg.size());
+    dev_h2d(c.dev, H.p, hd.data(), H.bytes);
+    dev_h2d(c.dev, G.p, hg.data(), G.bytes);
+    std::unique_ptr<petal_nmf> h(new petal_nmf());
+    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
+    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = 1; h->err = err; h->err_init = err_init;
+    finish_stats(c, timer);
+    h->h = H.f64(); H.p = nullptr;
+    h->hht = G.f64(); G.p = nullptr;
+    if (kernel_path) *kernel_path = 1;
+    return h.release();
+}
+
+void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, int64_t* kernel_path) {
+    nmf_usable(c, h);
+    csr_usable(c, x);
+    if (kernel_path) *kernel_path = 0;
+    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
+    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    const int64_t m = x.rows;
+    check_output(w_out, h.dtype, m, h.k);
+    const NmfScan sx = nmf_csr_scan(c, x);
+    nmf_reject(sx);
+    if (!nmf_csr_sweeps(c, x, h.k)) {
+        NmfCsrDense dense;
+        nmf_csr_densify(c, x, dense);
+        nmf_transform(c, h, dense.m, w_out);
+        return;
+    }
+    if (m == 0) return;
+    const Timer timer;
+    dev_reset_timing(c.dev);
+    c.stats = petal_stats{};
+    // H^T and H H^T in the sweep's padding, from the model's own blocks (a dense fit's among them)
+    const int64_t ks = nmf_csr_padded_k(h.k);
+    std::vector<double> hd(size_t(h.kp) * h.dp), hg(size_t(h.kp) * h.kp), hht, hs(size_t(ks) * ks, 0.0);
+    dev_d2h(c.dev, hd.data(), h.h, sizeof(double) * hd.size());
+    dev_d2h(c.dev, hg.data(), h.hht, sizeof(double) * hg.size());
+    dev_sync(c.dev);
+    nmf_transpose_in(hd.data(), h.dp, h.k, h.d, ks, hht);
+    for (int64_t i = 0; i < h.k; ++i)
+        for (int64_t j = 0; j < h.k; ++j) hs[size_t(i) * ks + j] = hg[size_t(i) * h.kp + j];
+    DBuf Ht(c.dev, sizeof(double) * hht.size()), S(c.dev, sizeof(double) * hs.size()), W(c.dev, sizeof(double) * size_t(m) * ks);
+    dev_h2d(c.dev, Ht.p, hht.data(), Ht.bytes);
+    dev_h2d(c.dev, S.p, hs.data(), S.bytes);
+    const double w0 = std::sqrt(sx.sum / (double(m) * double(h.d)) / double(h.k));
+    nmf_sweep_into(c, x, 0, h.k, ks, Ht.f64(), W.f64(), S.f64(), true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr);
+    h.last_kernel = 1;
+    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, ks, w_out);
+    finish_stats(c, timer);
+    if (kernel_path) *kernel_path = 1;
+}
+
+void nmf_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k, const double* g_in, const double* f, const NmfSpec& spec,
+                   int64_t inner, double* g_out, double* gram_out, double* dot_out, int64_t* info1) {
+    csr_usable(c, x);
+    if (info1) info1[0] = 0;
+    if (k < 1) invalid_input("nmf_sweep: the number of components should be at least 1");
+    if (inner < 0) invalid_input("negative parameter");
+    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0) || std::isinf(spec.l1_w) || std::isinf(spec.l2_w))
+        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    if (dot_out && !gram_out) invalid_input("dot_out comes with gram_out or not at all");
+    const int t = transposed ? 1 : 0, dt = x.dtype;
+    const int64_t R = transposed ? x.cols : x.rows, C = transposed ? x.rows : x.cols;
+    const double l1 = spec.l1_w, l2 = spec.l2_w;
+    if (!x.resident) {   // the plain host loop of a layer without the kernel: the statement in position order
+        const petal_csr::Image& im = x.host[t];
+        std::vector<double> S(size_t(k) * k, 0.0), z(static_cast<size_t>(k)), g(static_cast<size_t>(k)), gn(static_cast<size_t>(k));
+        for (int64_t r = 0; r < C; ++r)
+            for (int64_t i = 0; i < k; ++i)
+                for (int64_t j = 0; j < k; ++j) S[size_t(i) * k + j] += f[r * k + i] * f[r * k + j];
+        if (gram_out) std::fill(gram_out, gram_out + k * k, 0.0);
+        double dot = 0.0;
+        for (int64_t r = 0; r < R; ++r) {
+            std::fill(z.begin(), z.end(), 0.0);
+            for (int64_t q = im.ptr[r]; q < im.ptr[r + 1]; ++q) {
+                const double v = get_elem(im.val.data(), dt, q);
+                for (int64_t j = 0; j < k; ++j) z[j] += v * f[int64_t(im.idx[q]) * k + j];
+            }
+            std::copy(g_in + r * k, g_in + (r + 1) * k, g.begin());
+            for (int64_t it = 0; it < inner; ++it) {
+                for (int64_t j = 0; j < k; ++j) {
+                    double dd = 0.0;
+                    for (int64_t i = 0; i < k; ++i) dd += g[i] * S[size_t(i) * k + j];
+                    double den = (dd + l1) + l2 * g[j];
+                    if (den == 0.0) den = NMF_EPS;
+                    gn[j] = g[j] * (z[j] / den);
+                }
+                g.swap(gn);
+            }
+            std::copy(g.begin(), g.end(), g_out + r * k);
+            if (gram_out) {
+                for (int64_t i = 0; i < k; ++i)
+                    for (int64_t j = 0; j < k; ++j) gram_out[i * k + j] += g[i] * g[j];
+                for (int64_t j = 0; j < k; ++j) dot += z[j] * g[j];
+            }
+        }
+        if (dot_out) *dot_out = dot;
+        return;
+    }
+    if (k > 64) invalid_input("nmf_sweep: the sparse kernel takes at most 64 components");
+    if (R == 0) { if (gram_out) std::fill(gram_out, gram_out + k * k, 0.0); if (dot_out) *dot_out = 0.0; return; }
+    const int64_t ks = nmf_csr_padded_k(k), kk1 = ks * ks + 1;
+    std::vector<double> hg(size_t(R) * ks, 0.0), hf(size_t(std::max<int64_t>(C, 1)) * ks, 0.0);
+    for (int64_t i = 0; i < R; ++i) std::copy(g_in + i * k, g_in + (i + 1) * k, hg.begin() + i * ks);
+    for (int64_t i = 0; i < C; ++i) std::copy(f + i * k, f + (i + 1) * k, hf.begin() + i * ks);
+    // G is formed inside a guard: one row more, every byte 0xFF beforehand.  The guard row must come back untouched and the padding
+    // columns of G as zeros.
+    DBuf Gd(c.dev, sizeof(double) * size_t(R + 1) * ks), F(c.dev, sizeof(double) * hf.size()), S(c.dev, sizeof(double) * size_t(kk1)), GD;
+    if (gram_out) GD = DBuf(c.dev, sizeof(double) * size_t(kk1));
+    dev_memset(c.dev, Gd.p, 0xFF, Gd.bytes);
+    dev_h2d(c.dev, Gd.p, hg.data(), sizeof(double) * hg.size());
+    dev_h2d(c.dev, F.p, hf.data(), F.bytes);
+    if (C == 0) dev_memset(c.dev, S.p, 0, S.bytes);
+    else if (!op_nmf_gram(c.dev, F.f64(), C, ks, nullptr, S.f64())) device_error("Nmf: the device-op layer refused the Gram product");
+    nmf_sweep_into(c, x, t, k, ks, F.f64(), Gd.f64(), S.f64(), false, 0.0, l1, l2, inner, gram_out ? GD.f64() : nullptr);
+    std::vector<double> back(size_t(R + 1) * ks), hgd(gram_out ? size_t(kk1) : 0);
+    dev_d2h(c.dev, back.data(), Gd.p, Gd.bytes);
+    if (gram_out) dev_d2h(c.dev, hgd.data(), GD.p, GD.bytes);
+    dev_sync(c.dev);
+    for (int64_t i = 0; i <= R; ++i)
+        for (int64_t j = 0; j < ks; ++j) {
+            uint64_t bits = 0;
+            std::memcpy(&bits, &back[size_t(i) * ks + j], 8);
+            if (i == R ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_sweep wrote outside the R x k block");
+        }
+    for (int64_t i = 0; i < R; ++i) std::copy(back.begin() + i * ks, back.begin() + i * ks + k, g_out + i * k);
+    if (gram_out)
+        for (int64_t i = 0; i < k; ++i) std::copy(hgd.begin() + i * ks, hgd.begin() + i * ks + k, gram_out + i * k);
+    if (dot_out) *dot_out = hgd[size_t(ks * ks)];
+    if (info1) info1[0] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include "../../include/petal_hip_wide.h"
 #include "../../include/petal_hip_kpca.h"
 #include "../../include/petal_hip_nmf.h"
+#include "../../include/petal_hip_nmf_sparse.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -442,6 +443,37 @@ int petal_nmf_pass(petal_ctx* ctx, const petal_matrix* x, int64_t k, const doubl
         need(spec, "spec");
         need(w_out, "w_out");
         nmf_pass(*ctx, *x, k, w_in, h, nmf_spec(*spec), inner_iters, w_out, a_out, b_out, info1);
+    });
+}
+
+// ---- include/petal_hip_nmf_sparse.h: Nmf on a resident CSR matrix -----------------------------------------------------------------
+int petal_nmf_fit_csr(petal_ctx* ctx, const petal_csr* x, int64_t k, const petal_nmf_spec* spec, const petal_matrix* w0, const petal_matrix* h0,
+                      int64_t seed, petal_nmf** out, const petal_matrix* w_out, int64_t* kernel_path) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(spec, "spec");
+        need(out, "out");
+        *out = nmf_fit_csr(*ctx, *x, k, nmf_spec(*spec), w0, h0, seed, w_out, kernel_path);
+    });
+}
+int petal_nmf_transform_csr(petal_ctx* ctx, petal_nmf* h, const petal_csr* x, const petal_matrix* w_out, int64_t* kernel_path) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        need(x, "x");
+        need(w_out, "w_out");
+        nmf_transform_csr(*ctx, *h, *x, *w_out, kernel_path);
+    });
+}
+int petal_nmf_sweep_csr(petal_ctx* ctx, const petal_csr* x, int transposed, int64_t k, const double* g_in, const double* f,
+                        const petal_nmf_spec* spec, int64_t inner_iters, double* g_out, double* gram_out, double* dot_out, int64_t* info1) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(g_in, "g_in");
+        need(f, "f");
+        need(spec, "spec");
+        need(g_out, "g_out");
+        nmf_sweep_csr(*ctx, *x, transposed != 0, k, g_in, f, nmf_spec(*spec), inner_iters, g_out, gram_out, dot_out, info1);
     });
 }
 

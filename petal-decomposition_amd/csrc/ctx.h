@@ -197,6 +197,12 @@ void nmf_destroy(petal_nmf* h);
 void nmf_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out);
 void nmf_inverse_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& w, const petal_matrix& x_out);
 void nmf_get(const petal_nmf& h, double* components, int64_t* info6, double* err2);
+// include/petal_hip_nmf_sparse.h: Nmf on a sparse matrix
+petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                       int64_t seed, const petal_matrix* w_out, int64_t* kernel_path);
+void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, int64_t* kernel_path);
+void nmf_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k, const double* g_in, const double* f, const NmfSpec& spec,
+                   int64_t inner, double* g_out, double* gram_out, double* dot_out, int64_t* info1);
 void nmf_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* h, const NmfSpec& spec, int64_t inner, double* w_out,
               double* a_out, double* b_out, int64_t* info1);
 // include/petal_hip_ipca.h: IncrementalPca

@@ -350,6 +350,9 @@ static void nmf_pass_ft(Dev* d, bool ab, int g, const T* X, int64_t ldx, int64_t
 bool op_nmf_pass(Dev* d, int dt, const void* X, int64_t n, int64_t dp, int64_t ldx, const double* H, const double* HHt, int64_t k, int64_t kp,
                  double* W, bool from_const, double wconst, double l1, double l2, int64_t inner, double* A, double* B) {
     const int64_t el = dt == F32 ? 4 : 2;
+    // (the kernel exists for 16, 32 and 64 padded components only: nmf_padded_k gives 48 for k = 33 .. 48, which the KT = 4 form would
+    //  walk with a row pitch of 64 -- past the end of W, H and H H^T; those fits take the composed path)
+    if (kp != 16 && kp != 32 && kp != 64) return false;
     if (n < 1 || n > (int64_t(1) << 40) || k < 1 || k > 64 || kp != nmf_padded_k(k) || dp < 16 || dp % 16 || dp > 512 || ldx < dp || ldx % el ||
         !aligned16(X) || !aligned16(H) || inner < 0 || inner > (int64_t(1) << 30) || !W || !aligned16(W) || !HHt || ((A == nullptr) != (B == nullptr)))
         return false;

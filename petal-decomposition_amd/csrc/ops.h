@@ -238,7 +238,7 @@ bool op_kpca_finish(Dev*, int dtype, const double* O, int64_t ldo, int64_t m, in
 // Nmf (include/petal_hip_nmf.h; an extension beyond the crate): multiplicative updates for the Frobenius loss.  Device layouts, all
 // fp64: W n x kp, H and A kp x dp (leading dimension dp), H H^T and B kp x kp, kp = nmf_padded_k(k), ZERO in every padding row and
 // column.  Each returns "this layer did the work": false, NOTHING done, where the shape is outside the kernel's envelope (k > 64,
-// dp > 512), X does not allow 16-byte loads along its rows or the layer lacks the op -- algo.cpp's weak defaults return false and the
+// kp = 48, dp > 512), X does not allow 16-byte loads along its rows or the layer lacks the op -- algo.cpp's weak defaults return false and the
 // caller builds the same statement from op_cvt_to_f64, op_dgemm and an element-wise step on the host.
 inline int64_t nmf_padded_k(int64_t k) { return k <= 16 ? 16 : (k <= 32 ? 32 : (k + 15) / 16 * 16); }
 // out4 (DEVICE) = { sum x, sum x^2, min(x, 0), 1 if a NaN or an infinity was seen else 0 } over X (n x dp in dtype, ldx), fp64, a fixed order.
@@ -252,6 +252,23 @@ bool op_nmf_pass(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64_t 
 // The H side of an iteration: E = B H + l1 + l2 H, E[E == 0] = 2^-23, H <- H o A / E, HHt = H H^T, dots2 (DEVICE) = { <A, H>, <B, HHt> }
 // with the new H (the two inner products of the loss).
 bool op_nmf_hupdate(Dev*, int64_t kp, int64_t dp, const double* A, const double* B, double* H, double* HHt, double l1, double l2, double* dots2);
+// Nmf on sparse CSR data (include/petal_hip_nmf_sparse.h; an extension beyond the crate).  The sweep's own padding: 16, 32 or 64 columns
+// (nmf_padded_k gives 48, which does not fill whole lanes of a gathered row).  Each returns "this layer did the work": false, NOTHING
+// done, where the shape is outside the kernel's envelope (k > 64) or the layer lacks the op -- algo.cpp's weak defaults return false.
+inline int64_t nmf_csr_padded_k(int64_t k) { return k <= 16 ? 16 : (k <= 32 ? 32 : 64); }
+// One sweep of an image (img.rows = R, its column count = C): G (R x kp, DEVICE fp64, in place; from_const: starts as gconst in its k
+// leading columns), F (C x kp), S = F^T F (kp x kp), all ZERO in the padding:
+//     z_r = sum over the stored entries t of row r, in the items' fixed order, of val[t] F[idx[t], :]
+//     inner times:  D = g_r S + l1 + l2 g_r,  D[D == 0] = 2^-23,  g_r <- g_r o (z_r / D)        (inner == 0 without from_const: G is left alone)
+// gram_dot (nullable, DEVICE, kp kp + 1 doubles): G^T G with the G just written, then sum_r <z_r, g_r>.  No atomics.
+bool op_nmf_sweep_csr(Dev*, int dtype, const CsrImage& img, int64_t k, int64_t kp, const double* F, double* G, const double* S, bool from_const,
+                      double gconst, double l1, double l2, int64_t inner, double* gram_dot);
+// gram_dot (DEVICE, kp kp + 1 doubles) = { G^T G, sum of dots (nullable: 0) } over G (rows x kp fp64), a fixed order.
+bool op_nmf_gram(Dev*, const double* G, int64_t rows, int64_t kp, const double* dots, double* gram_dot);
+// out4 (DEVICE) = { sum v, sum v^2, min(v, 0), 1 if a NaN or an infinity was seen else 0 } over nnz stored values in dtype.
+bool op_nmf_valscan(Dev*, int dtype, const void* val, int64_t nnz, double* out4);
+// out (img.rows x cols in dtype, ldo; DEVICE) = the dense image: zeros, then every stored entry added in position order.
+bool op_csr_densify(Dev*, int dtype, const CsrImage& img, void* out, int64_t cols, int64_t ldo);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns
 // L .. M of the result are zero), Z = (X - mu) . P_out.  Same results contract as op_chol_inv(G -> T, Lz = M) followed by
 // op_gemm_xp_prod(A, T); T (M x M, ldt) is SCRATCH here -- it may hold R^-1 or a factored form of it, callers must not read it.

@@ -6,6 +6,7 @@ mod ffi;
 mod ffi_ipca;
 mod ffi_kpca;
 mod ffi_nmf;
+mod ffi_nmf_sparse;
 mod ffi_score;
 mod ffi_segments;
 mod ffi_sparse;

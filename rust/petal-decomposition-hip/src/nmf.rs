@@ -2,6 +2,8 @@
 //! beta_loss="frobenius")`.  An iteration is one fused pass over the data; `transform` is one pass whatever `max_iter` is.  Everything
 //! is float64 inside; outputs are rounded once to `A`.
 use crate::ffi_nmf::{self, PetalNmf, PetalNmfSpec};
+use crate::ffi_nmf_sparse;
+use crate::pca::CsrMatrix;
 use crate::{view, with_ctx, DecompositionError, HipScalar};
 use ndarray::{Array2, ArrayBase, Data, Ix2};
 use std::marker::PhantomData;
@@ -37,12 +39,13 @@ pub struct Nmf<A: HipScalar> {
     raw: *mut PetalNmf,
     k: usize,
     params: NmfParams,
+    kernel_path: i64,
     _a: PhantomData<A>,
 }
 unsafe impl<A: HipScalar> Send for Nmf<A> {}
 
 impl<A: HipScalar> Nmf<A> {
-    pub fn new(n_components: usize, params: NmfParams) -> Self { Self { raw: std::ptr::null_mut(), k: n_components, params, _a: PhantomData } }
+    pub fn new(n_components: usize, params: NmfParams) -> Self { Self { raw: std::ptr::null_mut(), k: n_components, params, kernel_path: 0, _a: PhantomData } }
     pub fn n_components(&self) -> usize { self.k }
 
     /// Random initialisation from `Pcg(seed)`.
@@ -94,6 +97,57 @@ impl<A: HipScalar> Nmf<A> {
         Ok(NmfInfo { n: v[0], d: v[1], k: v[2], n_iter: v[3], fit_kernel: v[4] != 0, transform_kernel: v[5] })
     }
 
+    /// Sparse CSR input (include/petal_hip_nmf_sparse.h; source only, unverified like the rest of this crate): never densified where
+    /// the sweep kernel runs (at most 64 components, a resident handle); `kernel_path` says which path the last sparse call took.
+    pub fn fit_csr(&mut self, input: &CsrMatrix<A>) -> Result<(), DecompositionError> { self.inner_fit_csr(input, None, None) }
+    pub fn fit_transform_csr(&mut self, input: &CsrMatrix<A>) -> Result<Array2<A>, DecompositionError> {
+        let mut w = Array2::<A>::default((input.nrows(), self.k));
+        self.inner_fit_csr(input, None, Some(&mut w))?;
+        Ok(w)
+    }
+    pub fn fit_transform_csr_from(&mut self, input: &CsrMatrix<A>, w0: &Array2<A>, h0: &Array2<A>) -> Result<Array2<A>, DecompositionError> {
+        let mut w = Array2::<A>::default((input.nrows(), self.k));
+        self.inner_fit_csr(input, Some((w0, h0)), Some(&mut w))?;
+        Ok(w)
+    }
+    pub fn transform_csr(&mut self, input: &CsrMatrix<A>) -> Result<Array2<A>, DecompositionError> {
+        let raw = self.handle()?;
+        let mut w = Array2::<A>::default((input.nrows(), self.k));
+        let wv = view(&w.view_mut());
+        let mut path = 0i64;
+        with_ctx(|ctx| unsafe { ffi_nmf_sparse::petal_nmf_transform_csr(ctx, raw, input.raw(), &wv, &mut path) }, || ())?;
+        self.kernel_path = path;
+        Ok(w)
+    }
+    /// 1: the sweep kernel ran in the last sparse call; 0: the call densified.
+    pub fn kernel_path(&self) -> i64 { self.kernel_path }
+
+    fn spec(&self, n: f64, d: f64) -> PetalNmfSpec {
+        let p = self.params;
+        let (aw, ah, rho) = (p.alpha_w, p.alpha_h.unwrap_or(p.alpha_w), p.l1_ratio);
+        PetalNmfSpec { max_iter: p.max_iter as i64, tol: p.tol, l1_w: d * aw * rho, l2_w: d * aw * (1.0 - rho), l1_h: n * ah * rho, l2_h: n * ah * (1.0 - rho) }
+    }
+    fn inner_fit_csr(&mut self, input: &CsrMatrix<A>, init: Option<(&Array2<A>, &Array2<A>)>, w: Option<&mut Array2<A>>)
+        -> Result<(), DecompositionError> {
+        let wv = w.map(|w| view(&w.view_mut()));
+        let iv = init.map(|(w0, h0)| (view(w0), view(h0)));
+        let spec = self.spec(input.nrows() as f64, input.ncols() as f64);
+        let mut raw = std::ptr::null_mut();
+        let mut path = 0i64;
+        let (k, seed) = (self.k as i64, self.params.seed as i64);
+        with_ctx(
+            |ctx| unsafe {
+                ffi_nmf_sparse::petal_nmf_fit_csr(ctx, input.raw(), k, &spec, iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _),
+                                                  iv.as_ref().map_or(std::ptr::null(), |m| &m.1 as *const _), seed, &mut raw,
+                                                  wv.as_ref().map_or(std::ptr::null(), |m| m as *const _), &mut path)
+            },
+            || (),
+        )?;
+        unsafe { ffi_nmf::petal_nmf_destroy(self.raw) };
+        self.raw = raw;
+        self.kernel_path = path;
+        Ok(())
+    }
     fn handle(&self) -> Result<*mut PetalNmf, DecompositionError> {
         if self.raw.is_null() {
             return Err(DecompositionError::InvalidInput("the model has not been fitted".into()));
@@ -105,15 +159,9 @@ impl<A: HipScalar> Nmf<A> {
         let x = view(input);
         let wv = w.map(|w| view(&w.view_mut()));
         let iv = init.map(|(w0, h0)| (view(w0), view(h0)));
-        let (n, d) = (input.nrows() as f64, input.ncols() as f64);
-        let p = self.params;
-        let (aw, ah, rho) = (p.alpha_w, p.alpha_h.unwrap_or(p.alpha_w), p.l1_ratio);
-        let spec = PetalNmfSpec {
-            max_iter: p.max_iter as i64, tol: p.tol,
-            l1_w: d * aw * rho, l2_w: d * aw * (1.0 - rho), l1_h: n * ah * rho, l2_h: n * ah * (1.0 - rho),
-        };
+        let spec = self.spec(input.nrows() as f64, input.ncols() as f64);
         let mut raw = std::ptr::null_mut();
-        let (k, seed) = (self.k as i64, p.seed as i64);
+        let (k, seed) = (self.k as i64, self.params.seed as i64);
         with_ctx(
             |ctx| unsafe {
                 ffi_nmf::petal_nmf_fit(ctx, &x, k, &spec, iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _),

@@ -566,6 +566,7 @@ impl<A: HipScalar> CsrMatrix<A> {
     pub fn nrows(&self) -> usize { self.rows }
     pub fn ncols(&self) -> usize { self.cols }
     pub fn nnz(&self) -> usize { self.nnz }
+    pub(crate) fn raw(&self) -> *const ffi_sparse::PetalCsr { self.raw }
     /// false where the device-op layer has no sparse product: the fit and the transform then densify on the host
     pub fn resident(&self) -> bool {
         let mut v = [0i64; 8];
