@@ -29,6 +29,7 @@
 #include "petal_hip_kpca.h"
 #include "petal_hip_nmf.h"
 #include "petal_hip_nmf_sparse.h"
+#include "petal_hip_nmf_kl.h"
 
 namespace petal_decomposition {
 
@@ -568,6 +569,10 @@ struct NmfInfo {
 template <class A>
 class CsrMatrix;   // (declared below: Nmf takes it in place of an Array2, petal_hip_nmf_sparse.h)
 
+// extension beyond the crate (petal_hip_nmf_kl.h): the loss of a fit on sparse CSR input.  KullbackLeibler is scikit-learn's
+// beta_loss="kullback-leibler"; it is taken by the CsrMatrix overloads only -- the dense overloads throw InvalidInput under it.
+enum class NmfLoss : int64_t { Frobenius = PETAL_NMF_LOSS_FROBENIUS, KullbackLeibler = PETAL_NMF_LOSS_KL };
+
 template <class A>
 class Nmf {
   public:
@@ -579,8 +584,16 @@ class Nmf {
     Nmf& operator=(const Nmf&) = delete;
     Nmf(Nmf&& o) noexcept
         : k_(o.k_), max_iter_(o.max_iter_), tol_(o.tol_), seed_(o.seed_), alpha_w_(o.alpha_w_), alpha_h_(o.alpha_h_), l1_ratio_(o.l1_ratio_),
-          ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+          ctx_(o.ctx_), h_(o.h_), kernel_path_(o.kernel_path_), loss_(o.loss_) { o.h_ = nullptr; }
     ~Nmf() { petal_nmf_destroy(h_); }
+    Nmf& loss(NmfLoss l) { loss_ = l; return *this; }   // the loss of the NEXT fit on a CsrMatrix (petal_hip_nmf_kl.h)
+    NmfLoss loss() const { return loss_; }
+    // the loss the fitted model remembers
+    NmfLoss model_loss() const {
+        int64_t v = 0;
+        if (petal_nmf_get_loss(handle(), &v) != PETAL_OK) throw DecompositionError(DecompositionError::InvalidInput, "petal_nmf_get_loss failed");
+        return static_cast<NmfLoss>(v);
+    }
     Nmf& fit(const Array2<A>& input) { inner_fit(input, nullptr, nullptr, nullptr); return *this; }
     Nmf& fit(const Array2<A>& input, const Array2<A>& w0, const Array2<A>& h0) { inner_fit(input, &w0, &h0, nullptr); return *this; }
     Array2<A> fit_transform(const Array2<A>& input) {
@@ -594,6 +607,7 @@ class Nmf {
         return w;
     }
     Array2<A> transform(const Array2<A>& input) {
+        no_dense_kl();
         Array2<A> w(input.nrows(), k_);
         petal_matrix mx = input.view(), mw = w.view();
         context().check(petal_nmf_transform(context().get(), handle(), &mx, &mw));
@@ -657,7 +671,13 @@ class Nmf {
         if (!h_) throw DecompositionError(DecompositionError::InvalidInput, "the model has not been fitted");
         return h_;
     }
+    void no_dense_kl() const {
+        if (loss_ == NmfLoss::KullbackLeibler)
+            throw DecompositionError(DecompositionError::InvalidInput,
+                                     "Nmf: the kullback-leibler loss takes a CsrMatrix (compress the dense rows to the CSR of their non-zero entries)");
+    }
     void inner_fit(const Array2<A>& input, const Array2<A>* w0, const Array2<A>* h0, Array2<A>* w) {
+        no_dense_kl();
         petal_matrix mx = input.view(), m0{}, m1{}, mw{};
         if (w0) { m0 = w0->view(); m1 = h0->view(); }
         if (w) mw = w->view();
@@ -682,8 +702,12 @@ class Nmf {
         spec.l1_w = d * alpha_w_ * l1_ratio_; spec.l2_w = d * alpha_w_ * (1.0 - l1_ratio_);
         spec.l1_h = n * alpha_h_ * l1_ratio_; spec.l2_h = n * alpha_h_ * (1.0 - l1_ratio_);
         petal_nmf* h = nullptr;
-        context().check(petal_nmf_fit_csr(context().get(), input.get(), k_, &spec, w0 ? &m0 : nullptr, w0 ? &m1 : nullptr, int64_t(seed_), &h,
-                                          w ? &mw : nullptr, &kernel_path_));
+        if (loss_ == NmfLoss::Frobenius)
+            context().check(petal_nmf_fit_csr(context().get(), input.get(), k_, &spec, w0 ? &m0 : nullptr, w0 ? &m1 : nullptr, int64_t(seed_), &h,
+                                              w ? &mw : nullptr, &kernel_path_));
+        else
+            context().check(petal_nmf_fit_csr_loss(context().get(), input.get(), k_, &spec, static_cast<int64_t>(loss_), w0 ? &m0 : nullptr,
+                                                   w0 ? &m1 : nullptr, int64_t(seed_), &h, w ? &mw : nullptr, &kernel_path_));
         petal_nmf_destroy(h_);
         h_ = h;
     }
@@ -694,6 +718,7 @@ class Nmf {
     Context* ctx_;
     petal_nmf* h_ = nullptr;
     int64_t kernel_path_ = 0;
+    NmfLoss loss_ = NmfLoss::Frobenius;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

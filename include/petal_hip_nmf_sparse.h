@@ -39,7 +39,8 @@
  * Measured: see README.md (Nmf on sparse data) and EXPERIMENTS.md; every figure not measured on the device is marked "unmeasured".
  *
  * Not in this version: sharded fits, device-resident CSR arrays, other beta-losses, a tolerance stop in transform, k > 64 on the sweep
- * (it densifies), CSR output of inverse_transform.
+ * (it densifies), CSR output of inverse_transform.  (The Kullback-Leibler loss has since been added beside this header:
+ * petal_hip_nmf_kl.h.)
  */
 #ifndef PETAL_HIP_NMF_SPARSE_H
 #define PETAL_HIP_NMF_SPARSE_H

@@ -234,6 +234,14 @@ ABI_NMF_SPARSE = [
     ("petal_nmf_sweep_csr", C.c_int, [_P, _P, C.c_int, C.c_int64, _D, _D, _NS, C.c_int64, _D, _D, _D, _L]),
 ]
 
+# every symbol include/petal_hip_nmf_kl.h declares (Nmf with the Kullback-Leibler loss on sparse CSR data and its sweep by itself)
+NMF_LOSS_FROBENIUS, NMF_LOSS_KL = 0, 1
+ABI_NMF_KL = [
+    ("petal_nmf_fit_csr_loss", C.c_int, [_P, _P, C.c_int64, _NS, C.c_int64, _M, _M, C.c_int64, C.POINTER(C.c_void_p), _M, _L]),
+    ("petal_nmf_get_loss", C.c_int, [_P, _L]),
+    ("petal_nmf_kl_sweep_csr", C.c_int, [_P, _P, C.c_int, C.c_int64, _D, _D, _NS, C.c_int64, _D, _D, _D, _L]),
+]
+
 
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
@@ -251,7 +259,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h, petal_hip_nmf_sparse.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h, petal_hip_nmf_sparse.h, petal_hip_nmf_kl.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -260,7 +268,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF + ABI_NMF_SPARSE:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF + ABI_NMF_SPARSE + ABI_NMF_KL:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -838,6 +846,67 @@ def nmf_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0, i
     return (out, {"kernel": int(info[0])}) if want_info else out
 
 
+def nmf_kl_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0, inner_iters=1, want_term: Optional[bool] = None,
+                 want_info: bool = False):
+    """Test aid (``petal_nmf_kl_sweep_csr``, include/petal_hip_nmf_kl.h): one Kullback-Leibler sweep of sparse ``Nmf`` by itself, in
+    float64, over the matrix (``transposed=False``: R x C = ``sx.shape``) or its transposed image.  ``g`` (R x k) is updated, ``f``
+    (C x k) gathered, c = colsum(f): ``inner_iters`` times, for every stored entry of row r, wh = max(<g_r, f[idx]>, 2^-23),
+    num = sum val / wh f[idx], den = c + l1 + l2 g_r, den[den == 0] = 2^-23, g_r <- g_r o num / den.  Returns ``(g_new, colsum)`` with
+    colsum = the column sums of g_new; with ``inner_iters=0`` (``want_term`` defaults to that) ``(g, colsum, term)`` with
+    term = sum [val > 2^-23] val log(val / wh).  ``want_info``: also ``{"kernel": k_nmf_kl_sweep ran}``."""
+    rows, inner = (sx.shape[1], sx.shape[0]) if transposed else sx.shape
+    g = np.ascontiguousarray(np.asarray(g, dtype=np.float64))
+    f = np.ascontiguousarray(np.asarray(f, dtype=np.float64))
+    if g.ndim != 2 or f.ndim != 2 or g.shape[0] != rows or f.shape != (inner, g.shape[1]):
+        raise InvalidInput(f"g should be {rows} x k and f {inner} x k")
+    k = g.shape[1]
+    if want_term is None:
+        want_term = int(inner_iters) == 0
+    spec = _nmf_spec(1, 0.0, l1, l2)
+    go, colsum, term = np.zeros((rows, k)), np.zeros(k), np.zeros(1)
+    info = (C.c_int64 * 1)()
+    ctx = sx.ctx
+    ctx.check(ctx.lib.petal_nmf_kl_sweep_csr(ctx._h, sx._handle(), int(bool(transposed)), k, g.ctypes.data_as(_D), f.ctypes.data_as(_D),
+                                             C.byref(spec), int(inner_iters), go.ctypes.data_as(_D), colsum.ctypes.data_as(_D),
+                                             term.ctypes.data_as(_D) if want_term else None, info))
+    out = (go, colsum, float(term[0])) if want_term else (go, colsum)
+    return (out, {"kernel": int(info[0])}) if want_info else out
+
+
+def _like_input(x, w):
+    """w (a numpy array computed on the host) where x lives: a torch tensor on x's device for a torch x"""
+    if _is_torch(x):
+        import torch
+        return torch.from_numpy(w).to(x.device)
+    return w
+
+
+def _beta_loss_code(beta_loss) -> int:
+    if isinstance(beta_loss, str):
+        if beta_loss in ("frobenius", "kullback-leibler"):
+            return NMF_LOSS_FROBENIUS if beta_loss == "frobenius" else NMF_LOSS_KL
+    elif not isinstance(beta_loss, bool) and beta_loss in (1, 2):
+        return NMF_LOSS_KL if beta_loss == 1 else NMF_LOSS_FROBENIUS
+    raise InvalidInput(f"unknown beta_loss {beta_loss!r} ('frobenius' / 2 or 'kullback-leibler' / 1)")
+
+
+class _DenseAsCsr:
+    """the CSR of the non-zero entries of a dense array, row by row in column order (what the Kullback-Leibler loss reads of it)"""
+
+    def __init__(self, x):
+        if _is_torch(x):
+            x = x.detach().cpu().numpy()   # (a device tensor is copied to the host: the compression runs there)
+        x = np.asarray(x)
+        if x.ndim != 2:
+            raise InvalidInput("expected a 2-D array")
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64)
+        r, c = np.nonzero(x)
+        self.indptr = np.zeros(x.shape[0] + 1, dtype=np.int64)
+        np.cumsum(np.bincount(r, minlength=x.shape[0]), out=self.indptr[1:])
+        self.data, self.indices, self.shape = x[r, c], c.astype(np.int32), x.shape
+
+
 class Nmf:
     """Non-negative matrix factorisation X ~ W H (``petal_nmf``, include/petal_hip_nmf.h; an extension beyond the crate, DESIGN.md
     sections 4 and 7) -- scikit-learn's ``NMF(solver="mu", beta_loss="frobenius")``.  ``fit``, ``fit_transform`` and ``transform``
@@ -845,12 +914,19 @@ class Nmf:
     ``Pcg(seed)``; ``init="custom"`` takes them from ``fit_transform(x, W=..., H=...)``.  ``alpha_W``, ``alpha_H`` ("same": alpha_W)
     and ``l1_ratio`` are scikit-learn's penalties.  ``tol > 0`` stops at a check every 10th iteration; ``transform`` runs exactly
     ``max_iter`` W-updates in one pass over its input.  Everything is float64 inside; outputs are rounded once to the data's type.
-    The fitted model lives with its ctx."""
+    The fitted model lives with its ctx.
+
+    ``beta_loss="kullback-leibler"`` (or 1; include/petal_hip_nmf_kl.h) fits the generalised Kullback-Leibler divergence instead of the
+    Frobenius loss ("frobenius" or 2, the default).  It runs on sparse input at the stored entries alone: a dense array is compressed
+    here, on the host, to the CSR of its non-zero entries (a ``torch.cuda`` tensor is copied to the host for that) and takes the same
+    path; at most 64 components; ``transform`` then costs ``max_iter`` sweeps.  ``beta_loss`` is readable."""
 
     def __init__(self, n_components: int, max_iter: int = 200, tol: float = 1e-4, init: str = "random", seed: int = 0,
-                 alpha_W: float = 0.0, alpha_H="same", l1_ratio: float = 0.0, ctx: Optional[Context] = None):
+                 alpha_W: float = 0.0, alpha_H="same", l1_ratio: float = 0.0, ctx: Optional[Context] = None, beta_loss="frobenius"):
         if init not in ("random", "custom"):
             raise InvalidInput(f"unknown init {init!r} (random or custom)")
+        self._loss = _beta_loss_code(beta_loss)
+        self.beta_loss = "frobenius" if self._loss == NMF_LOSS_FROBENIUS else "kullback-leibler"
         self._k = int(n_components)
         self.max_iter, self.tol, self.init, self.seed = int(max_iter), float(tol), init, int(seed)
         self.alpha_W, self.alpha_H, self.l1_ratio = float(alpha_W), alpha_H, float(l1_ratio)
@@ -925,9 +1001,12 @@ class Nmf:
                 w = np.empty((rows, self._k), dtype=_np_dtype(sx._dt))
                 mo = describe(w, keep)
             h, path = C.c_void_p(), C.c_int64(0)
-            ctx.check(ctx.lib.petal_nmf_fit_csr(ctx._h, sx._handle(), self._k, C.byref(spec), C.byref(mw) if mw is not None else None,
-                                                C.byref(mh) if mh is not None else None, C.c_int64(self.seed & ((1 << 64) - 1)),
-                                                C.byref(h), C.byref(mo) if mo is not None else None, C.byref(path)))
+            args = (C.byref(mw) if mw is not None else None, C.byref(mh) if mh is not None else None,
+                    C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h), C.byref(mo) if mo is not None else None, C.byref(path))
+            if self._loss == NMF_LOSS_FROBENIUS:
+                ctx.check(ctx.lib.petal_nmf_fit_csr(ctx._h, sx._handle(), self._k, C.byref(spec), *args))
+            else:
+                ctx.check(ctx.lib.petal_nmf_fit_csr_loss(ctx._h, sx._handle(), self._k, C.byref(spec), self._loss, *args))
             self.close()
             self._h = h
             ctx._nmf.add(self)
@@ -940,6 +1019,9 @@ class Nmf:
     def _inner_fit(self, x, W, H, want_w: bool):
         if _is_sparse(x):
             return self._inner_fit_sparse(x, W, H, want_w)
+        if self._loss == NMF_LOSS_KL:   # dense input under this loss: the CSR of its non-zero entries, the same path
+            w = self._inner_fit_sparse(_DenseAsCsr(x), W, H, want_w)
+            return _like_input(x, w) if want_w else None
         keep = []
         mx = describe(x, keep)
         ctx = self._ctx()
@@ -968,8 +1050,11 @@ class Nmf:
     def transform(self, x):
         """``max_iter`` W-updates with H fixed; sparse input (a CsrMatrix or an object with .data / .indices / .indptr / .shape) goes
         through the sparse sweep and sets ``kernel_path``."""
+        self._handle()
+        dense_kl = not _is_sparse(x) and self._model_loss() == NMF_LOSS_KL
+        if dense_kl:
+            return _like_input(x, self.transform(_DenseAsCsr(x)))
         if _is_sparse(x):
-            self._handle()
             sx, mine = self._sparse(x)
             try:
                 ctx = self._ctx()
@@ -1007,6 +1092,12 @@ class Nmf:
                                       err.ctypes.data_as(_D) if err is not None else None) != PETAL_OK:
             raise InvalidInput("petal_nmf_get failed")
         return out
+
+    def _model_loss(self) -> int:
+        out = C.c_int64(0)
+        if self._ctx().lib.petal_nmf_get_loss(self._handle(), C.byref(out)) != PETAL_OK:
+            raise InvalidInput("petal_nmf_get_loss failed")
+        return int(out.value)
 
     def info(self) -> dict:
         """n, d, k, ``n_iter``, ``fit_kernel`` (k_nmf_pass ran in the fit; 0: the composed path), ``transform_kernel`` (the same for

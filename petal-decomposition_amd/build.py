@@ -15,6 +15,7 @@ HEADERS = ["ops.h", "ctx.h", os.path.join("..", "..", "include", "petal_hip.h"),
            os.path.join("..", "..", "include", "petal_hip_kpca.h"),
            os.path.join("..", "..", "include", "petal_hip_nmf.h"),
            os.path.join("..", "..", "include", "petal_hip_nmf_sparse.h"),
+           os.path.join("..", "..", "include", "petal_hip_nmf_kl.h"),
            os.path.join("..", "..", "include", "petal_hip_probe.h")] + \
     [os.path.join("kernels", f) for f in sorted(os.listdir(os.path.join(CSRC, "kernels"))) if f.endswith(".inc")]   # the parts of hip_ops.hip
 

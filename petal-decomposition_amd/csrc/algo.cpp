@@ -1861,6 +1861,8 @@ petal_nmf* nmf_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec
 
 void nmf_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
     nmf_usable(c, h);
+    if (h.loss != 0)
+        invalid_input("Nmf: the dense transform does not take a kullback-leibler model (petal_nmf_transform_csr does: compress the rows to CSR)");
     const Timer timer = start_fit(c, x);
     if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
     if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
@@ -3645,6 +3647,7 @@ void nmf_sweep_into(petal_ctx& c, const petal_csr& x, int t, int64_t k, int64_t 
     dev_set_tag(c.dev, TAG_NONE);
     if (!ran) device_error("Nmf: the device-op layer refused the sparse sweep");
 }
+void nmf_kl_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, const NmfScan& sx, int64_t* kernel_path);
 }  // namespace
 
 petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
@@ -3754,6 +3757,10 @@ void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const pet
     check_output(w_out, h.dtype, m, h.k);
     const NmfScan sx = nmf_csr_scan(c, x);
     nmf_reject(sx);
+    if (h.loss != 0) {   // a Kullback-Leibler model (include/petal_hip_nmf_kl.h): its own sweep, never densified
+        nmf_kl_transform_csr(c, h, x, w_out, sx, kernel_path);
+        return;
+    }
     if (!nmf_csr_sweeps(c, x, h.k)) {
         NmfCsrDense dense;
         nmf_csr_densify(c, x, dense);
@@ -3861,6 +3868,378 @@ void nmf_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k,
     if (gram_out)
         for (int64_t i = 0; i < k; ++i) std::copy(hgd.begin() + i * ks, hgd.begin() + i * ks + k, gram_out + i * k);
     if (dot_out) *dot_out = hgd[size_t(ks * ks)];
+    if (info1) info1[0] = 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Nmf with the generalised Kullback-Leibler loss on sparse CSR data (include/petal_hip_nmf_kl.h; DESIGN.md sections 4 and 7).  The updates
+// touch X only at its stored entries, so an iteration is two sweeps of op_nmf_kl_sweep_csr: over the rows of X with G = W, F = H^T,
+// c = rowsum(H), and over the rows of the transposed image with G = H^T, F = the new W, c = colsum(W); each leaves colsum(G) on the
+// device for the next one.  The loss is read by a sweep with inner = 0.  ONE driver runs on two engines: the kernels on a resident handle,
+// and a plain host loop of the statement in position order on a handle that is not resident (a device-op layer without the kernels) or
+// with PETAL_OPT_NMF_FALLBACK set (the images of a resident handle are copied back).  There is no densifying path.
+__attribute__((weak)) bool op_nmf_kl_sweep_csr(Dev*, int, const CsrImage&, int64_t, int64_t, const double*, double*, const double*, bool, double,
+                                               double, double, int64_t, double*) {
+    return false;
+}
+__attribute__((weak)) bool op_nmf_kl_colsum(Dev*, const double*, int64_t, int64_t, const double*, double*) { return false; }
+__attribute__((weak)) bool op_nmf_kl_vsum(Dev*, int, const void*, int64_t, double*) { return false; }
+
+namespace {
+constexpr int64_t NMF_LOSS_FROBENIUS = 0, NMF_LOSS_KL = 1;
+
+// an image on the host, values widened
+struct KlHostImage {
+    int64_t rows = 0;
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> idx;
+    std::vector<double> val;
+};
+KlHostImage kl_host_image(petal_ctx& c, const petal_csr& x, int t) {
+    KlHostImage im;
+    im.rows = t ? x.cols : x.rows;
+    im.val.resize(size_t(x.nnz));
+    if (!x.resident) {
+        im.ptr = x.host[t].ptr;
+        im.idx = x.host[t].idx;
+        for (int64_t q = 0; q < x.nnz; ++q) im.val[size_t(q)] = get_elem(x.host[t].val.data(), x.dtype, q);
+        return im;
+    }
+    // a resident handle keeps no host copy: the indices, the values and the work items come back (every row has at least one item,
+    // the items are in row order)
+    const CsrImage& dv = x.dev[t];
+    std::vector<CsrItem> items(static_cast<size_t>(dv.n_items));
+    std::vector<char> raw(dtype_size(x.dtype) * size_t(x.nnz));
+    im.idx.resize(size_t(x.nnz));
+    if (dv.n_items) dev_d2h(c.dev, items.data(), dv.items, sizeof(CsrItem) * items.size());
+    if (x.nnz) {
+        dev_d2h(c.dev, im.idx.data(), dv.idx, sizeof(int32_t) * size_t(x.nnz));
+        dev_d2h(c.dev, raw.data(), dv.val, raw.size());
+    }
+    dev_sync(c.dev);
+    im.ptr.assign(size_t(im.rows) + 1, 0);
+    for (const CsrItem& it : items) im.ptr[size_t(it.row) + 1] = it.first + it.count;
+    for (int64_t q = 0; q < x.nnz; ++q) im.val[size_t(q)] = get_elem(raw.data(), x.dtype, q);
+    return im;
+}
+
+// the header's sweep on the host, in position order; G, F: leading dimension k.  colsum (k, nullable) = colsum(G) afterwards; term
+// (nullable) is written for inner == 0 only.
+void kl_host_sweep(const KlHostImage& im, int64_t k, const double* F, double* G, const double* csum, bool from_const, double gconst, double l1,
+                   double l2, int64_t inner, double* colsum, double* term) {
+    std::vector<double> num(static_cast<size_t>(k));
+    double tsum = 0.0;
+    for (int64_t r = 0; r < im.rows; ++r) {
+        double* g = G + r * k;
+        if (from_const) std::fill(g, g + k, gconst);
+        for (int64_t it = 0; it < std::max<int64_t>(inner, 1); ++it) {
+            std::fill(num.begin(), num.end(), 0.0);
+            for (int64_t q = im.ptr[r]; q < im.ptr[r + 1]; ++q) {
+                const double* fr = F + int64_t(im.idx[q]) * k;
+                double wh = 0.0;
+                for (int64_t j = 0; j < k; ++j) wh += g[j] * fr[j];
+                if (wh < NMF_EPS) wh = NMF_EPS;
+                const double v = im.val[size_t(q)];
+                if (inner == 0) {
+                    if (v > NMF_EPS) tsum += v * std::log(v / wh);
+                    continue;
+                }
+                const double qt = v / wh;
+                for (int64_t j = 0; j < k; ++j) num[j] += qt * fr[j];
+            }
+            if (inner == 0) break;
+            for (int64_t j = 0; j < k; ++j) {
+                double den = (csum[j] + l1) + l2 * g[j];
+                if (den == 0.0) den = NMF_EPS;
+                g[j] = g[j] * (num[j] / den);
+            }
+        }
+    }
+    if (colsum) {
+        std::fill(colsum, colsum + k, 0.0);
+        for (int64_t r = 0; r < im.rows; ++r)
+            for (int64_t j = 0; j < k; ++j) colsum[j] += G[r * k + j];
+    }
+    if (term && inner == 0) *term = tsum;
+}
+
+// A block of doubles where the engine computes: on the device or on the host.
+struct KlBuf {
+    DBuf d;
+    std::vector<double> h;
+    bool device = false;
+    double* p() { return device ? d.f64() : h.data(); }
+    const double* p() const { return device ? static_cast<const double*>(d.p) : h.data(); }
+};
+
+// The two engines of the one driver.  Factors are rows x ks (ks: the kernel's padding on the device, k on the host), a colsum block is
+// ks + 1 doubles: the column sums, then the sweep's term.
+struct KlEngine {
+    petal_ctx& c;
+    const petal_csr& x;
+    const bool device;
+    const int64_t k, ks;
+    KlHostImage him[2];
+    bool have[2] = {false, false};
+
+    KlEngine(petal_ctx& cc, const petal_csr& xx, int64_t kk)
+        : c(cc), x(xx), device(xx.resident && !cc.nmf_fallback), k(kk), ks(device ? nmf_csr_padded_k(kk) : kk) {}
+
+    const KlHostImage& image(int t) {
+        if (!have[t]) { him[t] = kl_host_image(c, x, t); have[t] = true; }
+        return him[t];
+    }
+    KlBuf make(int64_t count) {
+        KlBuf b;
+        b.device = device;
+        if (device) {
+            b.d = DBuf(c.dev, sizeof(double) * size_t(std::max<int64_t>(count, 2)));
+            dev_memset(c.dev, b.d.p, 0, b.d.bytes);
+        } else {
+            b.h.assign(size_t(std::max<int64_t>(count, 2)), 0.0);
+        }
+        return b;
+    }
+    void upload(KlBuf& b, const double* src, int64_t count) {
+        if (device) dev_h2d(c.dev, b.d.p, src, sizeof(double) * size_t(count));
+        else std::copy(src, src + count, b.h.begin());
+    }
+    void download(const KlBuf& b, double* dst, int64_t count) {
+        if (device) { dev_d2h(c.dev, dst, b.d.p, sizeof(double) * size_t(count)); dev_sync(c.dev); }
+        else std::copy(b.h.begin(), b.h.begin() + count, dst);
+    }
+    // colsum_term (nullable) = { colsum(G), the term (inner == 0) } after the sweep
+    void sweep(int t, const KlBuf& F, KlBuf& G, const KlBuf& csum, bool from_const, double gconst, double l1, double l2, int64_t inner,
+               KlBuf* colsum_term) {
+        if (device) {
+            dev_set_tag(c.dev, TAG_POW);
+            const bool ran = op_nmf_kl_sweep_csr(c.dev, x.dtype, x.dev[t], k, ks, F.p(), G.p(), csum.p(), from_const, gconst, l1, l2, inner,
+                                                 colsum_term ? colsum_term->p() : nullptr);
+            dev_set_tag(c.dev, TAG_NONE);
+            if (!ran) device_error("Nmf: the device-op layer refused the Kullback-Leibler sweep");
+            return;
+        }
+        double term = 0.0;
+        kl_host_sweep(image(t), k, F.p(), G.p(), csum.p(), from_const, gconst, l1, l2, inner, colsum_term ? colsum_term->p() : nullptr, &term);
+        if (colsum_term) colsum_term->p()[k] = term;
+    }
+    void colsum(const KlBuf& G, int64_t rows, KlBuf& out) {
+        if (device) {
+            if (!op_nmf_kl_colsum(c.dev, G.p(), rows, ks, nullptr, out.p())) device_error("Nmf: the device-op layer refused the column sums");
+            return;
+        }
+        std::fill(out.h.begin(), out.h.end(), 0.0);
+        for (int64_t r = 0; r < rows; ++r)
+            for (int64_t j = 0; j < k; ++j) out.h[size_t(j)] += G.h[size_t(r * k + j)];
+    }
+    // sum over the stored values of [v > eps] v
+    double vsum() {
+        if (x.nnz == 0) return 0.0;
+        if (device) {
+            DBuf o(c.dev, sizeof(double) * 2);
+            if (!op_nmf_kl_vsum(c.dev, x.dtype, x.dev[0].val, x.nnz, o.f64())) device_error("Nmf: the device-op layer has no masked sum of the stored values");
+            double v = 0.0;
+            dev_d2h(c.dev, &v, o.p, sizeof(double));
+            dev_sync(c.dev);
+            return v;
+        }
+        double s = 0.0;
+        for (double v : image(0).val)
+            if (v > NMF_EPS) s += v;
+        return s;
+    }
+};
+
+// a dense n x k matrix in dt (host or device) as host doubles, row-major
+std::vector<double> kl_to_host(petal_ctx& c, int dt, const petal_matrix& m, int64_t rows, int64_t cols) {
+    const DevMat M = ingest(c, m);
+    nmf_reject(nmf_scan(c, M));
+    DBuf D(c.dev, sizeof(double) * size_t(rows) * cols);
+    op_pad_to_f64(c.dev, dt, D.f64(), rows, cols, M.p, rows, cols, M.ld);
+    std::vector<double> out(size_t(rows) * cols);
+    dev_d2h(c.dev, out.data(), D.p, D.bytes);
+    dev_sync(c.dev);
+    return out;
+}
+
+// W (rows x ks fp64, device or host) rounded once to dtype into the caller's matrix
+void kl_emit_w(petal_ctx& c, KlEngine& e, int dt, KlBuf& W, int64_t rows, const petal_matrix& out) {
+    if (e.device) { nmf_emit_w(c, dt, W.p(), rows, e.k, e.ks, out); return; }
+    DBuf Wd(c.dev, sizeof(double) * size_t(rows) * e.ks);
+    dev_h2d(c.dev, Wd.p, W.p(), Wd.bytes);
+    nmf_emit_w(c, dt, Wd.f64(), rows, e.k, e.ks, out);
+    dev_sync(c.dev);
+}
+
+petal_nmf* nmf_kl_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                          int64_t seed, const petal_matrix* w_out, int64_t* kernel_path) {
+    csr_usable(c, x);
+    if (kernel_path) *kernel_path = 0;
+    const int dt = x.dtype;
+    const int64_t n = x.rows, d = x.cols;
+    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
+    if (k > 64) invalid_input("Nmf: kullback-leibler takes at most 64 components");
+    const NmfScan sx = nmf_csr_scan(c, x);
+    nmf_reject(sx);
+    const Timer timer;
+    dev_reset_timing(c.dev);
+    c.stats = petal_stats{};
+    KlEngine e(c, x, k);
+    const int64_t ks = e.ks;
+    std::vector<double> hw(size_t(n) * ks, 0.0), hht(size_t(d) * ks, 0.0);
+    if (w0) {
+        const std::vector<double> w = kl_to_host(c, dt, *w0, n, k), hh = kl_to_host(c, dt, *h0, k, d);
+        for (int64_t i = 0; i < n; ++i) std::copy(w.begin() + i * k, w.begin() + (i + 1) * k, hw.begin() + i * ks);
+        nmf_transpose_in(hh.data(), d, k, d, ks, hht);
+    } else {
+        // avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first, then H0, both in row-major order (nmf_fit's stream)
+        const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
+        NmfPcg rng(static_cast<uint64_t>(seed));
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t j = 0; j < k; ++j) hw[size_t(i) * ks + j] = std::fabs(avg * rng.standard_normal());
+        for (int64_t i = 0; i < k; ++i)
+            for (int64_t j = 0; j < d; ++j) hht[size_t(j) * ks + i] = std::fabs(avg * rng.standard_normal());
+    }
+    KlBuf W = e.make(n * ks), Ht = e.make(d * ks), cW = e.make(ks + 1), cH = e.make(ks + 1), L = e.make(ks + 1);
+    e.upload(W, hw.data(), n * ks);
+    e.upload(Ht, hht.data(), d * ks);
+    const double xsum = e.vsum();
+    // the loss = sqrt(2 max(0, term + <colsum W, rowsum H> - sum[val > eps] val)): a row sweep with inner = 0 leaves colsum(W) and the term
+    std::vector<double> hl(size_t(ks) + 1), hc(size_t(ks) + 1);
+    const auto read_loss = [&]() {
+        e.sweep(0, Ht, W, cH, false, 0.0, spec.l1_w, spec.l2_w, 0, &L);
+        e.download(L, hl.data(), ks + 1);
+        e.download(cH, hc.data(), ks);
+        double dot = 0.0;
+        for (int64_t j = 0; j < k; ++j) dot += hl[size_t(j)] * hc[size_t(j)];
+        return std::sqrt(2.0 * std::max(0.0, (hl[size_t(ks)] + dot) - xsum));
+    };
+    e.colsum(Ht, d, cH);
+    const double err_init = read_loss();
+    double err_prev = err_init, err = err_init;
+    int64_t n_iter = spec.max_iter;
+    bool read = false;   // `err` is the loss of the iteration just run
+    for (int64_t it = 1; it <= spec.max_iter; ++it) {
+        e.sweep(0, Ht, W, cH, false, 0.0, spec.l1_w, spec.l2_w, 1, &cW);
+        e.sweep(1, W, Ht, cW, false, 0.0, spec.l1_h, spec.l2_h, 1, &cH);
+        read = false;
+        if (spec.tol > 0 && it % 10 == 0) {
+            err = read_loss();
+            read = true;
+            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
+            err_prev = err;
+        }
+    }
+    if (!read) err = read_loss();
+    if (w_out) kl_emit_w(c, e, dt, W, n, *w_out);
+    // the handle is an ordinary petal_nmf: H as kp x dp in the dense entries' padding (H H^T, which this loss never reads, as zeros)
+    const int64_t kp = nmf_padded_k(k), dp = round_up(d, 16);
+    e.download(Ht, hht.data(), d * ks);
+    std::vector<double> hd(size_t(kp) * dp, 0.0);
+    for (int64_t i = 0; i < k; ++i)
+        for (int64_t j = 0; j < d; ++j) hd[size_t(i) * dp + j] = hht[size_t(j) * ks + i];
+    DBuf H(c.dev, sizeof(double) * hd.size()), G(c.dev, sizeof(double) * size_t(kp) * kp);
+    dev_h2d(c.dev, H.p, hd.data(), H.bytes);
+    dev_memset(c.dev, G.p, 0, G.bytes);
+    dev_sync(c.dev);
+    std::unique_ptr<petal_nmf> h(new petal_nmf());
+    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
+    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = e.device ? 1 : 0; h->err = err; h->err_init = err_init; h->loss = NMF_LOSS_KL;
+    finish_stats(c, timer);
+    h->h = H.f64(); H.p = nullptr;
+    h->hht = G.f64(); G.p = nullptr;
+    if (kernel_path) *kernel_path = e.device ? 1 : 0;
+    return h.release();
+}
+
+// transform of a Kullback-Leibler model: W starts at the constant sqrt(mean(Xq) / k) and takes exactly max_iter updates with H fixed
+void nmf_kl_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, const NmfScan& sx, int64_t* kernel_path) {
+    const int64_t m = x.rows;
+    if (m == 0) return;
+    const Timer timer;
+    dev_reset_timing(c.dev);
+    c.stats = petal_stats{};
+    KlEngine e(c, x, h.k);
+    const int64_t ks = e.ks;
+    std::vector<double> hd(size_t(h.kp) * h.dp), hht;
+    dev_d2h(c.dev, hd.data(), h.h, sizeof(double) * hd.size());
+    dev_sync(c.dev);
+    nmf_transpose_in(hd.data(), h.dp, h.k, h.d, ks, hht);
+    KlBuf Ht = e.make(h.d * ks), W = e.make(m * ks), cH = e.make(ks + 1);
+    e.upload(Ht, hht.data(), h.d * ks);
+    e.colsum(Ht, h.d, cH);
+    const double w0 = std::sqrt(sx.sum / (double(m) * double(h.d)) / double(h.k));
+    e.sweep(0, Ht, W, cH, true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr);
+    h.last_kernel = e.device ? 1 : 0;
+    kl_emit_w(c, e, h.dtype, W, m, w_out);
+    finish_stats(c, timer);
+    if (kernel_path) *kernel_path = e.device ? 1 : 0;
+}
+}  // namespace
+
+petal_nmf* nmf_fit_csr_loss(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, int64_t loss, const petal_matrix* w0,
+                            const petal_matrix* h0, int64_t seed, const petal_matrix* w_out, int64_t* kernel_path) {
+    if (kernel_path) *kernel_path = 0;
+    if (loss == NMF_LOSS_FROBENIUS) return nmf_fit_csr(c, x, k, spec, w0, h0, seed, w_out, kernel_path);
+    if (loss != NMF_LOSS_KL) invalid_input("Nmf: unknown loss " + std::to_string(loss) + " (0: frobenius, 1: kullback-leibler)");
+    return nmf_kl_fit_csr(c, x, k, spec, w0, h0, seed, w_out, kernel_path);
+}
+
+void nmf_kl_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k, const double* g_in, const double* f, const NmfSpec& spec,
+                      int64_t inner, double* g_out, double* colsum_out, double* term_out, int64_t* info1) {
+    csr_usable(c, x);
+    if (info1) info1[0] = 0;
+    if (k < 1) invalid_input("nmf_kl_sweep: the number of components should be at least 1");
+    if (inner < 0) invalid_input("negative parameter");
+    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0) || std::isinf(spec.l1_w) || std::isinf(spec.l2_w))
+        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    if (term_out && inner != 0) invalid_input("term_out comes with inner_iters = 0 only");
+    const int t = transposed ? 1 : 0;
+    const int64_t R = transposed ? x.cols : x.rows, C = transposed ? x.rows : x.cols;
+    const double l1 = spec.l1_w, l2 = spec.l2_w;
+    if (!x.resident) {   // the plain host loop of a layer without the kernel: the statement in position order
+        const KlHostImage im = kl_host_image(c, x, t);
+        std::vector<double> csum(static_cast<size_t>(k), 0.0);
+        for (int64_t r = 0; r < C; ++r)
+            for (int64_t j = 0; j < k; ++j) csum[size_t(j)] += f[r * k + j];
+        std::copy(g_in, g_in + R * k, g_out);
+        double term = 0.0;
+        kl_host_sweep(im, k, f, g_out, csum.data(), false, 0.0, l1, l2, inner, colsum_out, &term);
+        if (term_out) *term_out = term;
+        return;
+    }
+    if (k > 64) invalid_input("nmf_kl_sweep: kullback-leibler takes at most 64 components");
+    if (R == 0) { if (colsum_out) std::fill(colsum_out, colsum_out + k, 0.0); if (term_out) *term_out = 0.0; return; }
+    const int64_t ks = nmf_csr_padded_k(k);
+    std::vector<double> hg(size_t(R) * ks, 0.0), hf(size_t(std::max<int64_t>(C, 1)) * ks, 0.0);
+    for (int64_t i = 0; i < R; ++i) std::copy(g_in + i * k, g_in + (i + 1) * k, hg.begin() + i * ks);
+    for (int64_t i = 0; i < C; ++i) std::copy(f + i * k, f + (i + 1) * k, hf.begin() + i * ks);
+    // G is formed inside a guard: one row more, every byte 0xFF beforehand.  The guard row must come back untouched and the padding
+    // columns of G as zeros.
+    DBuf Gd(c.dev, sizeof(double) * size_t(R + 1) * ks), F(c.dev, sizeof(double) * hf.size()), cF(c.dev, sizeof(double) * size_t(ks + 1)),
+        CT(c.dev, sizeof(double) * size_t(ks + 1));
+    dev_memset(c.dev, Gd.p, 0xFF, Gd.bytes);
+    dev_h2d(c.dev, Gd.p, hg.data(), sizeof(double) * hg.size());
+    dev_h2d(c.dev, F.p, hf.data(), F.bytes);
+    if (C == 0) dev_memset(c.dev, cF.p, 0, cF.bytes);
+    else if (!op_nmf_kl_colsum(c.dev, F.f64(), C, ks, nullptr, cF.f64())) device_error("Nmf: the device-op layer refused the column sums");
+    dev_set_tag(c.dev, TAG_POW);
+    const bool ran = op_nmf_kl_sweep_csr(c.dev, x.dtype, x.dev[t], k, ks, F.f64(), Gd.f64(), cF.f64(), false, 0.0, l1, l2, inner, CT.f64());
+    dev_set_tag(c.dev, TAG_NONE);
+    if (!ran) device_error("Nmf: the device-op layer refused the Kullback-Leibler sweep");
+    std::vector<double> back(size_t(R + 1) * ks), hct(size_t(ks) + 1);
+    dev_d2h(c.dev, back.data(), Gd.p, Gd.bytes);
+    dev_d2h(c.dev, hct.data(), CT.p, CT.bytes);
+    dev_sync(c.dev);
+    for (int64_t i = 0; i <= R; ++i)
+        for (int64_t j = 0; j < ks; ++j) {
+            uint64_t bits = 0;
+            std::memcpy(&bits, &back[size_t(i) * ks + j], 8);
+            if (i == R ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_kl_sweep wrote outside the R x k block");
+        }
+    for (int64_t i = 0; i < R; ++i) std::copy(back.begin() + i * ks, back.begin() + i * ks + k, g_out + i * k);
+    if (colsum_out) std::copy(hct.begin(), hct.begin() + k, colsum_out);
+    if (term_out) *term_out = hct[size_t(ks)];
     if (info1) info1[0] = 1;
 }
 

@@ -13,6 +13,7 @@
 #include "../../include/petal_hip_kpca.h"
 #include "../../include/petal_hip_nmf.h"
 #include "../../include/petal_hip_nmf_sparse.h"
+#include "../../include/petal_hip_nmf_kl.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -474,6 +475,34 @@ int petal_nmf_sweep_csr(petal_ctx* ctx, const petal_csr* x, int transposed, int6
         need(spec, "spec");
         need(g_out, "g_out");
         nmf_sweep_csr(*ctx, *x, transposed != 0, k, g_in, f, nmf_spec(*spec), inner_iters, g_out, gram_out, dot_out, info1);
+    });
+}
+
+// ---- include/petal_hip_nmf_kl.h: the Kullback-Leibler loss on a resident CSR matrix ------------------------------------------------
+int petal_nmf_fit_csr_loss(petal_ctx* ctx, const petal_csr* x, int64_t k, const petal_nmf_spec* spec, int64_t loss, const petal_matrix* w0,
+                           const petal_matrix* h0, int64_t seed, petal_nmf** out, const petal_matrix* w_out, int64_t* kernel_path) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(spec, "spec");
+        need(out, "out");
+        *out = nmf_fit_csr_loss(*ctx, *x, k, nmf_spec(*spec), loss, w0, h0, seed, w_out, kernel_path);
+    });
+}
+int petal_nmf_get_loss(const petal_nmf* h, int64_t* loss) {
+    if (!h || !loss) return PETAL_INVALID_INPUT;
+    *loss = h->loss;
+    return PETAL_OK;
+}
+int petal_nmf_kl_sweep_csr(petal_ctx* ctx, const petal_csr* x, int transposed, int64_t k, const double* g_in, const double* f,
+                           const petal_nmf_spec* spec, int64_t inner_iters, double* g_out, double* colsum_out, double* term_out, int64_t* info1) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(g_in, "g_in");
+        need(f, "f");
+        need(spec, "spec");
+        need(g_out, "g_out");
+        nmf_kl_sweep_csr(*ctx, *x, transposed != 0, k, g_in, f, nmf_spec(*spec), inner_iters, g_out, colsum_out, term_out, info1);
     });
 }
 

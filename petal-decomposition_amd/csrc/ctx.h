@@ -87,9 +87,10 @@ struct petal_nmf {
     int dtype = 0;
     double l1_w = 0, l2_w = 0;
     int64_t fit_kernel = 0, last_kernel = -1;
+    int64_t loss = 0;                    // PETAL_NMF_LOSS_FROBENIUS / PETAL_NMF_LOSS_KL (include/petal_hip_nmf_kl.h)
     double err = 0, err_init = 0;
     double* h = nullptr;                 // device fp64, kp x dp (ld dp): H, zero in the padding
-    double* hht = nullptr;               // device fp64, kp x kp: H H^T
+    double* hht = nullptr;               // device fp64, kp x kp: H H^T (zeros in a Kullback-Leibler model, which never reads it)
 };
 
 namespace petal {
@@ -203,6 +204,11 @@ petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpe
 void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, int64_t* kernel_path);
 void nmf_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k, const double* g_in, const double* f, const NmfSpec& spec,
                    int64_t inner, double* g_out, double* gram_out, double* dot_out, int64_t* info1);
+// include/petal_hip_nmf_kl.h: the Kullback-Leibler loss on a sparse matrix
+petal_nmf* nmf_fit_csr_loss(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, int64_t loss, const petal_matrix* w0,
+                            const petal_matrix* h0, int64_t seed, const petal_matrix* w_out, int64_t* kernel_path);
+void nmf_kl_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k, const double* g_in, const double* f, const NmfSpec& spec,
+                      int64_t inner, double* g_out, double* colsum_out, double* term_out, int64_t* info1);
 void nmf_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* h, const NmfSpec& spec, int64_t inner, double* w_out,
               double* a_out, double* b_out, int64_t* info1);
 // include/petal_hip_ipca.h: IncrementalPca

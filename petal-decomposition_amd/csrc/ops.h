@@ -267,6 +267,18 @@ bool op_nmf_sweep_csr(Dev*, int dtype, const CsrImage& img, int64_t k, int64_t k
 bool op_nmf_gram(Dev*, const double* G, int64_t rows, int64_t kp, const double* dots, double* gram_dot);
 // out4 (DEVICE) = { sum v, sum v^2, min(v, 0), 1 if a NaN or an infinity was seen else 0 } over nnz stored values in dtype.
 bool op_nmf_valscan(Dev*, int dtype, const void* val, int64_t nnz, double* out4);
+// Nmf with the Kullback-Leibler loss on sparse CSR data (include/petal_hip_nmf_kl.h).  One sweep of an image: G (R x kp, DEVICE fp64, in
+// place; from_const: starts as gconst in its k leading columns), F (C x kp), csum = colsum(F) (kp), all ZERO in the padding; `inner` times
+//     wh_t = <g_r, F[idx_t, :]>, wh_t < 2^-23 -> 2^-23, num = sum_t (val_t / wh_t) F[idx_t, :] in the items' fixed order,
+//     den = (csum + l1) + l2 g_r,  den[den == 0] = 2^-23,  g_r <- g_r o (num / den)
+// colsum_term (nullable, DEVICE, kp + 1 doubles): colsum(G) with the G just written, then 0.  inner == 0 (needs colsum_term, no
+// from_const): G is left alone and colsum_term[kp] = sum_r sum_t [val_t > 2^-23] val_t log(val_t / wh_t).  No atomics.
+bool op_nmf_kl_sweep_csr(Dev*, int dtype, const CsrImage& img, int64_t k, int64_t kp, const double* F, double* G, const double* csum,
+                         bool from_const, double gconst, double l1, double l2, int64_t inner, double* colsum_term);
+// colsum_term (DEVICE, kp + 1 doubles) = { colsum(G), sum of terms (nullable: 0) } over G (rows x kp fp64), a fixed order.
+bool op_nmf_kl_colsum(Dev*, const double* G, int64_t rows, int64_t kp, const double* terms, double* colsum_term);
+// out1 (DEVICE) = sum over nnz stored values in dtype of [v > 2^-23] v, a fixed order.
+bool op_nmf_kl_vsum(Dev*, int dtype, const void* val, int64_t nnz, double* out1);
 // out (img.rows x cols in dtype, ldo; DEVICE) = the dense image: zeros, then every stored entry added in position order.
 bool op_csr_densify(Dev*, int dtype, const CsrImage& img, void* out, int64_t cols, int64_t ldo);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns

@@ -7,6 +7,7 @@ mod ffi_ipca;
 mod ffi_kpca;
 mod ffi_nmf;
 mod ffi_nmf_sparse;
+mod ffi_nmf_kl;
 mod ffi_score;
 mod ffi_segments;
 mod ffi_sparse;
@@ -21,7 +22,7 @@ pub use ffi_kpca::PETAL_OPT_KPCA_FALLBACK;
 pub use ffi_nmf::PETAL_OPT_NMF_FALLBACK;
 pub use ffi_wide::{PETAL_OPT_PCA_DUAL, PETAL_OPT_PCA_DUAL_FALLBACK};
 pub use kpca::{Kernel, KernelPca, KernelPcaInfo};
-pub use nmf::{Nmf, NmfInfo, NmfParams};
+pub use nmf::{Nmf, NmfInfo, NmfLoss, NmfParams};
 pub use pca::{CsrMatrix, IncrementalPca, Pca, PcaBuilder, PcaRoute, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
 
 use ndarray::{ArrayBase, Data, Ix2};

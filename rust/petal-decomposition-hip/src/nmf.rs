@@ -2,13 +2,33 @@
 //! beta_loss="frobenius")`.  An iteration is one fused pass over the data; `transform` is one pass whatever `max_iter` is.  Everything
 //! is float64 inside; outputs are rounded once to `A`.
 use crate::ffi_nmf::{self, PetalNmf, PetalNmfSpec};
+use crate::ffi_nmf_kl;
 use crate::ffi_nmf_sparse;
 use crate::pca::CsrMatrix;
 use crate::{view, with_ctx, DecompositionError, HipScalar};
 use ndarray::{Array2, ArrayBase, Data, Ix2};
 use std::marker::PhantomData;
 
-/// The parameters of a fit; `alpha_h: None` means the same as `alpha_w` (scikit-learn's "same").
+/// The loss of a fit on sparse CSR input (include/petal_hip_nmf_kl.h; source only, unverified like the rest of this crate).
+/// `KullbackLeibler` is scikit-learn's `beta_loss="kullback-leibler"`; dense input is refused under it.
+#[derive(Debug, Clone, Copy, PartialEq, Eq, Default)]
+pub enum NmfLoss {
+    #[default]
+    Frobenius,
+    KullbackLeibler,
+}
+
+impl NmfLoss {
+    fn code(self) -> i64 {
+        match self {
+            NmfLoss::Frobenius => ffi_nmf_kl::PETAL_NMF_LOSS_FROBENIUS,
+            NmfLoss::KullbackLeibler => ffi_nmf_kl::PETAL_NMF_LOSS_KL,
+        }
+    }
+}
+
+/// The parameters of a fit; `alpha_h: None` means the same as `alpha_w` (scikit-learn's "same").  `loss` is read by `fit_csr` and its
+/// siblings; `transform_csr` follows the loss the model was fitted with.
 #[derive(Debug, Clone, Copy, PartialEq)]
 pub struct NmfParams {
     pub max_iter: usize,
@@ -17,10 +37,11 @@ pub struct NmfParams {
     pub alpha_w: f64,
     pub alpha_h: Option<f64>,
     pub l1_ratio: f64,
+    pub loss: NmfLoss,
 }
 
 impl Default for NmfParams {
-    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0 } }
+    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0, loss: NmfLoss::Frobenius } }
 }
 
 /// { n, d, k, iterations run, k_nmf_pass ran in the fit, k_nmf_pass ran in the last transform (-1 before the first) }
@@ -119,7 +140,14 @@ impl<A: HipScalar> Nmf<A> {
         self.kernel_path = path;
         Ok(w)
     }
-    /// 1: the sweep kernel ran in the last sparse call; 0: the call densified.
+    /// The loss the fitted model remembers.
+    pub fn model_loss(&self) -> Result<NmfLoss, DecompositionError> {
+        let raw = self.handle()?;
+        let mut v = 0i64;
+        with_ctx(|_| unsafe { ffi_nmf_kl::petal_nmf_get_loss(raw, &mut v) }, || ())?;
+        Ok(if v == ffi_nmf_kl::PETAL_NMF_LOSS_KL { NmfLoss::KullbackLeibler } else { NmfLoss::Frobenius })
+    }
+    /// 1: the sweep kernel ran in the last sparse call; 0: the call densified (Frobenius) or ran the host loop (Kullback-Leibler).
     pub fn kernel_path(&self) -> i64 { self.kernel_path }
 
     fn spec(&self, n: f64, d: f64) -> PetalNmfSpec {
@@ -134,12 +162,16 @@ impl<A: HipScalar> Nmf<A> {
         let spec = self.spec(input.nrows() as f64, input.ncols() as f64);
         let mut raw = std::ptr::null_mut();
         let mut path = 0i64;
-        let (k, seed) = (self.k as i64, self.params.seed as i64);
+        let (k, seed, loss) = (self.k as i64, self.params.seed as i64, self.params.loss);
         with_ctx(
             |ctx| unsafe {
-                ffi_nmf_sparse::petal_nmf_fit_csr(ctx, input.raw(), k, &spec, iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _),
-                                                  iv.as_ref().map_or(std::ptr::null(), |m| &m.1 as *const _), seed, &mut raw,
-                                                  wv.as_ref().map_or(std::ptr::null(), |m| m as *const _), &mut path)
+                let (w0, h0) = (iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _), iv.as_ref().map_or(std::ptr::null(), |m| &m.1 as *const _));
+                let wo = wv.as_ref().map_or(std::ptr::null(), |m| m as *const _);
+                if loss == NmfLoss::Frobenius {
+                    ffi_nmf_sparse::petal_nmf_fit_csr(ctx, input.raw(), k, &spec, w0, h0, seed, &mut raw, wo, &mut path)
+                } else {
+                    ffi_nmf_kl::petal_nmf_fit_csr_loss(ctx, input.raw(), k, &spec, loss.code(), w0, h0, seed, &mut raw, wo, &mut path)
+                }
             },
             || (),
         )?;
@@ -156,6 +188,9 @@ impl<A: HipScalar> Nmf<A> {
     }
     fn inner_fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, init: Option<(&Array2<A>, &Array2<A>)>, w: Option<&mut Array2<A>>)
         -> Result<(), DecompositionError> {
+        if self.params.loss == NmfLoss::KullbackLeibler {
+            return Err(DecompositionError::InvalidInput("Nmf: the kullback-leibler loss takes a CsrMatrix".into()));
+        }
         let x = view(input);
         let wv = w.map(|w| view(&w.view_mut()));
         let iv = init.map(|(w0, h0)| (view(w0), view(h0)));
