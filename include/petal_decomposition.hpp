@@ -30,6 +30,7 @@
 #include "petal_hip_nmf.h"
 #include "petal_hip_nmf_sparse.h"
 #include "petal_hip_nmf_kl.h"
+#include "petal_hip_nmf_kl_dense.h"
 
 namespace petal_decomposition {
 
@@ -572,6 +573,11 @@ class CsrMatrix;   // (declared below: Nmf takes it in place of an Array2, petal
 // extension beyond the crate (petal_hip_nmf_kl.h): the loss of a fit on sparse CSR input.  KullbackLeibler is scikit-learn's
 // beta_loss="kullback-leibler"; it is taken by the CsrMatrix overloads only -- the dense overloads throw InvalidInput under it.
 enum class NmfLoss : int64_t { Frobenius = PETAL_NMF_LOSS_FROBENIUS, KullbackLeibler = PETAL_NMF_LOSS_KL };
+// extension beyond the crate (petal_hip_nmf_kl_dense.h): what the dense overloads do under the Kullback-Leibler loss.  Compress (the
+// default) keeps them throwing "takes a CsrMatrix"; Fused sends the Array2 to the fused dense pass k_nmf_kl_pass (petal_nmf_fit_loss,
+// petal_nmf_transform_loss; the composed path outside the kernel's envelope, no cap on the components).  Under the Frobenius loss it
+// changes nothing.
+enum class NmfDensePath : int { Compress = 0, Fused = 1 };
 
 template <class A>
 class Nmf {
@@ -584,10 +590,12 @@ class Nmf {
     Nmf& operator=(const Nmf&) = delete;
     Nmf(Nmf&& o) noexcept
         : k_(o.k_), max_iter_(o.max_iter_), tol_(o.tol_), seed_(o.seed_), alpha_w_(o.alpha_w_), alpha_h_(o.alpha_h_), l1_ratio_(o.l1_ratio_),
-          ctx_(o.ctx_), h_(o.h_), kernel_path_(o.kernel_path_), loss_(o.loss_) { o.h_ = nullptr; }
+          ctx_(o.ctx_), h_(o.h_), kernel_path_(o.kernel_path_), loss_(o.loss_), dense_path_(o.dense_path_) { o.h_ = nullptr; }
     ~Nmf() { petal_nmf_destroy(h_); }
     Nmf& loss(NmfLoss l) { loss_ = l; return *this; }   // the loss of the NEXT fit on a CsrMatrix (petal_hip_nmf_kl.h)
     NmfLoss loss() const { return loss_; }
+    Nmf& dense_path(NmfDensePath p) { dense_path_ = p; return *this; }   // the route of the NEXT dense call under the Kullback-Leibler loss
+    NmfDensePath dense_path() const { return dense_path_; }
     // the loss the fitted model remembers
     NmfLoss model_loss() const {
         int64_t v = 0;
@@ -607,10 +615,15 @@ class Nmf {
         return w;
     }
     Array2<A> transform(const Array2<A>& input) {
-        no_dense_kl();
+        if (dense_path_ != NmfDensePath::Fused) no_dense_kl();
         Array2<A> w(input.nrows(), k_);
         petal_matrix mx = input.view(), mw = w.view();
-        context().check(petal_nmf_transform(context().get(), handle(), &mx, &mw));
+        if (dense_path_ == NmfDensePath::Fused) {   // dispatches on the model's loss; a Frobenius model: petal_nmf_transform's bytes
+            context().check(petal_nmf_transform_loss(context().get(), handle(), &mx, &mw));
+            if (model_loss() == NmfLoss::KullbackLeibler && input.nrows() > 0) kernel_path_ = info().transform_kernel;
+        } else {
+            context().check(petal_nmf_transform(context().get(), handle(), &mx, &mw));
+        }
         return w;
     }
     Array2<A> inverse_transform(const Array2<A>& w) {
@@ -639,7 +652,8 @@ class Nmf {
         context().check(petal_nmf_transform_csr(context().get(), handle(), input.get(), &mw, &kernel_path_));
         return w;
     }
-    int64_t kernel_path() const { return kernel_path_; }   // the last sparse call: 1 the sweep kernel, 0 the densifying fall-back
+    // the last sparse call: 1 the sweep kernel, 0 the densifying fall-back; the last fused dense Kullback-Leibler call: 1 k_nmf_kl_pass, 0 the composed path
+    int64_t kernel_path() const { return kernel_path_; }
     int64_t n_components() const { return k_; }
     // H, k x d, float64
     Array2<double> components() const {
@@ -677,7 +691,8 @@ class Nmf {
                                      "Nmf: the kullback-leibler loss takes a CsrMatrix (compress the dense rows to the CSR of their non-zero entries)");
     }
     void inner_fit(const Array2<A>& input, const Array2<A>* w0, const Array2<A>* h0, Array2<A>* w) {
-        no_dense_kl();
+        const bool fused = loss_ == NmfLoss::KullbackLeibler && dense_path_ == NmfDensePath::Fused;
+        if (!fused) no_dense_kl();
         petal_matrix mx = input.view(), m0{}, m1{}, mw{};
         if (w0) { m0 = w0->view(); m1 = h0->view(); }
         if (w) mw = w->view();
@@ -687,10 +702,15 @@ class Nmf {
         spec.l1_w = d * alpha_w_ * l1_ratio_; spec.l2_w = d * alpha_w_ * (1.0 - l1_ratio_);
         spec.l1_h = n * alpha_h_ * l1_ratio_; spec.l2_h = n * alpha_h_ * (1.0 - l1_ratio_);
         petal_nmf* h = nullptr;
-        context().check(petal_nmf_fit(context().get(), &mx, k_, &spec, w0 ? &m0 : nullptr, w0 ? &m1 : nullptr, int64_t(seed_), &h,
-                                      w ? &mw : nullptr));
+        if (fused)
+            context().check(petal_nmf_fit_loss(context().get(), &mx, k_, &spec, static_cast<int64_t>(loss_), w0 ? &m0 : nullptr,
+                                               w0 ? &m1 : nullptr, int64_t(seed_), &h, w ? &mw : nullptr));
+        else
+            context().check(petal_nmf_fit(context().get(), &mx, k_, &spec, w0 ? &m0 : nullptr, w0 ? &m1 : nullptr, int64_t(seed_), &h,
+                                          w ? &mw : nullptr));
         petal_nmf_destroy(h_);
         h_ = h;
+        if (fused) kernel_path_ = info().fit_kernel ? 1 : 0;
     }
     void inner_fit_sparse(const CsrMatrix<A>& input, const Array2<A>* w0, const Array2<A>* h0, Array2<A>* w) {
         petal_matrix m0{}, m1{}, mw{};
@@ -719,6 +739,7 @@ class Nmf {
     petal_nmf* h_ = nullptr;
     int64_t kernel_path_ = 0;
     NmfLoss loss_ = NmfLoss::Frobenius;
+    NmfDensePath dense_path_ = NmfDensePath::Compress;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

@@ -44,7 +44,8 @@
  * Measured: see README.md (Nmf with the Kullback-Leibler loss) and EXPERIMENTS.md; every figure not measured on the device is marked
  * "unmeasured".
  *
- * Not in this version: sharded fits, k > 64, a fused dense Kullback-Leibler kernel (dense input is compressed on the host), other beta,
+ * Not in this version: sharded fits, k > 64, a fused dense Kullback-Leibler kernel (dense input is compressed on the host; the dense
+ * kernel now lives beside this header, in petal_hip_nmf_kl_dense.h, with entries of its own), other beta,
  * a loss term fused into the column sweep (a check costs one more sweep), one-launch multi-update transform on images with split rows
  * (such an image takes one launch pair per update), a tolerance stop in transform, device-resident CSR arrays.
  */

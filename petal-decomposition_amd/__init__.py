@@ -241,6 +241,12 @@ ABI_NMF_KL = [
     ("petal_nmf_get_loss", C.c_int, [_P, _L]),
     ("petal_nmf_kl_sweep_csr", C.c_int, [_P, _P, C.c_int, C.c_int64, _D, _D, _NS, C.c_int64, _D, _D, _D, _L]),
 ]
+# every symbol include/petal_hip_nmf_kl_dense.h declares (Nmf with the Kullback-Leibler loss on dense data and its fused pass by itself)
+ABI_NMF_KL_DENSE = [
+    ("petal_nmf_fit_loss", C.c_int, [_P, _M, C.c_int64, _NS, C.c_int64, _M, _M, C.c_int64, C.POINTER(C.c_void_p), _M]),
+    ("petal_nmf_transform_loss", C.c_int, [_P, _P, _M, _M]),
+    ("petal_nmf_kl_pass", C.c_int, [_P, _M, C.c_int64, _D, _D, _NS, C.c_int64, _D, _D, _D, _D, _L]),
+]
 
 
 def _preload_torch_hip_runtime():
@@ -259,7 +265,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h, petal_hip_nmf_sparse.h, petal_hip_nmf_kl.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h, petal_hip_nmf_sparse.h, petal_hip_nmf_kl.h, petal_hip_nmf_kl_dense.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -268,7 +274,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF + ABI_NMF_SPARSE + ABI_NMF_KL:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF + ABI_NMF_SPARSE + ABI_NMF_KL + ABI_NMF_KL_DENSE:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -873,6 +879,34 @@ def nmf_kl_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0
     return (out, {"kernel": int(info[0])}) if want_info else out
 
 
+def nmf_kl_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, want_a=True, want_term: Optional[bool] = None,
+                ctx: Optional["Context"] = None, want_info: bool = False):
+    """Test aid (``petal_nmf_kl_pass``, include/petal_hip_nmf_kl_dense.h): the fused pass of a dense Kullback-Leibler ``Nmf`` iteration
+    by itself, in float64.  ``x`` (n x d): numpy or ``torch.cuda``, any strides; ``w`` (n x k), ``h`` (k x d): float64.
+    ``inner_iters`` times WH = max(W h, 2^-23), den = rowsum(h) + l1_w + l2_w W, den[den == 0] = 2^-23,
+    W <- W o (((x / WH) h^T) / den).  Returns ``(w_new, a, colsum)`` with a = w_new^T (x / max(w_new h, 2^-23)) and colsum = the column
+    sums of w_new (``want_a=False``: ``w_new`` alone); with ``inner_iters=0`` (``want_term`` defaults to that) ``(w, a, colsum, term)``
+    with term = sum [x > 2^-23] x log(x / WH).  ``want_info``: also ``{"kernel": k_nmf_kl_pass ran}``."""
+    keep = []
+    mx = describe(x, keep)
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+    h = np.ascontiguousarray(np.asarray(h, dtype=np.float64))
+    if w.ndim != 2 or h.ndim != 2 or w.shape[0] != mx.rows or h.shape != (w.shape[1], mx.cols):
+        raise InvalidInput(f"w should be {mx.rows} x k and h k x {mx.cols}")
+    k = w.shape[1]
+    if want_term is None:
+        want_term = int(inner_iters) == 0
+    spec = _nmf_spec(1, 0.0, l1_w, l2_w)
+    wo, a, colsum, term = np.zeros((mx.rows, k)), np.zeros((k, mx.cols)), np.zeros(k), np.zeros(1)
+    info = (C.c_int64 * 1)()
+    ctx.check(ctx.lib.petal_nmf_kl_pass(ctx._h, C.byref(mx), k, w.ctypes.data_as(_D), h.ctypes.data_as(_D), C.byref(spec), int(inner_iters),
+                                        wo.ctypes.data_as(_D), a.ctypes.data_as(_D) if want_a else None,
+                                        colsum.ctypes.data_as(_D) if want_a else None, term.ctypes.data_as(_D) if want_term else None, info))
+    out = ((wo, a, colsum, float(term[0])) if want_term else (wo, a, colsum)) if want_a or want_term else wo
+    return (out, {"kernel": int(info[0])}) if want_info else out
+
+
 def _like_input(x, w):
     """w (a numpy array computed on the host) where x lives: a torch tensor on x's device for a torch x"""
     if _is_torch(x):
@@ -919,12 +953,23 @@ class Nmf:
     ``beta_loss="kullback-leibler"`` (or 1; include/petal_hip_nmf_kl.h) fits the generalised Kullback-Leibler divergence instead of the
     Frobenius loss ("frobenius" or 2, the default).  It runs on sparse input at the stored entries alone: a dense array is compressed
     here, on the host, to the CSR of its non-zero entries (a ``torch.cuda`` tensor is copied to the host for that) and takes the same
-    path; at most 64 components; ``transform`` then costs ``max_iter`` sweeps.  ``beta_loss`` is readable."""
+    path; at most 64 components; ``transform`` then costs ``max_iter`` sweeps.  ``beta_loss`` is readable.
+
+    ``dense_path`` chooses the route of DENSE input under that loss (include/petal_hip_nmf_kl_dense.h).  ``"compress"``, the default,
+    is the route above; ``"fused"`` sends the array as it is to the fused dense pass k_nmf_kl_pass: a ``torch.cuda`` tensor goes
+    zero-copy and the results stay on its device, ``transform`` reads its input once whatever ``max_iter`` is, there is no cap on the
+    components (outside the kernel's envelope the library's composed path runs), and ``kernel_path`` says whether the kernel ran (1)
+    or the composed path (0).  The default stays ``"compress"`` only because existing callers are pinned to its bytes; a measured
+    crossover may move it in a later change.  Under the Frobenius loss the keyword is read and changes nothing."""
 
     def __init__(self, n_components: int, max_iter: int = 200, tol: float = 1e-4, init: str = "random", seed: int = 0,
-                 alpha_W: float = 0.0, alpha_H="same", l1_ratio: float = 0.0, ctx: Optional[Context] = None, beta_loss="frobenius"):
+                 alpha_W: float = 0.0, alpha_H="same", l1_ratio: float = 0.0, ctx: Optional[Context] = None, beta_loss="frobenius",
+                 dense_path: str = "compress"):
         if init not in ("random", "custom"):
             raise InvalidInput(f"unknown init {init!r} (random or custom)")
+        if dense_path not in ("compress", "fused"):
+            raise InvalidInput(f"unknown dense_path {dense_path!r} (compress or fused)")
+        self.dense_path = dense_path
         self._loss = _beta_loss_code(beta_loss)
         self.beta_loss = "frobenius" if self._loss == NMF_LOSS_FROBENIUS else "kullback-leibler"
         self._k = int(n_components)
@@ -1019,7 +1064,7 @@ class Nmf:
     def _inner_fit(self, x, W, H, want_w: bool):
         if _is_sparse(x):
             return self._inner_fit_sparse(x, W, H, want_w)
-        if self._loss == NMF_LOSS_KL:   # dense input under this loss: the CSR of its non-zero entries, the same path
+        if self._loss == NMF_LOSS_KL and self.dense_path == "compress":   # the CSR of the non-zero entries, the same path
             w = self._inner_fit_sparse(_DenseAsCsr(x), W, H, want_w)
             return _like_input(x, w) if want_w else None
         keep = []
@@ -1032,12 +1077,17 @@ class Nmf:
             w = _alloc_like(x, mx.rows, self._k, mx.dtype)
             mo = describe(w, keep)
         h = C.c_void_p()
-        ctx.check(ctx.lib.petal_nmf_fit(ctx._h, C.byref(mx), self._k, C.byref(spec), C.byref(mw) if mw is not None else None,
-                                        C.byref(mh) if mh is not None else None, C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h),
-                                        C.byref(mo) if mo is not None else None))
+        args = (C.byref(mw) if mw is not None else None, C.byref(mh) if mh is not None else None,
+                C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h), C.byref(mo) if mo is not None else None)
+        if self._loss == NMF_LOSS_FROBENIUS:
+            ctx.check(ctx.lib.petal_nmf_fit(ctx._h, C.byref(mx), self._k, C.byref(spec), *args))
+        else:   # dense_path="fused" (include/petal_hip_nmf_kl_dense.h)
+            ctx.check(ctx.lib.petal_nmf_fit_loss(ctx._h, C.byref(mx), self._k, C.byref(spec), self._loss, *args))
         self.close()
         self._h = h
         ctx._nmf.add(self)
+        if self._loss != NMF_LOSS_FROBENIUS:
+            self.kernel_path = self.info()["fit_kernel"]
         return w
 
     def fit(self, x, W=None, H=None):
@@ -1052,7 +1102,7 @@ class Nmf:
         through the sparse sweep and sets ``kernel_path``."""
         self._handle()
         dense_kl = not _is_sparse(x) and self._model_loss() == NMF_LOSS_KL
-        if dense_kl:
+        if dense_kl and self.dense_path == "compress":
             return _like_input(x, self.transform(_DenseAsCsr(x)))
         if _is_sparse(x):
             sx, mine = self._sparse(x)
@@ -1073,7 +1123,11 @@ class Nmf:
         ctx = self._ctx()
         w = _alloc_like(x, mx.rows, self._k, mx.dtype)
         mo = describe(w, keep)
-        ctx.check(ctx.lib.petal_nmf_transform(ctx._h, self._handle(), C.byref(mx), C.byref(mo)))
+        if dense_kl:   # dense_path="fused" (include/petal_hip_nmf_kl_dense.h)
+            ctx.check(ctx.lib.petal_nmf_transform_loss(ctx._h, self._handle(), C.byref(mx), C.byref(mo)))
+            self.kernel_path = self.info()["transform_kernel"] if mx.rows else self.kernel_path
+        else:
+            ctx.check(ctx.lib.petal_nmf_transform(ctx._h, self._handle(), C.byref(mx), C.byref(mo)))
         return w
 
     def inverse_transform(self, w):

@@ -1774,6 +1774,29 @@ void nmf_emit_w(petal_ctx& c, int dt, const double* W, int64_t n, int64_t k, int
     op_cvt_from_f64(c.dev, dt, wt.p, W, n * kp);
     emit(c, dt, wt.p, n, k, kp, out);
 }
+// the start of a dense fit: W (n x kp) and H (kp x dp), zero in the padding, from w0 / h0 or drawn
+void nmf_init_factors(petal_ctx& c, int dt, int64_t n, int64_t d, int64_t k, int64_t kp, int64_t dp, const NmfScan& sx, const petal_matrix* w0,
+                      const petal_matrix* h0, int64_t seed, DBuf& W, DBuf& H) {
+    if (w0) {
+        const DevMat W0 = ingest(c, *w0), H0 = ingest(c, *h0);
+        nmf_reject(nmf_scan(c, W0));
+        nmf_reject(nmf_scan(c, H0));
+        op_pad_to_f64(c.dev, dt, W.f64(), n, kp, W0.p, n, k, W0.ld);
+        op_pad_to_f64(c.dev, dt, H.f64(), kp, dp, H0.p, k, d, H0.ld);
+        dev_sync(c.dev);   // (W0 / H0 go back to the pool behind the two kernels)
+    } else {
+        // avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first, then H0, both in row-major order
+        const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
+        NmfPcg rng(static_cast<uint64_t>(seed));
+        std::vector<double> hw(size_t(n) * kp, 0.0), hh(size_t(kp) * dp, 0.0);
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t j = 0; j < k; ++j) hw[size_t(i) * kp + j] = std::fabs(avg * rng.standard_normal());
+        for (int64_t i = 0; i < k; ++i)
+            for (int64_t j = 0; j < d; ++j) hh[size_t(i) * dp + j] = std::fabs(avg * rng.standard_normal());
+        dev_h2d(c.dev, W.p, hw.data(), W.bytes);
+        dev_h2d(c.dev, H.p, hh.data(), H.bytes);
+    }
+}
 }  // namespace
 
 void nmf_destroy(petal_nmf* h) {
@@ -1796,25 +1819,7 @@ petal_nmf* nmf_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec
     const int64_t dp = X.dp, kp = nmf_padded_k(k);
     DBuf W(c.dev, sizeof(double) * size_t(n) * kp), H(c.dev, sizeof(double) * size_t(kp) * dp), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
     DBuf A(c.dev, sizeof(double) * size_t(kp) * dp), B(c.dev, sizeof(double) * size_t(kp) * kp), dots(c.dev, sizeof(double) * 2);
-    if (w0) {
-        const DevMat W0 = ingest(c, *w0), H0 = ingest(c, *h0);
-        nmf_reject(nmf_scan(c, W0));
-        nmf_reject(nmf_scan(c, H0));
-        op_pad_to_f64(c.dev, dt, W.f64(), n, kp, W0.p, n, k, W0.ld);
-        op_pad_to_f64(c.dev, dt, H.f64(), kp, dp, H0.p, k, d, H0.ld);
-        dev_sync(c.dev);   // (W0 / H0 go back to the pool behind the two kernels)
-    } else {
-        // avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first, then H0, both in row-major order
-        const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
-        NmfPcg rng(static_cast<uint64_t>(seed));
-        std::vector<double> hw(size_t(n) * kp, 0.0), hh(size_t(kp) * dp, 0.0);
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t j = 0; j < k; ++j) hw[size_t(i) * kp + j] = std::fabs(avg * rng.standard_normal());
-        for (int64_t i = 0; i < k; ++i)
-            for (int64_t j = 0; j < d; ++j) hh[size_t(i) * dp + j] = std::fabs(avg * rng.standard_normal());
-        dev_h2d(c.dev, W.p, hw.data(), W.bytes);
-        dev_h2d(c.dev, H.p, hh.data(), H.bytes);
-    }
+    nmf_init_factors(c, dt, n, d, k, kp, dp, sx, w0, h0, seed, W, H);
     op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
     // the loss at the start: A = W^T X and B = W^T W from a pass that leaves W alone
     bool kernel = nmf_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 0, A.f64(), B.f64());
@@ -4241,6 +4246,273 @@ void nmf_kl_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t
     if (colsum_out) std::copy(hct.begin(), hct.begin() + k, colsum_out);
     if (term_out) *term_out = hct[size_t(ks)];
     if (info1) info1[0] = 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Nmf with the generalised Kullback-Leibler loss on DENSE data (include/petal_hip_nmf_kl_dense.h; DESIGN.md sections 4 and 7): the
+// statement of the CSR section above on every entry of X.  An iteration is ONE fused pass over X (k_nmf_kl_pass through op_nmf_kl_pass:
+// the W rule, then A = W^T (X / (W H)) and colsum(W) with the new W) and the H side on k x d operands (op_nmf_kl_hrule,
+// op_nmf_kl_rowsum).  The layouts are the Frobenius section's: W n x kp, H and A kp x dp, fp64, zero in the padding.  A device-op layer
+// without the kernels (the host simulation), a shape outside their envelope (k > 64 included: no cap here) and PETAL_OPT_NMF_FALLBACK
+// build the same statements from op_cvt_to_f64, op_dgemm and element-wise steps on the host, X in row blocks of bounded size.
+__attribute__((weak)) bool op_nmf_kl_pass(Dev*, int, const void*, int64_t, int64_t, int64_t, const double*, const double*, int64_t, int64_t, double*,
+                                          bool, double, double, double, int64_t, double*, double*) {
+    return false;
+}
+__attribute__((weak)) bool op_nmf_kl_hrule(Dev*, int64_t, int64_t, const double*, const double*, double*, double, double) { return false; }
+__attribute__((weak)) bool op_nmf_kl_rowsum(Dev*, int64_t, int64_t, const double*, double*) { return false; }
+
+namespace {
+// The pass (ops.h, op_nmf_kl_pass): the kernel where the layer has it, else the same statement in row blocks.  rsum: DEVICE, kp doubles;
+// A (kp x dp) and cts (kp + 2: colsum(W), term, sum x) both or neither, DEVICE.  Returns "k_nmf_kl_pass ran".
+bool nmf_kl_pass_into(petal_ctx& c, const DevMat& X, const double* H, const double* rsum, int64_t k, int64_t kp, double* W, bool from_const,
+                      double wconst, double l1, double l2, int64_t inner, double* A, double* cts) {
+    const int64_t n = X.n, dp = X.dp, ld = X.ld;
+    if (!c.nmf_fallback) {
+        // (the one launch of an iteration under TAG_POW: with profiling on, stats.pow_ms is k_nmf_kl_pass's own time)
+        dev_set_tag(c.dev, TAG_POW);
+        const bool ran = op_nmf_kl_pass(c.dev, X.dtype, X.p, n, dp, ld, H, rsum, k, kp, W, from_const, wconst, l1, l2, inner, A, cts);
+        dev_set_tag(c.dev, TAG_NONE);
+        if (ran) return true;
+    }
+    const int64_t Bk = std::max<int64_t>(1, std::min(n, NMF_FALLBACK_BLOCK / ld));
+    const size_t esz = dtype_size(X.dtype);
+    DBuf Xb(c.dev, sizeof(double) * size_t((Bk - 1) * ld + dp)), Q(c.dev, sizeof(double) * size_t(Bk) * dp), Z(c.dev, sizeof(double) * size_t(Bk) * kp);
+    std::vector<double> hx(size_t((Bk - 1) * ld + dp)), hq(size_t(Bk) * dp), hz(size_t(Bk) * kp), hw(size_t(Bk) * kp), hr(static_cast<size_t>(kp)),
+        hc(size_t(kp) + 2, 0.0);
+    dev_d2h(c.dev, hr.data(), rsum, sizeof(double) * hr.size());
+    if (A) dev_memset(c.dev, A, 0, sizeof(double) * size_t(kp) * dp);
+    // Q (device) = X / max(W H, eps) on the block; with_term: the loss's term and the masked sum of x, added in row order
+    const auto quotient = [&](const double* Wb, int64_t b, bool with_term) {
+        op_dgemm(c.dev, false, false, b, dp, kp, 1.0, Wb, kp, H, dp, 0.0, Q.f64(), dp);
+        dev_d2h(c.dev, hq.data(), Q.p, sizeof(double) * size_t(b) * dp);
+        dev_sync(c.dev);
+        for (int64_t i = 0; i < b; ++i)
+            for (int64_t j = 0; j < dp; ++j) {
+                const double x = hx[size_t(i) * ld + j];
+                double wh = hq[size_t(i) * dp + j];
+                if (wh < NMF_EPS) wh = NMF_EPS;
+                if (with_term && x > NMF_EPS) {
+                    hc[size_t(kp)] += x * std::log(x / wh);
+                    hc[size_t(kp) + 1] += x;
+                }
+                hq[size_t(i) * dp + j] = x / wh;
+            }
+        dev_h2d(c.dev, Q.p, hq.data(), sizeof(double) * size_t(b) * dp);
+    };
+    for (int64_t r0 = 0; r0 < n; r0 += Bk) {
+        const int64_t b = std::min(Bk, n - r0), count = (b - 1) * ld + dp;
+        double* Wb = W + r0 * kp;
+        op_cvt_to_f64(c.dev, X.dtype, Xb.f64(), static_cast<const char*>(X.p) + size_t(r0) * ld * esz, count);
+        dev_d2h(c.dev, hx.data(), Xb.p, sizeof(double) * size_t(count));
+        if (from_const) {
+            for (int64_t i = 0; i < b; ++i)
+                for (int64_t j = 0; j < kp; ++j) hw[size_t(i) * kp + j] = j < k ? wconst : 0.0;
+            dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
+        }
+        for (int64_t it = 0; it < inner; ++it) {
+            quotient(Wb, b, false);
+            op_dgemm(c.dev, false, true, b, kp, dp, 1.0, Q.f64(), dp, H, dp, 0.0, Z.f64(), kp);
+            dev_d2h(c.dev, hz.data(), Z.p, sizeof(double) * size_t(b) * kp);
+            dev_d2h(c.dev, hw.data(), Wb, sizeof(double) * size_t(b) * kp);
+            dev_sync(c.dev);
+            for (int64_t idx = 0; idx < b * kp; ++idx) {
+                double den = (hr[size_t(idx % kp)] + l1) + l2 * hw[idx];
+                if (den == 0.0) den = NMF_EPS;
+                hw[idx] = hw[idx] * (hz[idx] / den);
+            }
+            dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
+        }
+        if (A) {   // the blocks' contributions are added in block order
+            quotient(Wb, b, inner == 0);
+            op_dgemm(c.dev, true, false, kp, dp, b, 1.0, Wb, kp, Q.f64(), dp, 1.0, A, dp);
+            dev_d2h(c.dev, hw.data(), Wb, sizeof(double) * size_t(b) * kp);
+            dev_sync(c.dev);
+            for (int64_t i = 0; i < b; ++i)
+                for (int64_t j = 0; j < kp; ++j) hc[size_t(j)] += hw[size_t(i) * kp + j];
+        }
+    }
+    if (cts) dev_h2d(c.dev, cts, hc.data(), sizeof(double) * hc.size());
+    dev_sync(c.dev);
+    return false;
+}
+
+// rsum (DEVICE, kp) = the row sums of H
+void nmf_kl_rowsum_into(petal_ctx& c, int64_t kp, int64_t dp, const double* H, double* rsum) {
+    if (!c.nmf_fallback && op_nmf_kl_rowsum(c.dev, kp, dp, H, rsum)) return;
+    std::vector<double> h(size_t(kp) * dp), r(static_cast<size_t>(kp), 0.0);
+    dev_d2h(c.dev, h.data(), H, sizeof(double) * h.size());
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < kp; ++i)
+        for (int64_t f = 0; f < dp; ++f) r[size_t(i)] += h[size_t(i) * dp + f];
+    dev_h2d(c.dev, rsum, r.data(), sizeof(double) * r.size());
+    dev_sync(c.dev);
+}
+
+// The H side of an iteration: H <- H o (A / (colsum(W) + l1 + l2 H)), then rsum = the row sums of the new H.
+void nmf_kl_hupdate_into(petal_ctx& c, int64_t kp, int64_t dp, const double* A, const double* colsum, double* H, double l1, double l2,
+                         double* rsum) {
+    if (c.nmf_fallback || !op_nmf_kl_hrule(c.dev, kp, dp, A, colsum, H, l1, l2)) {
+        std::vector<double> a(size_t(kp) * dp), h(size_t(kp) * dp), cs(static_cast<size_t>(kp));
+        dev_d2h(c.dev, a.data(), A, sizeof(double) * a.size());
+        dev_d2h(c.dev, h.data(), H, sizeof(double) * h.size());
+        dev_d2h(c.dev, cs.data(), colsum, sizeof(double) * cs.size());
+        dev_sync(c.dev);
+        for (int64_t i = 0; i < kp; ++i)
+            for (int64_t f = 0; f < dp; ++f) {
+                const double hv = h[size_t(i) * dp + f];
+                double den = (cs[size_t(i)] + l1) + l2 * hv;
+                if (den == 0.0) den = NMF_EPS;
+                h[size_t(i) * dp + f] = hv * (a[size_t(i) * dp + f] / den);
+            }
+        dev_h2d(c.dev, H, h.data(), sizeof(double) * h.size());
+        dev_sync(c.dev);
+    }
+    nmf_kl_rowsum_into(c, kp, dp, H, rsum);
+}
+
+petal_nmf* nmf_kl_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                      int64_t seed, const petal_matrix* w_out) {
+    const Timer timer = start_fit(c, x);
+    if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
+    const int dt = x.dtype;
+    const int64_t n = x.rows, d = x.cols;
+    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
+    const DevMat X = ingest(c, x);
+    const NmfScan sx = nmf_scan(c, X);
+    nmf_reject(sx);
+    const int64_t dp = X.dp, kp = nmf_padded_k(k);
+    DBuf W(c.dev, sizeof(double) * size_t(n) * kp), H(c.dev, sizeof(double) * size_t(kp) * dp), G(c.dev, sizeof(double) * size_t(kp) * kp);
+    DBuf A(c.dev, sizeof(double) * size_t(kp) * dp), cts(c.dev, sizeof(double) * size_t(kp + 2)), rsum(c.dev, sizeof(double) * size_t(kp));
+    nmf_init_factors(c, dt, n, d, k, kp, dp, sx, w0, h0, seed, W, H);
+    dev_memset(c.dev, G.p, 0, G.bytes);   // (H H^T, which this loss never reads, as zeros: the CSR fit's handle)
+    nmf_kl_rowsum_into(c, kp, dp, H.f64(), rsum.f64());
+    // the loss = sqrt(2 max(0, term + <colsum W, rowsum H> - sum[x > eps] x)): a pass with inner = 0 leaves colsum(W), the term and the sum
+    bool kernel = true;
+    std::vector<double> hc(size_t(kp) + 2), hr(static_cast<size_t>(kp));
+    const auto read_loss = [&]() {
+        kernel = nmf_kl_pass_into(c, X, H.f64(), rsum.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 0, A.f64(), cts.f64()) && kernel;
+        dev_d2h(c.dev, hc.data(), cts.p, cts.bytes);
+        dev_d2h(c.dev, hr.data(), rsum.p, rsum.bytes);
+        dev_sync(c.dev);
+        double dot = 0.0;
+        for (int64_t j = 0; j < k; ++j) dot += hc[size_t(j)] * hr[size_t(j)];
+        return std::sqrt(2.0 * std::max(0.0, (hc[size_t(kp)] + dot) - hc[size_t(kp) + 1]));
+    };
+    const double err_init = read_loss();
+    double err_prev = err_init, err = err_init;
+    int64_t n_iter = spec.max_iter;
+    bool read = false;   // `err` is the loss of the iteration just run
+    for (int64_t it = 1; it <= spec.max_iter; ++it) {
+        kernel = nmf_kl_pass_into(c, X, H.f64(), rsum.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 1, A.f64(), cts.f64()) && kernel;
+        nmf_kl_hupdate_into(c, kp, dp, A.f64(), cts.f64(), H.f64(), spec.l1_h, spec.l2_h, rsum.f64());
+        read = false;
+        if (spec.tol > 0 && it % 10 == 0) {
+            err = read_loss();
+            read = true;
+            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
+            err_prev = err;
+        }
+    }
+    if (!read) err = read_loss();
+    if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, kp, *w_out);
+    std::unique_ptr<petal_nmf> h(new petal_nmf());
+    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
+    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = kernel ? 1 : 0; h->err = err; h->err_init = err_init; h->loss = NMF_LOSS_KL;
+    finish_stats(c, timer);
+    h->h = H.f64(); H.p = nullptr;
+    h->hht = G.f64(); G.p = nullptr;
+    return h.release();
+}
+
+// transform of a Kullback-Leibler model on dense rows: W starts at the constant sqrt(mean(Xq) / k) and takes exactly max_iter updates
+// with H fixed -- one pass over X whatever max_iter is where the kernel runs
+void nmf_kl_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
+    const Timer timer = start_fit(c, x);
+    if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
+    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
+    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    const int64_t m = x.rows;
+    check_output(w_out, h.dtype, m, h.k);
+    if (m == 0) { finish_stats(c, timer); return; }
+    const DevMat X = ingest(c, x);
+    const NmfScan sx = nmf_scan(c, X);
+    nmf_reject(sx);
+    const double w0 = std::sqrt(sx.sum / (double(m) * double(h.d)) / double(h.k));
+    DBuf W(c.dev, sizeof(double) * size_t(m) * h.kp), rsum(c.dev, sizeof(double) * size_t(h.kp));
+    nmf_kl_rowsum_into(c, h.kp, h.dp, h.h, rsum.f64());
+    const bool ran = nmf_kl_pass_into(c, X, h.h, rsum.f64(), h.k, h.kp, W.f64(), true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr);
+    h.last_kernel = ran ? 1 : 0;
+    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, h.kp, w_out);
+    finish_stats(c, timer);
+}
+}  // namespace
+
+petal_nmf* nmf_fit_loss(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, int64_t loss, const petal_matrix* w0,
+                        const petal_matrix* h0, int64_t seed, const petal_matrix* w_out) {
+    if (loss == NMF_LOSS_FROBENIUS) return nmf_fit(c, x, k, spec, w0, h0, seed, w_out);
+    if (loss != NMF_LOSS_KL) invalid_input("Nmf: unknown loss " + std::to_string(loss) + " (0: frobenius, 1: kullback-leibler)");
+    return nmf_kl_fit(c, x, k, spec, w0, h0, seed, w_out);
+}
+
+void nmf_transform_loss(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
+    if (h.loss == NMF_LOSS_FROBENIUS) { nmf_transform(c, h, x, w_out); return; }
+    nmf_usable(c, h);
+    nmf_kl_transform(c, h, x, w_out);
+}
+
+void nmf_kl_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* hh, const NmfSpec& spec, int64_t inner,
+                 double* w_out, double* a_out, double* colsum_out, double* term_out, int64_t* info1) {
+    check_matrix(x, "x");
+    if (info1) info1[0] = 0;
+    if (sharded(c)) invalid_input("nmf_kl_pass: a sharded ctx is not supported in this version");
+    const int64_t n = x.rows, d = x.cols;
+    if (n == 0 || d == 0) invalid_input("nmf_kl_pass: the input has no rows or no columns");
+    if (k < 1) invalid_input("nmf_kl_pass: the number of components should be at least 1");
+    if (inner < 0) invalid_input("negative parameter");
+    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0) || std::isinf(spec.l1_w) || std::isinf(spec.l2_w))
+        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    if (term_out && inner != 0) invalid_input("term_out comes with inner_iters = 0 only");
+    const DevMat X = ingest(c, x);
+    nmf_reject(nmf_scan(c, X));
+    const int64_t dp = X.dp, kp = nmf_padded_k(k);
+    std::vector<double> hw(size_t(n) * kp, 0.0), hp(size_t(kp) * dp, 0.0);
+    for (int64_t i = 0; i < n; ++i) std::copy(w_in + i * k, w_in + (i + 1) * k, hw.begin() + i * kp);
+    for (int64_t i = 0; i < k; ++i) std::copy(hh + i * d, hh + (i + 1) * d, hp.begin() + i * dp);
+    // W is formed inside a guard: a row in front and a row behind, every byte 0xFF beforehand.  The guard rows must come back
+    // untouched and the padding columns of W as zeros.
+    DBuf G(c.dev, sizeof(double) * size_t(n + 2) * kp), H(c.dev, sizeof(double) * hp.size()), rsum(c.dev, sizeof(double) * size_t(kp));
+    const bool side = a_out || colsum_out || term_out || inner == 0;   // (the loss pass always forms A and the sums)
+    DBuf A, cts;
+    if (side) {
+        A = DBuf(c.dev, sizeof(double) * size_t(kp) * dp);
+        cts = DBuf(c.dev, sizeof(double) * size_t(kp + 2));
+    }
+    double* W = G.f64() + kp;
+    dev_memset(c.dev, G.p, 0xFF, G.bytes);
+    dev_h2d(c.dev, W, hw.data(), sizeof(double) * hw.size());
+    dev_h2d(c.dev, H.p, hp.data(), H.bytes);
+    nmf_kl_rowsum_into(c, kp, dp, H.f64(), rsum.f64());
+    const bool ran = nmf_kl_pass_into(c, X, H.f64(), rsum.f64(), k, kp, W, false, 0.0, spec.l1_w, spec.l2_w, inner, A.f64(), cts.f64());
+    std::vector<double> hg(size_t(n + 2) * kp), hc(size_t(kp) + 2, 0.0);
+    dev_d2h(c.dev, hg.data(), G.p, G.bytes);
+    if (side) dev_d2h(c.dev, hc.data(), cts.p, cts.bytes);
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < n + 2; ++i)
+        for (int64_t j = 0; j < kp; ++j) {
+            uint64_t bits = 0;
+            std::memcpy(&bits, &hg[size_t(i) * kp + j], 8);
+            const bool guard = i == 0 || i == n + 1;
+            if (guard ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_kl_pass wrote outside the n x k block");
+        }
+    for (int64_t i = 0; i < n; ++i) std::copy(hg.begin() + (i + 1) * kp, hg.begin() + (i + 1) * kp + k, w_out + i * k);
+    if (a_out) {
+        dev_copy2d(c.dev, a_out, sizeof(double) * d, A.p, sizeof(double) * dp, sizeof(double) * d, size_t(k), 1);
+        dev_sync(c.dev);
+    }
+    if (colsum_out) std::copy(hc.begin(), hc.begin() + k, colsum_out);
+    if (term_out) *term_out = hc[size_t(kp)];
+    if (info1) info1[0] = ran ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------

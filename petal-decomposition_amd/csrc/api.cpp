@@ -14,6 +14,7 @@
 #include "../../include/petal_hip_nmf.h"
 #include "../../include/petal_hip_nmf_sparse.h"
 #include "../../include/petal_hip_nmf_kl.h"
+#include "../../include/petal_hip_nmf_kl_dense.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -503,6 +504,37 @@ int petal_nmf_kl_sweep_csr(petal_ctx* ctx, const petal_csr* x, int transposed, i
         need(spec, "spec");
         need(g_out, "g_out");
         nmf_kl_sweep_csr(*ctx, *x, transposed != 0, k, g_in, f, nmf_spec(*spec), inner_iters, g_out, colsum_out, term_out, info1);
+    });
+}
+
+// ---- include/petal_hip_nmf_kl_dense.h: the Kullback-Leibler loss on a dense matrix ---------------------------------------------------
+int petal_nmf_fit_loss(petal_ctx* ctx, const petal_matrix* x, int64_t k, const petal_nmf_spec* spec, int64_t loss, const petal_matrix* w0,
+                       const petal_matrix* h0, int64_t seed, petal_nmf** out, const petal_matrix* w_out) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(spec, "spec");
+        need(out, "out");
+        *out = nmf_fit_loss(*ctx, *x, k, nmf_spec(*spec), loss, w0, h0, seed, w_out);
+    });
+}
+int petal_nmf_transform_loss(petal_ctx* ctx, petal_nmf* h, const petal_matrix* x, const petal_matrix* w_out) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        need(x, "x");
+        need(w_out, "w_out");
+        nmf_transform_loss(*ctx, *h, *x, *w_out);
+    });
+}
+int petal_nmf_kl_pass(petal_ctx* ctx, const petal_matrix* x, int64_t k, const double* w_in, const double* h, const petal_nmf_spec* spec,
+                      int64_t inner_iters, double* w_out, double* a_out, double* colsum_out, double* term_out, int64_t* info1) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(w_in, "w_in");
+        need(h, "h");
+        need(spec, "spec");
+        need(w_out, "w_out");
+        nmf_kl_pass(*ctx, *x, k, w_in, h, nmf_spec(*spec), inner_iters, w_out, a_out, colsum_out, term_out, info1);
     });
 }
 

@@ -211,6 +211,12 @@ void nmf_kl_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t
                       int64_t inner, double* g_out, double* colsum_out, double* term_out, int64_t* info1);
 void nmf_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* h, const NmfSpec& spec, int64_t inner, double* w_out,
               double* a_out, double* b_out, int64_t* info1);
+// include/petal_hip_nmf_kl_dense.h: the Kullback-Leibler loss on a dense matrix
+petal_nmf* nmf_fit_loss(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, int64_t loss, const petal_matrix* w0,
+                        const petal_matrix* h0, int64_t seed, const petal_matrix* w_out);
+void nmf_transform_loss(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out);
+void nmf_kl_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* h, const NmfSpec& spec, int64_t inner,
+                 double* w_out, double* a_out, double* colsum_out, double* term_out, int64_t* info1);
 // include/petal_hip_ipca.h: IncrementalPca
 petal_ipca* ipca_create(petal_ctx& c, int64_t d, int32_t dtype, bool centering);
 void ipca_destroy(petal_ipca* h);

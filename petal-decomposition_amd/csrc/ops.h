@@ -279,6 +279,20 @@ bool op_nmf_kl_sweep_csr(Dev*, int dtype, const CsrImage& img, int64_t k, int64_
 bool op_nmf_kl_colsum(Dev*, const double* G, int64_t rows, int64_t kp, const double* terms, double* colsum_term);
 // out1 (DEVICE) = sum over nnz stored values in dtype of [v > 2^-23] v, a fixed order.
 bool op_nmf_kl_vsum(Dev*, int dtype, const void* val, int64_t nnz, double* out1);
+// Nmf with the Kullback-Leibler loss on dense data (include/petal_hip_nmf_kl_dense.h).  Device layouts are op_nmf_pass's; rsum (DEVICE,
+// kp doubles) = the row sums of H.  The fused pass: `inner` times  WH = W H, WH[WH < 2^-23] = 2^-23, Q = X / WH, den = rsum + l1 + l2 W,
+// den[den == 0] = 2^-23, W <- W o ((Q H^T) / den)  (W in place; from_const as op_nmf_pass), then, where A and cts are given (both or
+// neither), A = W^T (X / max(W H, 2^-23)) with the W just written and cts (DEVICE, kp + 2 doubles) = { colsum(W), term, sum x }: the
+// last two for inner == 0 only (which needs A and leaves W alone), term = sum [x > 2^-23] x log(x / max(W H, 2^-23)) and sum x over the
+// same entries, else zeros.  X is read once from memory however large `inner` is (with the H side at 64 padded components and more than
+// 256 padded columns: three launches, X read twice -- k_nmf_kl_dense.inc); no n x dp intermediate; no atomics.  false, NOTHING done:
+// outside op_nmf_pass's envelope.
+bool op_nmf_kl_pass(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64_t ldx, const double* H, const double* rsum, int64_t k, int64_t kp,
+                    double* W, bool from_const, double wconst, double l1, double l2, int64_t inner, double* A, double* cts);
+// den = colsum[row] + l1 + l2 H, den[den == 0] = 2^-23, H <- H o (A / den) on kp x dp (ld dp).
+bool op_nmf_kl_hrule(Dev*, int64_t kp, int64_t dp, const double* A, const double* colsum, double* H, double l1, double l2);
+// out (DEVICE, kp doubles) = the row sums of H (kp x dp, ld dp), a fixed order.
+bool op_nmf_kl_rowsum(Dev*, int64_t kp, int64_t dp, const double* H, double* out);
 // out (img.rows x cols in dtype, ldo; DEVICE) = the dense image: zeros, then every stored entry added in position order.
 bool op_csr_densify(Dev*, int dtype, const CsrImage& img, void* out, int64_t cols, int64_t ldo);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns

@@ -3,6 +3,7 @@
 //! is float64 inside; outputs are rounded once to `A`.
 use crate::ffi_nmf::{self, PetalNmf, PetalNmfSpec};
 use crate::ffi_nmf_kl;
+use crate::ffi_nmf_kl_dense;
 use crate::ffi_nmf_sparse;
 use crate::pca::CsrMatrix;
 use crate::{view, with_ctx, DecompositionError, HipScalar};
@@ -27,6 +28,16 @@ impl NmfLoss {
     }
 }
 
+/// What the dense entries do under the Kullback-Leibler loss (include/petal_hip_nmf_kl_dense.h; source only, unverified like the rest
+/// of this crate).  `Compress` (the default) keeps them refusing; `Fused` sends the array to the fused dense pass `k_nmf_kl_pass` (the
+/// composed path outside its envelope).  Under the Frobenius loss it changes nothing.
+#[derive(Debug, Clone, Copy, PartialEq, Eq, Default)]
+pub enum NmfDensePath {
+    #[default]
+    Compress,
+    Fused,
+}
+
 /// The parameters of a fit; `alpha_h: None` means the same as `alpha_w` (scikit-learn's "same").  `loss` is read by `fit_csr` and its
 /// siblings; `transform_csr` follows the loss the model was fitted with.
 #[derive(Debug, Clone, Copy, PartialEq)]
@@ -38,10 +49,11 @@ pub struct NmfParams {
     pub alpha_h: Option<f64>,
     pub l1_ratio: f64,
     pub loss: NmfLoss,
+    pub dense_path: NmfDensePath,
 }
 
 impl Default for NmfParams {
-    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0, loss: NmfLoss::Frobenius } }
+    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0, loss: NmfLoss::Frobenius, dense_path: NmfDensePath::Compress } }
 }
 
 /// { n, d, k, iterations run, k_nmf_pass ran in the fit, k_nmf_pass ran in the last transform (-1 before the first) }
@@ -86,7 +98,15 @@ impl<A: HipScalar> Nmf<A> {
         let raw = self.handle()?;
         let mut w = Array2::<A>::default((input.nrows(), self.k));
         let (x, wv) = (view(input), view(&w.view_mut()));
-        with_ctx(|ctx| unsafe { ffi_nmf::petal_nmf_transform(ctx, raw, &x, &wv) }, || ())?;
+        if self.params.dense_path == NmfDensePath::Fused {
+            // dispatches on the model's loss; a Frobenius model: petal_nmf_transform's bytes
+            with_ctx(|ctx| unsafe { ffi_nmf_kl_dense::petal_nmf_transform_loss(ctx, raw, &x, &wv) }, || ())?;
+            if self.model_loss()? == NmfLoss::KullbackLeibler && input.nrows() > 0 {
+                self.kernel_path = self.info()?.transform_kernel;
+            }
+        } else {
+            with_ctx(|ctx| unsafe { ffi_nmf::petal_nmf_transform(ctx, raw, &x, &wv) }, || ())?;
+        }
         Ok(w)
     }
     pub fn inverse_transform<S: Data<Elem = A>>(&mut self, w: &ArrayBase<S, Ix2>) -> Result<Array2<A>, DecompositionError> {
@@ -188,7 +208,8 @@ impl<A: HipScalar> Nmf<A> {
     }
     fn inner_fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, init: Option<(&Array2<A>, &Array2<A>)>, w: Option<&mut Array2<A>>)
         -> Result<(), DecompositionError> {
-        if self.params.loss == NmfLoss::KullbackLeibler {
+        let fused = self.params.loss == NmfLoss::KullbackLeibler && self.params.dense_path == NmfDensePath::Fused;
+        if self.params.loss == NmfLoss::KullbackLeibler && !fused {
             return Err(DecompositionError::InvalidInput("Nmf: the kullback-leibler loss takes a CsrMatrix".into()));
         }
         let x = view(input);
@@ -196,17 +217,24 @@ impl<A: HipScalar> Nmf<A> {
         let iv = init.map(|(w0, h0)| (view(w0), view(h0)));
         let spec = self.spec(input.nrows() as f64, input.ncols() as f64);
         let mut raw = std::ptr::null_mut();
-        let (k, seed) = (self.k as i64, self.params.seed as i64);
+        let (k, seed, loss) = (self.k as i64, self.params.seed as i64, self.params.loss);
         with_ctx(
             |ctx| unsafe {
-                ffi_nmf::petal_nmf_fit(ctx, &x, k, &spec, iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _),
-                                       iv.as_ref().map_or(std::ptr::null(), |m| &m.1 as *const _), seed, &mut raw,
-                                       wv.as_ref().map_or(std::ptr::null(), |m| m as *const _))
+                let (w0, h0) = (iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _), iv.as_ref().map_or(std::ptr::null(), |m| &m.1 as *const _));
+                let wo = wv.as_ref().map_or(std::ptr::null(), |m| m as *const _);
+                if fused {
+                    ffi_nmf_kl_dense::petal_nmf_fit_loss(ctx, &x, k, &spec, loss.code(), w0, h0, seed, &mut raw, wo)
+                } else {
+                    ffi_nmf::petal_nmf_fit(ctx, &x, k, &spec, w0, h0, seed, &mut raw, wo)
+                }
             },
             || (),
         )?;
         unsafe { ffi_nmf::petal_nmf_destroy(self.raw) };
         self.raw = raw;
+        if fused {
+            self.kernel_path = if self.info()?.fit_kernel { 1 } else { 0 };
+        }
         Ok(())
     }
 }
