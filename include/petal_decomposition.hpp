@@ -31,6 +31,7 @@
 #include "petal_hip_nmf_sparse.h"
 #include "petal_hip_nmf_kl.h"
 #include "petal_hip_nmf_kl_dense.h"
+#include "petal_hip_nmf_cd.h"
 
 namespace petal_decomposition {
 
@@ -578,6 +579,10 @@ enum class NmfLoss : int64_t { Frobenius = PETAL_NMF_LOSS_FROBENIUS, KullbackLei
 // petal_nmf_transform_loss; the composed path outside the kernel's envelope, no cap on the components).  Under the Frobenius loss it
 // changes nothing.
 enum class NmfDensePath : int { Compress = 0, Fused = 1 };
+// extension beyond the crate (petal_hip_nmf_cd.h): the solver of the NEXT dense fit.  MultiplicativeUpdate (the default) is everything
+// above, byte for byte; CoordinateDescent is scikit-learn's NMF(solver="cd") (its default, shuffle=False) under the Frobenius loss:
+// the stopping rule runs after every iteration, transform starts from W = 0.  With the Kullback-Leibler loss or a CsrMatrix it throws.
+enum class NmfSolver : int64_t { MultiplicativeUpdate = PETAL_NMF_SOLVER_MU, CoordinateDescent = PETAL_NMF_SOLVER_CD };
 
 template <class A>
 class Nmf {
@@ -590,12 +595,20 @@ class Nmf {
     Nmf& operator=(const Nmf&) = delete;
     Nmf(Nmf&& o) noexcept
         : k_(o.k_), max_iter_(o.max_iter_), tol_(o.tol_), seed_(o.seed_), alpha_w_(o.alpha_w_), alpha_h_(o.alpha_h_), l1_ratio_(o.l1_ratio_),
-          ctx_(o.ctx_), h_(o.h_), kernel_path_(o.kernel_path_), loss_(o.loss_), dense_path_(o.dense_path_) { o.h_ = nullptr; }
+          ctx_(o.ctx_), h_(o.h_), kernel_path_(o.kernel_path_), loss_(o.loss_), dense_path_(o.dense_path_), solver_(o.solver_) { o.h_ = nullptr; }
     ~Nmf() { petal_nmf_destroy(h_); }
     Nmf& loss(NmfLoss l) { loss_ = l; return *this; }   // the loss of the NEXT fit on a CsrMatrix (petal_hip_nmf_kl.h)
     NmfLoss loss() const { return loss_; }
     Nmf& dense_path(NmfDensePath p) { dense_path_ = p; return *this; }   // the route of the NEXT dense call under the Kullback-Leibler loss
     NmfDensePath dense_path() const { return dense_path_; }
+    Nmf& solver(NmfSolver s) { solver_ = s; return *this; }   // the solver of the NEXT dense fit (petal_hip_nmf_cd.h)
+    NmfSolver solver() const { return solver_; }
+    // the solver the fitted model remembers
+    NmfSolver model_solver() const {
+        int64_t v = 0;
+        if (petal_nmf_get_solver(handle(), &v) != PETAL_OK) throw DecompositionError(DecompositionError::InvalidInput, "petal_nmf_get_solver failed");
+        return static_cast<NmfSolver>(v);
+    }
     // the loss the fitted model remembers
     NmfLoss model_loss() const {
         int64_t v = 0;
@@ -690,7 +703,14 @@ class Nmf {
             throw DecompositionError(DecompositionError::InvalidInput,
                                      "Nmf: the kullback-leibler loss takes a CsrMatrix (compress the dense rows to the CSR of their non-zero entries)");
     }
+    void no_sparse_cd() const {
+        if (solver_ == NmfSolver::CoordinateDescent)
+            throw DecompositionError(DecompositionError::InvalidInput, "Nmf: the coordinate-descent solver does not take a CsrMatrix in this version");
+    }
     void inner_fit(const Array2<A>& input, const Array2<A>* w0, const Array2<A>* h0, Array2<A>* w) {
+        const bool cd = solver_ == NmfSolver::CoordinateDescent;
+        if (cd && loss_ != NmfLoss::Frobenius)
+            throw DecompositionError(DecompositionError::InvalidInput, "Nmf: the coordinate-descent solver does not take the kullback-leibler loss");
         const bool fused = loss_ == NmfLoss::KullbackLeibler && dense_path_ == NmfDensePath::Fused;
         if (!fused) no_dense_kl();
         petal_matrix mx = input.view(), m0{}, m1{}, mw{};
@@ -702,7 +722,10 @@ class Nmf {
         spec.l1_w = d * alpha_w_ * l1_ratio_; spec.l2_w = d * alpha_w_ * (1.0 - l1_ratio_);
         spec.l1_h = n * alpha_h_ * l1_ratio_; spec.l2_h = n * alpha_h_ * (1.0 - l1_ratio_);
         petal_nmf* h = nullptr;
-        if (fused)
+        if (cd)
+            context().check(petal_nmf_fit_solver(context().get(), &mx, k_, &spec, static_cast<int64_t>(solver_), w0 ? &m0 : nullptr,
+                                                 w0 ? &m1 : nullptr, int64_t(seed_), &h, w ? &mw : nullptr));
+        else if (fused)
             context().check(petal_nmf_fit_loss(context().get(), &mx, k_, &spec, static_cast<int64_t>(loss_), w0 ? &m0 : nullptr,
                                                w0 ? &m1 : nullptr, int64_t(seed_), &h, w ? &mw : nullptr));
         else
@@ -713,6 +736,7 @@ class Nmf {
         if (fused) kernel_path_ = info().fit_kernel ? 1 : 0;
     }
     void inner_fit_sparse(const CsrMatrix<A>& input, const Array2<A>* w0, const Array2<A>* h0, Array2<A>* w) {
+        no_sparse_cd();
         petal_matrix m0{}, m1{}, mw{};
         if (w0) { m0 = w0->view(); m1 = h0->view(); }
         if (w) mw = w->view();
@@ -740,6 +764,7 @@ class Nmf {
     int64_t kernel_path_ = 0;
     NmfLoss loss_ = NmfLoss::Frobenius;
     NmfDensePath dense_path_ = NmfDensePath::Compress;
+    NmfSolver solver_ = NmfSolver::MultiplicativeUpdate;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

@@ -30,7 +30,8 @@
  * Not in this version: other beta-losses, the coordinate-descent solver, NNDSVD initialisation, CSR input, sharded fits, float32 /
  * split-bf16 products, a tolerance stop in transform.  CSR input and sharded fits are the natural follow-ups: the W rule is row-local
  * and W^T X, W^T W are sums over rows.  (CSR input has since been added beside this header: petal_hip_nmf_sparse.h; the
- * Kullback-Leibler loss on CSR input: petal_hip_nmf_kl.h.)
+ * Kullback-Leibler loss on CSR input: petal_hip_nmf_kl.h; the
+ * coordinate-descent solver on dense input: petal_hip_nmf_cd.h.)
  */
 #ifndef PETAL_HIP_NMF_H
 #define PETAL_HIP_NMF_H

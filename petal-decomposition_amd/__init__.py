@@ -247,6 +247,14 @@ ABI_NMF_KL_DENSE = [
     ("petal_nmf_transform_loss", C.c_int, [_P, _P, _M, _M]),
     ("petal_nmf_kl_pass", C.c_int, [_P, _M, C.c_int64, _D, _D, _NS, C.c_int64, _D, _D, _D, _D, _L]),
 ]
+# every symbol include/petal_hip_nmf_cd.h declares (Nmf with the coordinate-descent solver, its fused pass and its H side by themselves)
+NMF_SOLVER_MU, NMF_SOLVER_CD = 0, 1
+ABI_NMF_CD = [
+    ("petal_nmf_fit_solver", C.c_int, [_P, _M, C.c_int64, _NS, C.c_int64, _M, _M, C.c_int64, C.POINTER(C.c_void_p), _M]),
+    ("petal_nmf_get_solver", C.c_int, [_P, _L]),
+    ("petal_nmf_cd_pass", C.c_int, [_P, _M, C.c_int64, _D, _D, _NS, C.c_int64, C.c_int, _D, _D, _D, _D, _L]),
+    ("petal_nmf_cd_hupdate", C.c_int, [_P, C.c_int64, C.c_int64, _D, _D, _D, _NS, _D, _D, _L]),
+]
 
 
 def _preload_torch_hip_runtime():
@@ -265,7 +273,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h, petal_hip_nmf_sparse.h, petal_hip_nmf_kl.h, petal_hip_nmf_kl_dense.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h, petal_hip_nmf_sparse.h, petal_hip_nmf_kl.h, petal_hip_nmf_kl_dense.h, petal_hip_nmf_cd.h and petal_hip_probe.h and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -274,7 +282,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF + ABI_NMF_SPARSE + ABI_NMF_KL + ABI_NMF_KL_DENSE:
+    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF + ABI_NMF_SPARSE + ABI_NMF_KL + ABI_NMF_KL_DENSE + ABI_NMF_CD:
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -907,6 +915,52 @@ def nmf_kl_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, want_a=True, want_te
     return (out, {"kernel": int(info[0])}) if want_info else out
 
 
+def nmf_cd_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, from_zero: bool = False, want_ab=True, ctx: Optional["Context"] = None,
+                want_info: bool = False):
+    """Test aid (``petal_nmf_cd_pass``, include/petal_hip_nmf_cd.h): the fused pass of a coordinate-descent ``Nmf`` iteration by
+    itself, in float64.  ``x`` (n x d): numpy or ``torch.cuda``, any strides; ``w`` (n x k), ``h`` (k x d): float64.  Z = x h^T once,
+    then ``inner_iters`` Gauss-Seidel sweeps of every row of W with S = h h^T + l2_w I and z = Z - l1_w (``from_zero``: W starts as
+    zeros).  Returns ``(w_new, a, b, violation)`` with a = w_new^T x, b = w_new^T w_new and violation = one sum of |pg| per sweep
+    (``want_ab=False``: ``(w_new, violation)``).  ``want_info``: also ``{"kernel": k_nmf_cd_pass ran}``."""
+    keep = []
+    mx = describe(x, keep)
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+    h = np.ascontiguousarray(np.asarray(h, dtype=np.float64))
+    if w.ndim != 2 or h.ndim != 2 or w.shape[0] != mx.rows or h.shape != (w.shape[1], mx.cols):
+        raise InvalidInput(f"w should be {mx.rows} x k and h k x {mx.cols}")
+    k = w.shape[1]
+    spec = _nmf_spec(1, 0.0, l1_w, l2_w)
+    wo = np.zeros((mx.rows, k))
+    a = np.zeros((k, mx.cols)) if want_ab else None
+    b = np.zeros((k, k)) if want_ab else None
+    viol = np.zeros(max(int(inner_iters), 0))
+    info = (C.c_int64 * 1)()
+    ctx.check(ctx.lib.petal_nmf_cd_pass(ctx._h, C.byref(mx), k, w.ctypes.data_as(_D), h.ctypes.data_as(_D), C.byref(spec), int(inner_iters),
+                                        int(bool(from_zero)), wo.ctypes.data_as(_D), a.ctypes.data_as(_D) if want_ab else None,
+                                        b.ctypes.data_as(_D) if want_ab else None, viol.ctypes.data_as(_D) if viol.size else None, info))
+    out = (wo, a, b, viol) if want_ab else (wo, viol)
+    return (out, {"kernel": int(info[0])}) if want_info else out
+
+
+def nmf_cd_hupdate(a, b, h, l1_h=0.0, l2_h=0.0, ctx: Optional["Context"] = None, want_info: bool = False):
+    """Test aid (``petal_nmf_cd_hupdate``, include/petal_hip_nmf_cd.h): the H side of a coordinate-descent ``Nmf`` iteration by itself,
+    in float64: one sweep of every row of h^T with S = b + l2_h I and z = a[:, j] - l1_h.  ``a``, ``h`` (k x d), ``b`` (k x k).
+    Returns ``(h_new, violation)``.  ``want_info``: also ``{"kernel": k_nmf_cd_hrule ran}``."""
+    ctx = ctx or default_context()
+    a, b, h = (np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for v in (a, b, h))
+    if a.ndim != 2 or a.shape != h.shape or b.shape != (a.shape[0], a.shape[0]):
+        raise InvalidInput("a and h should be k x d and b k x k")
+    k, d = a.shape
+    spec = _nmf_spec(1, 0.0, 0.0, 0.0, l1_h, l2_h)
+    ho, viol = np.zeros((k, d)), np.zeros(1)
+    info = (C.c_int64 * 1)()
+    ctx.check(ctx.lib.petal_nmf_cd_hupdate(ctx._h, k, d, a.ctypes.data_as(_D), b.ctypes.data_as(_D), h.ctypes.data_as(_D), C.byref(spec),
+                                           ho.ctypes.data_as(_D), viol.ctypes.data_as(_D), info))
+    out = (ho, float(viol[0]))
+    return (out, {"kernel": int(info[0])}) if want_info else out
+
+
 def _like_input(x, w):
     """w (a numpy array computed on the host) where x lives: a torch tensor on x's device for a torch x"""
     if _is_torch(x):
@@ -960,17 +1014,28 @@ class Nmf:
     zero-copy and the results stay on its device, ``transform`` reads its input once whatever ``max_iter`` is, there is no cap on the
     components (outside the kernel's envelope the library's composed path runs), and ``kernel_path`` says whether the kernel ran (1)
     or the composed path (0).  The default stays ``"compress"`` only because existing callers are pinned to its bytes; a measured
-    crossover may move it in a later change.  Under the Frobenius loss the keyword is read and changes nothing."""
+    crossover may move it in a later change.  Under the Frobenius loss the keyword is read and changes nothing.
+
+    ``solver`` (include/petal_hip_nmf_cd.h): ``"mu"``, the default, is everything above, byte for byte; ``"cd"`` is scikit-learn's
+    coordinate-descent solver (its default, ``shuffle=False``) on dense input under the Frobenius loss: one fused pass k_nmf_cd_pass
+    per iteration, scikit-learn's stopping rule after every iteration when ``tol > 0`` (``tol = 0``: exactly ``max_iter``
+    iterations), ``transform`` from W = 0 with exactly ``max_iter`` sweeps.  ``"cd"`` with the Kullback-Leibler loss or with sparse
+    input is ``InvalidInput``.  ``solver`` is readable."""
 
     def __init__(self, n_components: int, max_iter: int = 200, tol: float = 1e-4, init: str = "random", seed: int = 0,
                  alpha_W: float = 0.0, alpha_H="same", l1_ratio: float = 0.0, ctx: Optional[Context] = None, beta_loss="frobenius",
-                 dense_path: str = "compress"):
+                 dense_path: str = "compress", solver: str = "mu"):
         if init not in ("random", "custom"):
             raise InvalidInput(f"unknown init {init!r} (random or custom)")
         if dense_path not in ("compress", "fused"):
             raise InvalidInput(f"unknown dense_path {dense_path!r} (compress or fused)")
+        if not isinstance(solver, str) or solver not in ("mu", "cd"):
+            raise InvalidInput(f"unknown solver {solver!r} (mu or cd)")
         self.dense_path = dense_path
+        self.solver = solver
         self._loss = _beta_loss_code(beta_loss)
+        if solver == "cd" and self._loss != NMF_LOSS_FROBENIUS:
+            raise InvalidInput("solver='cd' does not take the kullback-leibler loss (the coordinate-descent solver is for the frobenius loss)")
         self.beta_loss = "frobenius" if self._loss == NMF_LOSS_FROBENIUS else "kullback-leibler"
         self._k = int(n_components)
         self.max_iter, self.tol, self.init, self.seed = int(max_iter), float(tol), init, int(seed)
@@ -1062,6 +1127,8 @@ class Nmf:
                 sx.close()
 
     def _inner_fit(self, x, W, H, want_w: bool):
+        if self.solver == "cd" and _is_sparse(x):
+            raise InvalidInput("solver='cd' does not take sparse (CSR) input in this version")
         if _is_sparse(x):
             return self._inner_fit_sparse(x, W, H, want_w)
         if self._loss == NMF_LOSS_KL and self.dense_path == "compress":   # the CSR of the non-zero entries, the same path
@@ -1079,7 +1146,9 @@ class Nmf:
         h = C.c_void_p()
         args = (C.byref(mw) if mw is not None else None, C.byref(mh) if mh is not None else None,
                 C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h), C.byref(mo) if mo is not None else None)
-        if self._loss == NMF_LOSS_FROBENIUS:
+        if self.solver == "cd":   # include/petal_hip_nmf_cd.h
+            ctx.check(ctx.lib.petal_nmf_fit_solver(ctx._h, C.byref(mx), self._k, C.byref(spec), NMF_SOLVER_CD, *args))
+        elif self._loss == NMF_LOSS_FROBENIUS:
             ctx.check(ctx.lib.petal_nmf_fit(ctx._h, C.byref(mx), self._k, C.byref(spec), *args))
         else:   # dense_path="fused" (include/petal_hip_nmf_kl_dense.h)
             ctx.check(ctx.lib.petal_nmf_fit_loss(ctx._h, C.byref(mx), self._k, C.byref(spec), self._loss, *args))

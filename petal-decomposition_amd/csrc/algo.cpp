@@ -1866,6 +1866,7 @@ petal_nmf* nmf_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec
 
 void nmf_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
     nmf_usable(c, h);
+    if (h.solver != 0) { nmf_cd_transform(c, h, x, w_out); return; }   // a coordinate-descent model (include/petal_hip_nmf_cd.h)
     if (h.loss != 0)
         invalid_input("Nmf: the dense transform does not take a kullback-leibler model (petal_nmf_transform_csr does: compress the rows to CSR)");
     const Timer timer = start_fit(c, x);
@@ -3756,6 +3757,7 @@ void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const pet
     nmf_usable(c, h);
     csr_usable(c, x);
     if (kernel_path) *kernel_path = 0;
+    if (h.solver != 0) invalid_input("Nmf: the coordinate-descent solver does not take CSR input in this version");
     if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
     if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
     const int64_t m = x.rows;
@@ -4512,6 +4514,282 @@ void nmf_kl_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w
     }
     if (colsum_out) std::copy(hc.begin(), hc.begin() + k, colsum_out);
     if (term_out) *term_out = hc[size_t(kp)];
+    if (info1) info1[0] = ran ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Nmf by coordinate descent (include/petal_hip_nmf_cd.h; DESIGN.md sections 4 and 7): scikit-learn's NMF(solver="cd") without
+// shuffling.  An iteration is ONE fused pass over X (k_nmf_cd_pass through op_nmf_cd_pass: Z = X H^T, a Gauss-Seidel sweep of every
+// row of W, A = W^T X and B = W^T W with the new W) and the same sweep on the rows of H^T (op_nmf_cd_hupdate).  The composed path
+// (the host simulation, PETAL_OPT_NMF_FALLBACK, shapes outside op_nmf_pass's envelope) forms Z, A and B with op_cvt_to_f64 and op_dgemm
+// in row blocks and runs the sweep on the host over read-back copies, blocks added in block order.
+__attribute__((weak)) bool op_nmf_cd_pass(Dev*, int, const void*, int64_t, int64_t, int64_t, const double*, const double*, int64_t, int64_t, double*,
+                                          bool, double, double, int64_t, double*, double*, double*) {
+    return false;
+}
+__attribute__((weak)) bool op_nmf_cd_hupdate(Dev*, int64_t, int64_t, int64_t, const double*, const double*, double*, double*, double, double, double*,
+                                             double*) {
+    return false;
+}
+namespace {
+// one sweep of a row w (stride ws) over its kp coordinates with S (kp x kp, the penalty on its diagonal) and z (the penalty taken off):
+// the header's statement, literally.  Returns the row's violation.
+double nmf_cd_sweep_host(double* w, int64_t ws, const double* z, const double* S, int64_t kp) {
+    double viol = 0.0;
+    for (int64_t t = 0; t < kp; ++t) {
+        double grad = -z[t];
+        for (int64_t r = 0; r < kp; ++r) grad += S[t * kp + r] * w[r * ws];
+        const double pg = w[t * ws] == 0.0 ? std::min(0.0, grad) : grad;
+        viol += std::fabs(pg);
+        const double stt = S[t * kp + t];
+        if (stt != 0.0) w[t * ws] = std::max(w[t * ws] - grad / stt, 0.0);
+    }
+    return viol;
+}
+// S = G + l2 I on the first k diagonal entries (G: DEVICE, kp x kp), on the host
+std::vector<double> nmf_cd_host_s(petal_ctx& c, const double* G, int64_t k, int64_t kp, double l2) {
+    std::vector<double> s(size_t(kp) * kp);
+    dev_d2h(c.dev, s.data(), G, sizeof(double) * s.size());
+    dev_sync(c.dev);
+    for (int64_t t = 0; t < k; ++t) s[size_t(t) * kp + t] += l2;
+    return s;
+}
+
+// The pass (ops.h, op_nmf_cd_pass): the kernel where the layer has it, else the same statement in row blocks.  viol: DEVICE, `inner`
+// doubles, nullable.  Returns "k_nmf_cd_pass ran".
+bool nmf_cd_pass_into(petal_ctx& c, const DevMat& X, const double* H, const double* HHt, int64_t k, int64_t kp, double* W, bool from_zero, double l1,
+                      double l2, int64_t inner, double* A, double* B, double* viol) {
+    const int64_t n = X.n, dp = X.dp, ld = X.ld;
+    if (!c.nmf_fallback) {
+        dev_set_tag(c.dev, TAG_POW);   // (as nmf_pass_into: with profiling on, stats.pow_ms is the pass's own time)
+        const bool ran = op_nmf_cd_pass(c.dev, X.dtype, X.p, n, dp, ld, H, HHt, k, kp, W, from_zero, l1, l2, inner, A, B, viol);
+        dev_set_tag(c.dev, TAG_NONE);
+        if (ran) return true;
+    }
+    const int64_t Bk = std::max<int64_t>(1, std::min(n, NMF_FALLBACK_BLOCK / ld));
+    const size_t esz = dtype_size(X.dtype);
+    DBuf Xb(c.dev, sizeof(double) * size_t((Bk - 1) * ld + dp)), Z(c.dev, sizeof(double) * size_t(Bk) * kp);
+    std::vector<double> hz(size_t(Bk) * kp), hw(size_t(Bk) * kp), hv(size_t(std::max<int64_t>(inner, 1)), 0.0), s;
+    if (inner > 0) s = nmf_cd_host_s(c, HHt, k, kp, l2);
+    if (A) {
+        dev_memset(c.dev, A, 0, sizeof(double) * size_t(kp) * dp);
+        dev_memset(c.dev, B, 0, sizeof(double) * size_t(kp) * kp);
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += Bk) {
+        const int64_t b = std::min(Bk, n - r0);
+        double* Wb = W + r0 * kp;
+        op_cvt_to_f64(c.dev, X.dtype, Xb.f64(), static_cast<const char*>(X.p) + size_t(r0) * ld * esz, (b - 1) * ld + dp);
+        if (from_zero) dev_memset(c.dev, Wb, 0, sizeof(double) * size_t(b) * kp);
+        if (inner > 0) {
+            op_dgemm(c.dev, false, true, b, kp, dp, 1.0, Xb.f64(), ld, H, dp, 0.0, Z.f64(), kp);
+            dev_d2h(c.dev, hz.data(), Z.p, sizeof(double) * size_t(b) * kp);
+            dev_d2h(c.dev, hw.data(), Wb, sizeof(double) * size_t(b) * kp);
+            dev_sync(c.dev);
+            for (int64_t idx = 0; idx < b * kp; ++idx) hz[idx] -= l1;
+            for (int64_t it = 0; it < inner; ++it)
+                for (int64_t i = 0; i < b; ++i) hv[size_t(it)] += nmf_cd_sweep_host(&hw[size_t(i) * kp], 1, &hz[size_t(i) * kp], s.data(), kp);
+            dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
+        }
+        if (A) {   // the blocks' contributions are added in block order
+            op_dgemm(c.dev, true, false, kp, dp, b, 1.0, Wb, kp, Xb.f64(), ld, 1.0, A, dp);
+            op_dgemm(c.dev, true, false, kp, kp, b, 1.0, Wb, kp, Wb, kp, 1.0, B, kp);
+        }
+        dev_sync(c.dev);   // (hw goes up before the next block overwrites it)
+    }
+    if (viol && inner > 0) dev_h2d(c.dev, viol, hv.data(), sizeof(double) * size_t(inner));
+    dev_sync(c.dev);
+    return false;
+}
+
+// The H side of an iteration (ops.h, op_nmf_cd_hupdate); dots: DEVICE, two doubles; viol1: DEVICE, one double.  Returns "the layer's
+// kernels ran".
+bool nmf_cd_hupdate_into(petal_ctx& c, int64_t k, int64_t kp, int64_t dp, const double* A, const double* B, double* H, double* HHt, double l1,
+                         double l2, double* dots, double* viol1) {
+    if (!c.nmf_fallback && op_nmf_cd_hupdate(c.dev, k, kp, dp, A, B, H, HHt, l1, l2, dots, viol1)) return true;
+    std::vector<double> a(size_t(kp) * dp), b(size_t(kp) * kp), h(size_t(kp) * dp), z(size_t(kp), 0.0), hht;
+    const std::vector<double> s = nmf_cd_host_s(c, B, k, kp, l2);
+    dev_d2h(c.dev, a.data(), A, sizeof(double) * a.size());
+    dev_d2h(c.dev, b.data(), B, sizeof(double) * b.size());
+    dev_d2h(c.dev, h.data(), H, sizeof(double) * h.size());
+    dev_sync(c.dev);
+    double hv = 0.0;
+    for (int64_t f = 0; f < dp; ++f) {
+        for (int64_t t = 0; t < kp; ++t) z[size_t(t)] = a[size_t(t) * dp + f] - l1;
+        hv += nmf_cd_sweep_host(&h[size_t(f)], dp, z.data(), s.data(), kp);
+    }
+    double hd[2];
+    nmf_host_gram_dots(a, b, h, kp, dp, hht, hd);
+    dev_h2d(c.dev, H, h.data(), sizeof(double) * h.size());
+    dev_h2d(c.dev, HHt, hht.data(), sizeof(double) * hht.size());
+    dev_h2d(c.dev, dots, hd, sizeof(hd));
+    dev_h2d(c.dev, viol1, &hv, sizeof(hv));
+    dev_sync(c.dev);
+    return false;
+}
+
+petal_nmf* nmf_cd_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                      int64_t seed, const petal_matrix* w_out) {
+    const Timer timer = start_fit(c, x);
+    if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
+    const int dt = x.dtype;
+    const int64_t n = x.rows, d = x.cols;
+    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
+    const DevMat X = ingest(c, x);
+    const NmfScan sx = nmf_scan(c, X);
+    nmf_reject(sx);
+    const int64_t dp = X.dp, kp = nmf_padded_k(k);
+    DBuf W(c.dev, sizeof(double) * size_t(n) * kp), H(c.dev, sizeof(double) * size_t(kp) * dp), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
+    DBuf A(c.dev, sizeof(double) * size_t(kp) * dp), B(c.dev, sizeof(double) * size_t(kp) * kp), dots(c.dev, sizeof(double) * 2);
+    DBuf viol(c.dev, sizeof(double) * 2);   // { the W sweep's violation, the H sweep's }
+    nmf_init_factors(c, dt, n, d, k, kp, dp, sx, w0, h0, seed, W, H);
+    op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
+    // the loss at the start: A = W^T X and B = W^T W from a pass that leaves W alone
+    bool kernel = nmf_cd_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, spec.l1_w, spec.l2_w, 0, A.f64(), B.f64(), nullptr);
+    double hd[2];
+    {
+        std::vector<double> a(size_t(kp) * dp), b(size_t(kp) * kp), h(size_t(kp) * dp), hht;
+        dev_d2h(c.dev, a.data(), A.p, A.bytes);
+        dev_d2h(c.dev, b.data(), B.p, B.bytes);
+        dev_d2h(c.dev, h.data(), H.p, H.bytes);
+        dev_sync(c.dev);
+        nmf_host_gram_dots(a, b, h, kp, dp, hht, hd);
+    }
+    const double err_init = nmf_loss(sx.sumsq, hd);
+    int64_t n_iter = spec.max_iter;
+    double viol_init = 0.0;
+    for (int64_t it = 1; it <= spec.max_iter; ++it) {
+        kernel = nmf_cd_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, spec.l1_w, spec.l2_w, 1, A.f64(), B.f64(), viol.f64()) && kernel;
+        nmf_cd_hupdate_into(c, k, kp, dp, A.f64(), B.f64(), H.f64(), HHt.f64(), spec.l1_h, spec.l2_h, dots.f64(), viol.f64() + 1);
+        if (spec.tol > 0) {   // (tol = 0 queues the whole fit without a host round trip)
+            double hv[2];
+            dev_d2h(c.dev, hv, viol.p, sizeof(hv));
+            dev_sync(c.dev);
+            const double v = hv[0] + hv[1];
+            if (it == 1) viol_init = v;
+            if (viol_init == 0.0 || v / viol_init <= spec.tol) { n_iter = it; break; }
+        }
+    }
+    dev_d2h(c.dev, hd, dots.p, sizeof(hd));
+    dev_sync(c.dev);
+    const double err = nmf_loss(sx.sumsq, hd);
+    if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, kp, *w_out);
+    std::unique_ptr<petal_nmf> h(new petal_nmf());
+    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
+    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = kernel ? 1 : 0; h->err = err; h->err_init = err_init; h->solver = 1;
+    finish_stats(c, timer);
+    h->h = H.f64(); H.p = nullptr;
+    h->hht = HHt.f64(); HHt.p = nullptr;
+    return h.release();
+}
+}  // namespace
+
+petal_nmf* nmf_fit_solver(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, int64_t solver, const petal_matrix* w0,
+                          const petal_matrix* h0, int64_t seed, const petal_matrix* w_out) {
+    if (solver == 0) return nmf_fit(c, x, k, spec, w0, h0, seed, w_out);
+    if (solver != 1) invalid_input("Nmf: unknown solver " + std::to_string(solver) + " (0: multiplicative updates, 1: coordinate descent)");
+    return nmf_cd_fit(c, x, k, spec, w0, h0, seed, w_out);
+}
+
+// transform of a coordinate-descent model: W starts at ZERO and takes exactly max_iter sweeps on the fixed Z; no tolerance stop
+void nmf_cd_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
+    nmf_usable(c, h);
+    const Timer timer = start_fit(c, x);
+    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
+    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    const int64_t m = x.rows;
+    check_output(w_out, h.dtype, m, h.k);
+    if (m == 0) { finish_stats(c, timer); return; }
+    const DevMat X = ingest(c, x);
+    nmf_reject(nmf_scan(c, X));
+    DBuf W(c.dev, sizeof(double) * size_t(m) * h.kp);
+    const bool ran = nmf_cd_pass_into(c, X, h.h, h.hht, h.k, h.kp, W.f64(), true, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr, nullptr);
+    h.last_kernel = ran ? 1 : 0;
+    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, h.kp, w_out);
+    finish_stats(c, timer);
+}
+
+void nmf_cd_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* hh, const NmfSpec& spec, int64_t inner,
+                 bool from_zero, double* w_out, double* a_out, double* b_out, double* violation_out, int64_t* info1) {
+    check_matrix(x, "x");
+    if (info1) info1[0] = 0;
+    if (sharded(c)) invalid_input("nmf_cd_pass: a sharded ctx is not supported in this version");
+    const int64_t n = x.rows, d = x.cols;
+    if (n == 0 || d == 0) invalid_input("nmf_cd_pass: the input has no rows or no columns");
+    if (k < 1) invalid_input("nmf_cd_pass: the number of components should be at least 1");
+    if (inner < 0) invalid_input("negative parameter");
+    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0) || std::isinf(spec.l1_w) || std::isinf(spec.l2_w))
+        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    if ((a_out == nullptr) != (b_out == nullptr)) invalid_input("a_out and b_out should both be given or both be null");
+    const DevMat X = ingest(c, x);
+    nmf_reject(nmf_scan(c, X));
+    const int64_t dp = X.dp, kp = nmf_padded_k(k);
+    std::vector<double> hw(size_t(n) * kp, 0.0), hp(size_t(kp) * dp, 0.0);
+    for (int64_t i = 0; i < n; ++i) std::copy(w_in + i * k, w_in + (i + 1) * k, hw.begin() + i * kp);
+    for (int64_t i = 0; i < k; ++i) std::copy(hh + i * d, hh + (i + 1) * d, hp.begin() + i * dp);
+    // W is formed inside a guard: a row in front and a row behind, every byte 0xFF beforehand.  The guard rows must come back
+    // untouched and the padding columns of W as zeros.
+    DBuf G(c.dev, sizeof(double) * size_t(n + 2) * kp), H(c.dev, sizeof(double) * hp.size()), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
+    DBuf A, B, V;
+    if (a_out) {
+        A = DBuf(c.dev, sizeof(double) * size_t(kp) * dp);
+        B = DBuf(c.dev, sizeof(double) * size_t(kp) * kp);
+    }
+    if (violation_out && inner > 0) V = DBuf(c.dev, sizeof(double) * size_t(inner));
+    double* W = G.f64() + kp;
+    dev_memset(c.dev, G.p, 0xFF, G.bytes);
+    dev_h2d(c.dev, W, hw.data(), sizeof(double) * hw.size());
+    dev_h2d(c.dev, H.p, hp.data(), H.bytes);
+    op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
+    const bool ran = nmf_cd_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W, from_zero && inner > 0, spec.l1_w, spec.l2_w, inner, A.f64(), B.f64(), V.f64());
+    std::vector<double> hg(size_t(n + 2) * kp);
+    dev_d2h(c.dev, hg.data(), G.p, G.bytes);
+    if (V.p) dev_d2h(c.dev, violation_out, V.p, V.bytes);
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < n + 2; ++i)
+        for (int64_t j = 0; j < kp; ++j) {
+            uint64_t bits = 0;
+            std::memcpy(&bits, &hg[size_t(i) * kp + j], 8);
+            const bool guard = i == 0 || i == n + 1;
+            if (guard ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_cd_pass wrote outside the n x k block");
+        }
+    for (int64_t i = 0; i < n; ++i) std::copy(hg.begin() + (i + 1) * kp, hg.begin() + (i + 1) * kp + k, w_out + i * k);
+    if (a_out) {
+        dev_copy2d(c.dev, a_out, sizeof(double) * d, A.p, sizeof(double) * dp, sizeof(double) * d, size_t(k), 1);
+        dev_copy2d(c.dev, b_out, sizeof(double) * k, B.p, sizeof(double) * kp, sizeof(double) * k, size_t(k), 1);
+        dev_sync(c.dev);
+    }
+    if (info1) info1[0] = ran ? 1 : 0;
+}
+
+void nmf_cd_hupdate(petal_ctx& c, int64_t k, int64_t d, const double* a, const double* b, const double* h_in, const NmfSpec& spec, double* h_out,
+                    double* violation_out, int64_t* info1) {
+    if (info1) info1[0] = 0;
+    if (sharded(c)) invalid_input("nmf_cd_hupdate: a sharded ctx is not supported in this version");
+    if (k < 1 || d < 1) invalid_input("nmf_cd_hupdate: k and d should be at least 1");
+    if (!(spec.l1_h >= 0) || !(spec.l2_h >= 0) || std::isinf(spec.l1_h) || std::isinf(spec.l2_h))
+        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    const int64_t kp = nmf_padded_k(k), dp = (d + 15) / 16 * 16;
+    std::vector<double> ha(size_t(kp) * dp, 0.0), hb(size_t(kp) * kp, 0.0), hh(size_t(kp) * dp, 0.0);
+    for (int64_t i = 0; i < k; ++i) {
+        std::copy(a + i * d, a + (i + 1) * d, ha.begin() + i * dp);
+        std::copy(h_in + i * d, h_in + (i + 1) * d, hh.begin() + i * dp);
+        std::copy(b + i * k, b + (i + 1) * k, hb.begin() + i * kp);
+    }
+    DBuf A(c.dev, sizeof(double) * ha.size()), B(c.dev, sizeof(double) * hb.size()), H(c.dev, sizeof(double) * hh.size());
+    DBuf HHt(c.dev, sizeof(double) * size_t(kp) * kp), dv(c.dev, sizeof(double) * 3);
+    dev_h2d(c.dev, A.p, ha.data(), A.bytes);
+    dev_h2d(c.dev, B.p, hb.data(), B.bytes);
+    dev_h2d(c.dev, H.p, hh.data(), H.bytes);
+    const bool ran = nmf_cd_hupdate_into(c, k, kp, dp, A.f64(), B.f64(), H.f64(), HHt.f64(), spec.l1_h, spec.l2_h, dv.f64(), dv.f64() + 2);
+    dev_d2h(c.dev, hh.data(), H.p, H.bytes);
+    double hv[3];
+    dev_d2h(c.dev, hv, dv.p, sizeof(hv));
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < kp; ++i)
+        for (int64_t f = 0; f < dp; ++f)
+            if ((i >= k || f >= d) && hh[size_t(i) * dp + f] != 0.0) device_error("nmf_cd_hupdate wrote a non-zero into the padding of H");
+    for (int64_t i = 0; i < k; ++i) std::copy(hh.begin() + i * dp, hh.begin() + i * dp + d, h_out + i * d);
+    if (violation_out) *violation_out = hv[2];
     if (info1) info1[0] = ran ? 1 : 0;
 }
 

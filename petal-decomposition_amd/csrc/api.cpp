@@ -15,6 +15,7 @@
 #include "../../include/petal_hip_nmf_sparse.h"
 #include "../../include/petal_hip_nmf_kl.h"
 #include "../../include/petal_hip_nmf_kl_dense.h"
+#include "../../include/petal_hip_nmf_cd.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -535,6 +536,45 @@ int petal_nmf_kl_pass(petal_ctx* ctx, const petal_matrix* x, int64_t k, const do
         need(spec, "spec");
         need(w_out, "w_out");
         nmf_kl_pass(*ctx, *x, k, w_in, h, nmf_spec(*spec), inner_iters, w_out, a_out, colsum_out, term_out, info1);
+    });
+}
+
+// ---- include/petal_hip_nmf_cd.h: the coordinate-descent solver on a dense matrix ------------------------------------------------------
+int petal_nmf_fit_solver(petal_ctx* ctx, const petal_matrix* x, int64_t k, const petal_nmf_spec* spec, int64_t solver, const petal_matrix* w0,
+                         const petal_matrix* h0, int64_t seed, petal_nmf** out, const petal_matrix* w_out) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(spec, "spec");
+        need(out, "out");
+        *out = nmf_fit_solver(*ctx, *x, k, nmf_spec(*spec), solver, w0, h0, seed, w_out);
+    });
+}
+int petal_nmf_get_solver(const petal_nmf* h, int64_t* solver) {
+    if (!h || !solver) return PETAL_INVALID_INPUT;
+    *solver = h->solver;
+    return PETAL_OK;
+}
+int petal_nmf_cd_pass(petal_ctx* ctx, const petal_matrix* x, int64_t k, const double* w_in, const double* h, const petal_nmf_spec* spec,
+                      int64_t inner_iters, int from_zero, double* w_out, double* a_out, double* b_out, double* violation_out, int64_t* info1) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(w_in, "w_in");
+        need(h, "h");
+        need(spec, "spec");
+        need(w_out, "w_out");
+        nmf_cd_pass(*ctx, *x, k, w_in, h, nmf_spec(*spec), inner_iters, from_zero != 0, w_out, a_out, b_out, violation_out, info1);
+    });
+}
+int petal_nmf_cd_hupdate(petal_ctx* ctx, int64_t k, int64_t d, const double* a, const double* b, const double* h_in, const petal_nmf_spec* spec,
+                         double* h_out, double* violation_out, int64_t* info1) {
+    return guarded(ctx, [&] {
+        need(a, "a");
+        need(b, "b");
+        need(h_in, "h_in");
+        need(spec, "spec");
+        need(h_out, "h_out");
+        nmf_cd_hupdate(*ctx, k, d, a, b, h_in, nmf_spec(*spec), h_out, violation_out, info1);
     });
 }
 

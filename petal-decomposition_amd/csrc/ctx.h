@@ -88,6 +88,7 @@ struct petal_nmf {
     double l1_w = 0, l2_w = 0;
     int64_t fit_kernel = 0, last_kernel = -1;
     int64_t loss = 0;                    // PETAL_NMF_LOSS_FROBENIUS / PETAL_NMF_LOSS_KL (include/petal_hip_nmf_kl.h)
+    int64_t solver = 0;                  // PETAL_NMF_SOLVER_MU / PETAL_NMF_SOLVER_CD (include/petal_hip_nmf_cd.h)
     double err = 0, err_init = 0;
     double* h = nullptr;                 // device fp64, kp x dp (ld dp): H, zero in the padding
     double* hht = nullptr;               // device fp64, kp x kp: H H^T (zeros in a Kullback-Leibler model, which never reads it)
@@ -217,6 +218,14 @@ petal_nmf* nmf_fit_loss(petal_ctx& c, const petal_matrix& x, int64_t k, const Nm
 void nmf_transform_loss(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out);
 void nmf_kl_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* h, const NmfSpec& spec, int64_t inner,
                  double* w_out, double* a_out, double* colsum_out, double* term_out, int64_t* info1);
+// include/petal_hip_nmf_cd.h: the coordinate-descent solver on a dense matrix
+petal_nmf* nmf_fit_solver(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, int64_t solver, const petal_matrix* w0,
+                          const petal_matrix* h0, int64_t seed, const petal_matrix* w_out);
+void nmf_cd_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out);
+void nmf_cd_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* h, const NmfSpec& spec, int64_t inner,
+                 bool from_zero, double* w_out, double* a_out, double* b_out, double* violation_out, int64_t* info1);
+void nmf_cd_hupdate(petal_ctx& c, int64_t k, int64_t d, const double* a, const double* b, const double* h_in, const NmfSpec& spec, double* h_out,
+                    double* violation_out, int64_t* info1);
 // include/petal_hip_ipca.h: IncrementalPca
 petal_ipca* ipca_create(petal_ctx& c, int64_t d, int32_t dtype, bool centering);
 void ipca_destroy(petal_ipca* h);

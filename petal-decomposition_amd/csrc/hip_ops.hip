@@ -599,4 +599,5 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #include "kernels/k_nmf_csr.inc"   // Nmf on sparse CSR data: the sweep (k_nmf_sweep, k_nmf_sweep_split), G^T G and the loss's dot (k_nmf_gram), k_csr_densify, k_nmf_valscan
 #include "kernels/k_nmf_kl.inc"    // Nmf with the Kullback-Leibler loss on sparse CSR data: the fused gather sweep (k_nmf_kl_sweep, k_nmf_kl_split), colsum(G) and the loss's term (k_nmf_kl_colsum), k_nmf_kl_vsum
 #include "kernels/k_nmf_kl_dense.inc"   // Nmf with the Kullback-Leibler loss on dense data: the fused pass (k_nmf_kl_pass), the H rule and the row sums of H (k_nmf_kl_hrule, k_nmf_kl_rowsum)
+#include "kernels/k_nmf_cd.inc"   // Nmf by coordinate descent: the fused pass with the Gauss-Seidel sweep (k_nmf_cd_pass), the sweep on the rows of H^T (k_nmf_cd_hrule), k_nmf_cd_violsum
 }  // namespace petal

@@ -293,6 +293,17 @@ bool op_nmf_kl_pass(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64
 bool op_nmf_kl_hrule(Dev*, int64_t kp, int64_t dp, const double* A, const double* colsum, double* H, double l1, double l2);
 // out (DEVICE, kp doubles) = the row sums of H (kp x dp, ld dp), a fixed order.
 bool op_nmf_kl_rowsum(Dev*, int64_t kp, int64_t dp, const double* H, double* out);
+// Nmf by coordinate descent (include/petal_hip_nmf_cd.h).  Device layouts are op_nmf_pass's.  The fused pass: Z = X H^T once, then
+// `inner` Gauss-Seidel sweeps of every row of W over its coordinates with S = HHt + l2 I (the first k diagonal entries) and
+// z = Z[i, :] - l1 (W in place; from_zero: W starts as zeros; inner = 0 leaves W alone), then, where A and B are given (both or neither),
+// A = W^T X and B = W^T W with the W just written.  viol (nullable, DEVICE, `inner` doubles): the violation sum |pg| of every sweep, the
+// workgroups' parts added in workgroup order.  X is read once from memory; no atomics.  false, NOTHING done: outside op_nmf_pass's envelope.
+bool op_nmf_cd_pass(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64_t ldx, const double* H, const double* HHt, int64_t k, int64_t kp,
+                    double* W, bool from_zero, double l1, double l2, int64_t inner, double* A, double* B, double* viol);
+// The H side: one sweep of the dp rows of H^T with S = B + l2 I (the first k diagonal entries) and z = A[:, f] - l1, H in place; then
+// HHt = H H^T, dots2 (DEVICE) = { <A, H>, <B, HHt> } and viol1 (DEVICE) = the sweep's violation.  false, NOTHING done: kp not 16, 32 or 64.
+bool op_nmf_cd_hupdate(Dev*, int64_t k, int64_t kp, int64_t dp, const double* A, const double* B, double* H, double* HHt, double l1, double l2,
+                       double* dots2, double* viol1);
 // out (img.rows x cols in dtype, ldo; DEVICE) = the dense image: zeros, then every stored entry added in position order.
 bool op_csr_densify(Dev*, int dtype, const CsrImage& img, void* out, int64_t cols, int64_t ldo);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns

@@ -3,6 +3,7 @@
 //! is float64 inside; outputs are rounded once to `A`.
 use crate::ffi_nmf::{self, PetalNmf, PetalNmfSpec};
 use crate::ffi_nmf_kl;
+use crate::ffi_nmf_cd;
 use crate::ffi_nmf_kl_dense;
 use crate::ffi_nmf_sparse;
 use crate::pca::CsrMatrix;
@@ -38,6 +39,25 @@ pub enum NmfDensePath {
     Fused,
 }
 
+/// The solver of a dense fit (include/petal_hip_nmf_cd.h; source only, unverified like the rest of this crate).
+/// `CoordinateDescent` is scikit-learn's `solver="cd"` (its default, `shuffle=False`) under the Frobenius loss: the stopping rule runs
+/// after every iteration and `transform` starts from W = 0.  It is refused with the Kullback-Leibler loss and with a `CsrMatrix`.
+#[derive(Debug, Clone, Copy, PartialEq, Eq, Default)]
+pub enum NmfSolver {
+    #[default]
+    MultiplicativeUpdate,
+    CoordinateDescent,
+}
+
+impl NmfSolver {
+    fn code(self) -> i64 {
+        match self {
+            NmfSolver::MultiplicativeUpdate => ffi_nmf_cd::PETAL_NMF_SOLVER_MU,
+            NmfSolver::CoordinateDescent => ffi_nmf_cd::PETAL_NMF_SOLVER_CD,
+        }
+    }
+}
+
 /// The parameters of a fit; `alpha_h: None` means the same as `alpha_w` (scikit-learn's "same").  `loss` is read by `fit_csr` and its
 /// siblings; `transform_csr` follows the loss the model was fitted with.
 #[derive(Debug, Clone, Copy, PartialEq)]
@@ -50,10 +70,11 @@ pub struct NmfParams {
     pub l1_ratio: f64,
     pub loss: NmfLoss,
     pub dense_path: NmfDensePath,
+    pub solver: NmfSolver,
 }
 
 impl Default for NmfParams {
-    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0, loss: NmfLoss::Frobenius, dense_path: NmfDensePath::Compress } }
+    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0, loss: NmfLoss::Frobenius, dense_path: NmfDensePath::Compress, solver: NmfSolver::MultiplicativeUpdate } }
 }
 
 /// { n, d, k, iterations run, k_nmf_pass ran in the fit, k_nmf_pass ran in the last transform (-1 before the first) }
@@ -200,6 +221,15 @@ impl<A: HipScalar> Nmf<A> {
         self.kernel_path = path;
         Ok(())
     }
+    /// The solver the fitted model remembers.
+    pub fn model_solver(&self) -> Result<NmfSolver, DecompositionError> {
+        let raw = self.handle()?;
+        let mut v: i64 = 0;
+        if unsafe { ffi_nmf_cd::petal_nmf_get_solver(raw, &mut v) } != 0 {
+            return Err(DecompositionError::InvalidInput("petal_nmf_get_solver failed".into()));
+        }
+        Ok(if v == ffi_nmf_cd::PETAL_NMF_SOLVER_CD { NmfSolver::CoordinateDescent } else { NmfSolver::MultiplicativeUpdate })
+    }
     fn handle(&self) -> Result<*mut PetalNmf, DecompositionError> {
         if self.raw.is_null() {
             return Err(DecompositionError::InvalidInput("the model has not been fitted".into()));
@@ -208,6 +238,11 @@ impl<A: HipScalar> Nmf<A> {
     }
     fn inner_fit<S: Data<Elem = A>>(&mut self, input: &ArrayBase<S, Ix2>, init: Option<(&Array2<A>, &Array2<A>)>, w: Option<&mut Array2<A>>)
         -> Result<(), DecompositionError> {
+        let solver = self.params.solver;
+        let cd = solver == NmfSolver::CoordinateDescent;
+        if cd && self.params.loss != NmfLoss::Frobenius {
+            return Err(DecompositionError::InvalidInput("Nmf: the coordinate-descent solver does not take the kullback-leibler loss".into()));
+        }
         let fused = self.params.loss == NmfLoss::KullbackLeibler && self.params.dense_path == NmfDensePath::Fused;
         if self.params.loss == NmfLoss::KullbackLeibler && !fused {
             return Err(DecompositionError::InvalidInput("Nmf: the kullback-leibler loss takes a CsrMatrix".into()));
@@ -222,7 +257,9 @@ impl<A: HipScalar> Nmf<A> {
             |ctx| unsafe {
                 let (w0, h0) = (iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _), iv.as_ref().map_or(std::ptr::null(), |m| &m.1 as *const _));
                 let wo = wv.as_ref().map_or(std::ptr::null(), |m| m as *const _);
-                if fused {
+                if cd {
+                    ffi_nmf_cd::petal_nmf_fit_solver(ctx, &x, k, &spec, solver.code(), w0, h0, seed, &mut raw, wo)
+                } else if fused {
                     ffi_nmf_kl_dense::petal_nmf_fit_loss(ctx, &x, k, &spec, loss.code(), w0, h0, seed, &mut raw, wo)
                 } else {
                     ffi_nmf::petal_nmf_fit(ctx, &x, k, &spec, w0, h0, seed, &mut raw, wo)
