@@ -7,16 +7,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpetal_hip.so")
 SOURCES = ["hip_ops.hip", "algo.cpp", "api.cpp", "rccl.cpp"]
-HEADERS = ["ops.h", "ctx.h", os.path.join("..", "..", "include", "petal_hip.h"), os.path.join("..", "..", "include", "petal_hip_score.h"),
-           os.path.join("..", "..", "include", "petal_hip_segments.h"),
-           os.path.join("..", "..", "include", "petal_hip_sparse.h"),
-           os.path.join("..", "..", "include", "petal_hip_ipca.h"),
-           os.path.join("..", "..", "include", "petal_hip_wide.h"),
-           os.path.join("..", "..", "include", "petal_hip_kpca.h"),
-           os.path.join("..", "..", "include", "petal_hip_nmf.h"),
-           os.path.join("..", "..", "include", "petal_hip_nmf_sparse.h"),
-           os.path.join("..", "..", "include", "petal_hip_nmf_kl.h"),
-           os.path.join("..", "..", "include", "petal_hip_probe.h")] + \
+INCLUDE = os.path.join(HERE, "..", "include")
+HEADERS = ["ops.h", "ctx.h"] + \
+    [os.path.join("..", "..", "include", f) for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")] + \
     [os.path.join("kernels", f) for f in sorted(os.listdir(os.path.join(CSRC, "kernels"))) if f.endswith(".inc")]   # the parts of hip_ops.hip
 
 

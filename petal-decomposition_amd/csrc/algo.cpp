@@ -439,10 +439,15 @@ void finish_stats(petal_ctx& c, const Timer& t) {
 }
 
 // the start of every fit: the clock, cleared kernel timing and stats, the input's check
-Timer start_fit(petal_ctx& c, const petal_matrix& x) {
+// the clock and the statistics of an entry whose input is no petal_matrix (a CSR handle: csr_usable has looked at it)
+Timer start_unchecked_fit(petal_ctx& c) {
     Timer t;
     dev_reset_timing(c.dev);
     c.stats = petal_stats{};
+    return t;
+}
+Timer start_fit(petal_ctx& c, const petal_matrix& x) {
+    const Timer t = start_unchecked_fit(c);
     check_matrix(x, "input");
     return t;
 }
@@ -1557,6 +1562,10 @@ __attribute__((weak)) bool op_nmf_hupdate(Dev*, int64_t, int64_t, const double*,
 namespace {
 constexpr double NMF_EPS = 1.1920928955078125e-07;            // 2^-23 for both data types
 constexpr int64_t NMF_FALLBACK_BLOCK = int64_t(1) << 22;      // doubles of the widened block of X a composed step holds (32 MiB)
+constexpr int64_t NMF_LOSS_FROBENIUS = 0, NMF_LOSS_KL = 1;
+
+// rows of a block of a composed step over n rows of leading dimension ld
+int64_t nmf_block_rows(int64_t n, int64_t ld) { return std::max<int64_t>(1, std::min(n, NMF_FALLBACK_BLOCK / ld)); }
 
 // rand_pcg::Mcg128Xsl64 + rand_distr::StandardNormal (256-layer Ziggurat): the stream of petal_decomposition.hpp's Pcg and of pcg.py
 class NmfPcg {
@@ -1620,7 +1629,7 @@ NmfScan nmf_scan(petal_ctx& c, const DevMat& X) {
             return r;
         }
     }
-    const int64_t B = std::max<int64_t>(1, std::min(X.n, NMF_FALLBACK_BLOCK / X.ld));
+    const int64_t B = nmf_block_rows(X.n, X.ld);
     const size_t esz = dtype_size(X.dtype);
     DBuf Xb(c.dev, sizeof(double) * size_t((B - 1) * X.ld + X.dp));
     std::vector<double> hx(size_t((B - 1) * X.ld + X.dp));
@@ -1645,6 +1654,33 @@ void nmf_reject(const NmfScan& s) {
     if (s.negative) invalid_input("negative values in data");
 }
 
+// The frame of a composed pass with Z = X H^T (multiplicative updates, coordinate descent): X widened in row blocks of nmf_block_rows
+// rows; per block fill(W_b, b) (a transform's start; else nothing), rule(X_b, W_b, b) (the solver's update of the block of W), and where
+// A is given A += W_b^T X_b and B += W_b^T W_b, added in block order.  sync_blocks: a synchronisation behind every block.  The caller
+// synchronises at the end.
+template <class Fill, class Rule>
+void nmf_composed_pass(petal_ctx& c, const DevMat& X, int64_t kp, double* W, double* A, double* B, Fill fill, Rule rule, bool sync_blocks) {
+    const int64_t n = X.n, dp = X.dp, ld = X.ld, Bk = nmf_block_rows(n, ld);
+    const size_t esz = dtype_size(X.dtype);
+    DBuf Xb(c.dev, sizeof(double) * size_t((Bk - 1) * ld + dp));
+    if (A) {
+        dev_memset(c.dev, A, 0, sizeof(double) * size_t(kp) * dp);
+        dev_memset(c.dev, B, 0, sizeof(double) * size_t(kp) * kp);
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += Bk) {
+        const int64_t b = std::min(Bk, n - r0);
+        double* Wb = W + r0 * kp;
+        op_cvt_to_f64(c.dev, X.dtype, Xb.f64(), static_cast<const char*>(X.p) + size_t(r0) * ld * esz, (b - 1) * ld + dp);
+        fill(Wb, b);
+        rule(Xb.f64(), Wb, b);
+        if (A) {   // the blocks' contributions are added in block order
+            op_dgemm(c.dev, true, false, kp, dp, b, 1.0, Wb, kp, Xb.f64(), ld, 1.0, A, dp);
+            op_dgemm(c.dev, true, false, kp, kp, b, 1.0, Wb, kp, Wb, kp, 1.0, B, kp);
+        }
+        if (sync_blocks) dev_sync(c.dev);
+    }
+}
+
 // The pass (ops.h, op_nmf_pass): the kernel where the layer has it, else the same statement in row blocks.  Returns "k_nmf_pass ran".
 bool nmf_pass_into(petal_ctx& c, const DevMat& X, const double* H, const double* HHt, int64_t k, int64_t kp, double* W, bool from_const,
                    double wconst, double l1, double l2, int64_t inner, double* A, double* B) {
@@ -1656,25 +1692,18 @@ bool nmf_pass_into(petal_ctx& c, const DevMat& X, const double* H, const double*
         dev_set_tag(c.dev, TAG_NONE);
         if (ran) return true;
     }
-    const int64_t Bk = std::max<int64_t>(1, std::min(n, NMF_FALLBACK_BLOCK / ld));
-    const size_t esz = dtype_size(X.dtype);
-    DBuf Xb(c.dev, sizeof(double) * size_t((Bk - 1) * ld + dp)), Z(c.dev, sizeof(double) * size_t(Bk) * kp), D(c.dev, sizeof(double) * size_t(Bk) * kp);
+    const int64_t Bk = nmf_block_rows(n, ld);
+    DBuf Z(c.dev, sizeof(double) * size_t(Bk) * kp), D(c.dev, sizeof(double) * size_t(Bk) * kp);
     std::vector<double> hz(size_t(Bk) * kp), hd(size_t(Bk) * kp), hw(size_t(Bk) * kp);
-    if (A) {
-        dev_memset(c.dev, A, 0, sizeof(double) * size_t(kp) * dp);
-        dev_memset(c.dev, B, 0, sizeof(double) * size_t(kp) * kp);
-    }
-    for (int64_t r0 = 0; r0 < n; r0 += Bk) {
-        const int64_t b = std::min(Bk, n - r0);
-        double* Wb = W + r0 * kp;
-        op_cvt_to_f64(c.dev, X.dtype, Xb.f64(), static_cast<const char*>(X.p) + size_t(r0) * ld * esz, (b - 1) * ld + dp);
-        if (from_const) {
-            for (int64_t i = 0; i < b; ++i)
-                for (int64_t j = 0; j < kp; ++j) hw[size_t(i) * kp + j] = j < k ? wconst : 0.0;
-            dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
-        }
+    const auto fill = [&](double* Wb, int64_t b) {
+        if (!from_const) return;
+        for (int64_t i = 0; i < b; ++i)
+            for (int64_t j = 0; j < kp; ++j) hw[size_t(i) * kp + j] = j < k ? wconst : 0.0;
+        dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
+    };
+    const auto rule = [&](const double* Xb, double* Wb, int64_t b) {
         if (inner > 0) {
-            op_dgemm(c.dev, false, true, b, kp, dp, 1.0, Xb.f64(), ld, H, dp, 0.0, Z.f64(), kp);
+            op_dgemm(c.dev, false, true, b, kp, dp, 1.0, Xb, ld, H, dp, 0.0, Z.f64(), kp);
             dev_d2h(c.dev, hz.data(), Z.p, sizeof(double) * size_t(b) * kp);
         }
         for (int64_t it = 0; it < inner; ++it) {
@@ -1689,11 +1718,8 @@ bool nmf_pass_into(petal_ctx& c, const DevMat& X, const double* H, const double*
             }
             dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
         }
-        if (A) {   // the blocks' contributions are added in block order
-            op_dgemm(c.dev, true, false, kp, dp, b, 1.0, Wb, kp, Xb.f64(), ld, 1.0, A, dp);
-            op_dgemm(c.dev, true, false, kp, kp, b, 1.0, Wb, kp, Wb, kp, 1.0, B, kp);
-        }
-    }
+    };
+    nmf_composed_pass(c, X, kp, W, A, B, fill, rule, /*sync_blocks=*/false);
     dev_sync(c.dev);
     return false;
 }
@@ -1774,6 +1800,17 @@ void nmf_emit_w(petal_ctx& c, int dt, const double* W, int64_t n, int64_t k, int
     op_cvt_from_f64(c.dev, dt, wt.p, W, n * kp);
     emit(c, dt, wt.p, n, k, kp, out);
 }
+// The drawn start of every fit, one stream: avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first (n x k into rows of stride ws),
+// then H0 (k x d) row by row, entry (i, j) at h[i * hrs + j * hcs] -- the dense layout (hrs = dp, hcs = 1) or the sweeps' transposed
+// one (hrs = 1, hcs = ks).  The arrays are zero beforehand.
+void nmf_draw_start(const NmfScan& sx, int64_t n, int64_t d, int64_t k, int64_t seed, double* w, int64_t ws, double* h, int64_t hrs, int64_t hcs) {
+    const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
+    NmfPcg rng(static_cast<uint64_t>(seed));
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < k; ++j) w[i * ws + j] = std::fabs(avg * rng.standard_normal());
+    for (int64_t i = 0; i < k; ++i)
+        for (int64_t j = 0; j < d; ++j) h[i * hrs + j * hcs] = std::fabs(avg * rng.standard_normal());
+}
 // the start of a dense fit: W (n x kp) and H (kp x dp), zero in the padding, from w0 / h0 or drawn
 void nmf_init_factors(petal_ctx& c, int dt, int64_t n, int64_t d, int64_t k, int64_t kp, int64_t dp, const NmfScan& sx, const petal_matrix* w0,
                       const petal_matrix* h0, int64_t seed, DBuf& W, DBuf& H) {
@@ -1785,17 +1822,153 @@ void nmf_init_factors(petal_ctx& c, int dt, int64_t n, int64_t d, int64_t k, int
         op_pad_to_f64(c.dev, dt, H.f64(), kp, dp, H0.p, k, d, H0.ld);
         dev_sync(c.dev);   // (W0 / H0 go back to the pool behind the two kernels)
     } else {
-        // avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first, then H0, both in row-major order
-        const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
-        NmfPcg rng(static_cast<uint64_t>(seed));
         std::vector<double> hw(size_t(n) * kp, 0.0), hh(size_t(kp) * dp, 0.0);
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t j = 0; j < k; ++j) hw[size_t(i) * kp + j] = std::fabs(avg * rng.standard_normal());
-        for (int64_t i = 0; i < k; ++i)
-            for (int64_t j = 0; j < d; ++j) hh[size_t(i) * dp + j] = std::fabs(avg * rng.standard_normal());
+        nmf_draw_start(sx, n, d, k, seed, hw.data(), kp, hh.data(), dp, 1);
         dev_h2d(c.dev, W.p, hw.data(), W.bytes);
         dev_h2d(c.dev, H.p, hh.data(), H.bytes);
     }
+}
+
+// The front of a dense fit (multiplicative updates under either loss, coordinate descent): the checks, X on the device and looked at
+// once, the padded sizes, W (n x kp) and H (kp x dp) at their start.
+struct NmfDenseFit {
+    Timer timer;
+    DevMat X;
+    NmfScan sx;
+    int dt = 0;
+    int64_t n = 0, d = 0, dp = 0, k = 0, kp = 0;
+    DBuf W, H;
+};
+NmfDenseFit nmf_dense_fit_front(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                                int64_t seed, const petal_matrix* w_out) {
+    NmfDenseFit f;
+    f.timer = start_fit(c, x);
+    if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
+    f.dt = x.dtype; f.n = x.rows; f.d = x.cols; f.k = k;
+    nmf_check_fit(f.n, f.d, f.dt, k, spec, w0, h0, w_out);
+    f.X = ingest(c, x);
+    f.sx = nmf_scan(c, f.X);
+    nmf_reject(f.sx);
+    f.dp = f.X.dp; f.kp = nmf_padded_k(k);
+    f.W = DBuf(c.dev, sizeof(double) * size_t(f.n) * f.kp);
+    f.H = DBuf(c.dev, sizeof(double) * size_t(f.kp) * f.dp);
+    nmf_init_factors(c, f.dt, f.n, f.d, k, f.kp, f.dp, f.sx, w0, h0, seed, f.W, f.H);
+    return f;
+}
+// the Frobenius loss at the start of a dense fit, from A = W^T X and B = W^T W of a pass that left W alone
+double nmf_initial_loss_frobenius(petal_ctx& c, const NmfDenseFit& f, const DBuf& A, const DBuf& B) {
+    std::vector<double> a(size_t(f.kp) * f.dp), b(size_t(f.kp) * f.kp), h(size_t(f.kp) * f.dp), hht;
+    double hd[2];
+    dev_d2h(c.dev, a.data(), A.p, A.bytes);
+    dev_d2h(c.dev, b.data(), B.p, B.bytes);
+    dev_d2h(c.dev, h.data(), f.H.p, f.H.bytes);
+    dev_sync(c.dev);
+    nmf_host_gram_dots(a, b, h, f.kp, f.dp, hht, hd);
+    return nmf_loss(f.sx.sumsq, hd);
+}
+
+// The stopping loop of the multiplicative updates: step() is an iteration; with tol > 0 the loss is read at every tenth one (read_loss)
+// and the fit stops where (previous - loss) / err_init < tol; the loss of the last iteration is read if that check has not just read it.
+// tol = 0 reaches the last iteration without a host round trip.
+struct NmfStop { int64_t n_iter; double err; };
+template <class Step, class ReadLoss>
+NmfStop nmf_mu_iterate(const NmfSpec& spec, double err_init, Step step, ReadLoss read_loss) {
+    double err_prev = err_init, err = err_init;
+    int64_t n_iter = spec.max_iter;
+    bool read = false;   // `err` is the loss of the iteration just run
+    for (int64_t it = 1; it <= spec.max_iter; ++it) {
+        step();
+        read = false;
+        if (spec.tol > 0 && it % 10 == 0) {
+            err = read_loss();
+            read = true;
+            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
+            err_prev = err;
+        }
+    }
+    if (!read) err = read_loss();
+    return {n_iter, err};
+}
+
+// The model of a fit: the handle filled, the statistics closed while the fit still owns its buffers, then H and HHt (kp x dp and
+// kp x kp, the dense entries' padding) given to the handle.
+struct NmfDims { int dt; int64_t n, d, dp, k, kp; };
+petal_nmf* nmf_finish_handle(petal_ctx& c, const Timer& timer, const NmfDims& s, const NmfSpec& spec, double err_init, const NmfStop& stop,
+                             bool fit_kernel, int64_t loss, int64_t solver, DBuf& H, DBuf& HHt) {
+    const auto& [dt, n, d, dp, k, kp] = s;
+    std::unique_ptr<petal_nmf> h(new petal_nmf());
+    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = stop.n_iter; h->dtype = dt;
+    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = fit_kernel ? 1 : 0; h->err = stop.err; h->err_init = err_init;
+    h->loss = loss; h->solver = solver;
+    finish_stats(c, timer);
+    h->h = H.f64(); H.p = nullptr;
+    h->hht = HHt.f64(); HHt.p = nullptr;
+    return h.release();
+}
+NmfDims nmf_dims(const NmfDenseFit& f) { return {f.dt, f.n, f.d, f.dp, f.k, f.kp}; }
+
+// The frame of a dense transform: the checks, X on the device and looked at once, W (m x kp) formed by pass(X, w0, W) -- w0 the
+// constant start sqrt(mean(X) / k) -- and rounded once into w_out.  The caller has started the clock (and made its own refusals).
+template <class Pass>
+void nmf_dense_transform(petal_ctx& c, petal_nmf& h, const Timer& timer, const petal_matrix& x, const petal_matrix& w_out, Pass pass) {
+    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
+    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    const int64_t m = x.rows;
+    check_output(w_out, h.dtype, m, h.k);
+    if (m == 0) { finish_stats(c, timer); return; }
+    const DevMat X = ingest(c, x);
+    const NmfScan sx = nmf_scan(c, X);
+    nmf_reject(sx);
+    const double w0 = std::sqrt(sx.sum / (double(m) * double(h.d)) / double(h.k));
+    DBuf W(c.dev, sizeof(double) * size_t(m) * h.kp);
+    h.last_kernel = pass(X, w0, W.f64()) ? 1 : 0;
+    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, h.kp, w_out);
+    finish_stats(c, timer);
+}
+
+// the penalty check of the probe entries
+void nmf_check_penalties(double l1, double l2) {
+    if (!(l1 >= 0) || !(l2 >= 0) || std::isinf(l1) || std::isinf(l2))
+        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+}
+
+// src (rows x cols, ld lds) as the leading block of a zeroed prows x pcols array
+std::vector<double> nmf_padded(const double* src, int64_t lds, int64_t rows, int64_t cols, int64_t prows, int64_t pcols) {
+    std::vector<double> out(size_t(prows) * pcols, 0.0);
+    for (int64_t i = 0; i < rows; ++i) std::copy(src + i * lds, src + i * lds + cols, out.begin() + i * pcols);
+    return out;
+}
+// The guard of the probe entries: a factor (rows x k of the caller) is staged as rows x kp inside `front` rows before it and `back` rows
+// behind it, every byte of the whole block 0xFF beforehand.  After the entry's pass nmf_guard_collect reads the block back (also():
+// the entry's other read-backs, queued in front of the one synchronisation), raises `what` where a guard row was touched or a padding
+// column is not zero, and unpads into dst.
+struct NmfGuarded {
+    DBuf G;
+    int64_t rows, k, kp, front, back;
+    double* block() const { return G.f64() + front * kp; }
+};
+NmfGuarded nmf_guard_stage(petal_ctx& c, const double* src, int64_t rows, int64_t k, int64_t kp, int64_t front, int64_t back) {
+    const std::vector<double> hw = nmf_padded(src, k, rows, k, rows, kp);
+    NmfGuarded g{DBuf(c.dev, sizeof(double) * size_t(front + rows + back) * kp), rows, k, kp, front, back};
+    dev_memset(c.dev, g.G.p, 0xFF, g.G.bytes);
+    dev_h2d(c.dev, g.block(), hw.data(), sizeof(double) * hw.size());
+    return g;
+}
+template <class Also>
+void nmf_guard_collect(petal_ctx& c, const NmfGuarded& g, double* dst, const char* what, Also also) {
+    const int64_t total = g.front + g.rows + g.back;
+    std::vector<double> hg(size_t(total) * g.kp);
+    dev_d2h(c.dev, hg.data(), g.G.p, g.G.bytes);
+    also();
+    dev_sync(c.dev);
+    for (int64_t i = 0; i < total; ++i)
+        for (int64_t j = 0; j < g.kp; ++j) {
+            uint64_t bits = 0;
+            std::memcpy(&bits, &hg[size_t(i) * g.kp + j], 8);
+            const bool guard = i < g.front || i >= g.front + g.rows;
+            if (guard ? bits != ~uint64_t(0) : (j >= g.k && bits != 0)) device_error(what);
+        }
+    for (int64_t i = 0; i < g.rows; ++i) std::copy(hg.begin() + (g.front + i) * g.kp, hg.begin() + (g.front + i) * g.kp + g.k, dst + i * g.k);
 }
 }  // namespace
 
@@ -1808,60 +1981,29 @@ void nmf_destroy(petal_nmf* h) {
 
 petal_nmf* nmf_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
                    int64_t seed, const petal_matrix* w_out) {
-    const Timer timer = start_fit(c, x);
-    if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
-    const int dt = x.dtype;
-    const int64_t n = x.rows, d = x.cols;
-    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
-    const DevMat X = ingest(c, x);
-    const NmfScan sx = nmf_scan(c, X);
-    nmf_reject(sx);
-    const int64_t dp = X.dp, kp = nmf_padded_k(k);
-    DBuf W(c.dev, sizeof(double) * size_t(n) * kp), H(c.dev, sizeof(double) * size_t(kp) * dp), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
+    NmfDenseFit f = nmf_dense_fit_front(c, x, k, spec, w0, h0, seed, w_out);
+    const int64_t dp = f.dp, kp = f.kp;
+    double *W = f.W.f64(), *H = f.H.f64();
+    DBuf HHt(c.dev, sizeof(double) * size_t(kp) * kp);
     DBuf A(c.dev, sizeof(double) * size_t(kp) * dp), B(c.dev, sizeof(double) * size_t(kp) * kp), dots(c.dev, sizeof(double) * 2);
-    nmf_init_factors(c, dt, n, d, k, kp, dp, sx, w0, h0, seed, W, H);
-    op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
+    op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H, dp, H, dp, 0.0, HHt.f64(), kp);
     // the loss at the start: A = W^T X and B = W^T W from a pass that leaves W alone
-    bool kernel = nmf_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 0, A.f64(), B.f64());
-    double hd[2];
-    {
-        std::vector<double> a(size_t(kp) * dp), b(size_t(kp) * kp), h(size_t(kp) * dp), hht;
-        dev_d2h(c.dev, a.data(), A.p, A.bytes);
-        dev_d2h(c.dev, b.data(), B.p, B.bytes);
-        dev_d2h(c.dev, h.data(), H.p, H.bytes);
-        dev_sync(c.dev);
-        nmf_host_gram_dots(a, b, h, kp, dp, hht, hd);
-    }
-    const double err_init = nmf_loss(sx.sumsq, hd);
-    double err_prev = err_init, err = err_init;
-    int64_t n_iter = spec.max_iter;
-    bool read = false;   // `err` is the loss of the iteration just run
-    for (int64_t it = 1; it <= spec.max_iter; ++it) {
-        kernel = nmf_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 1, A.f64(), B.f64()) && kernel;
-        nmf_hupdate_into(c, kp, dp, A.f64(), B.f64(), H.f64(), HHt.f64(), spec.l1_h, spec.l2_h, dots.f64());
-        read = false;
-        if (spec.tol > 0 && it % 10 == 0) {
+    bool kernel = nmf_pass_into(c, f.X, H, HHt.f64(), k, kp, W, false, 0.0, spec.l1_w, spec.l2_w, 0, A.f64(), B.f64());
+    const double err_init = nmf_initial_loss_frobenius(c, f, A, B);
+    const NmfStop stop = nmf_mu_iterate(
+        spec, err_init,
+        [&]() {
+            kernel = nmf_pass_into(c, f.X, H, HHt.f64(), k, kp, W, false, 0.0, spec.l1_w, spec.l2_w, 1, A.f64(), B.f64()) && kernel;
+            nmf_hupdate_into(c, kp, dp, A.f64(), B.f64(), H, HHt.f64(), spec.l1_h, spec.l2_h, dots.f64());
+        },
+        [&]() {   // the H side left the loss's two inner products on the device
+            double hd[2];
             dev_d2h(c.dev, hd, dots.p, sizeof(hd));
             dev_sync(c.dev);
-            err = nmf_loss(sx.sumsq, hd);
-            read = true;
-            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
-            err_prev = err;
-        }
-    }
-    if (!read) {
-        dev_d2h(c.dev, hd, dots.p, sizeof(hd));
-        dev_sync(c.dev);
-        err = nmf_loss(sx.sumsq, hd);
-    }
-    if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, kp, *w_out);
-    std::unique_ptr<petal_nmf> h(new petal_nmf());
-    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
-    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = kernel ? 1 : 0; h->err = err; h->err_init = err_init;
-    finish_stats(c, timer);
-    h->h = H.f64(); H.p = nullptr;
-    h->hht = HHt.f64(); HHt.p = nullptr;
-    return h.release();
+            return nmf_loss(f.sx.sumsq, hd);
+        });
+    if (w_out) nmf_emit_w(c, f.dt, W, f.n, k, kp, *w_out);
+    return nmf_finish_handle(c, f.timer, nmf_dims(f), spec, err_init, stop, kernel, NMF_LOSS_FROBENIUS, 0, f.H, HHt);
 }
 
 void nmf_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
@@ -1869,21 +2011,11 @@ void nmf_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const peta
     if (h.solver != 0) { nmf_cd_transform(c, h, x, w_out); return; }   // a coordinate-descent model (include/petal_hip_nmf_cd.h)
     if (h.loss != 0)
         invalid_input("Nmf: the dense transform does not take a kullback-leibler model (petal_nmf_transform_csr does: compress the rows to CSR)");
+    // (of the three dense transforms the Kullback-Leibler one alone refuses a sharded ctx, before the frame: nmf_kl_transform)
     const Timer timer = start_fit(c, x);
-    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
-    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
-    const int64_t m = x.rows;
-    check_output(w_out, h.dtype, m, h.k);
-    if (m == 0) { finish_stats(c, timer); return; }
-    const DevMat X = ingest(c, x);
-    const NmfScan sx = nmf_scan(c, X);
-    nmf_reject(sx);
-    const double w0 = std::sqrt(sx.sum / (double(m) * double(h.d)) / double(h.k));
-    DBuf W(c.dev, sizeof(double) * size_t(m) * h.kp);
-    const bool ran = nmf_pass_into(c, X, h.h, h.hht, h.k, h.kp, W.f64(), true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr);
-    h.last_kernel = ran ? 1 : 0;
-    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, h.kp, w_out);
-    finish_stats(c, timer);
+    nmf_dense_transform(c, h, timer, x, w_out, [&](const DevMat& X, double w0, double* W) {
+        return nmf_pass_into(c, X, h.h, h.hht, h.k, h.kp, W, true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr);
+    });
 }
 
 void nmf_inverse_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& w, const petal_matrix& x_out) {
@@ -1897,7 +2029,7 @@ void nmf_inverse_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& w, co
     const DevMat Wm = ingest(c, w);
     const size_t esz = dtype_size(h.dtype);
     // W H in row blocks of bounded size: the fp64 product of a block is rounded once into the output's own dtype
-    const int64_t Bk = std::max<int64_t>(1, std::min(m, NMF_FALLBACK_BLOCK / dp));
+    const int64_t Bk = nmf_block_rows(m, dp);
     DBuf Wd(c.dev, sizeof(double) * size_t(Bk) * kp), Xd(c.dev, sizeof(double) * size_t(Bk) * dp), Xt(c.dev, esz * size_t(m) * dp);
     for (int64_t r0 = 0; r0 < m; r0 += Bk) {
         const int64_t b = std::min(Bk, m - r0);
@@ -1931,39 +2063,24 @@ void nmf_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in
     if (n == 0 || d == 0) invalid_input("nmf_pass: the input has no rows or no columns");
     if (k < 1) invalid_input("nmf_pass: the number of components should be at least 1");
     if (inner < 0) invalid_input("negative parameter");
+    // (laxer than nmf_check_penalties, which the four later probe entries call: an infinite penalty passes here, as it always has)
     if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0)) invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
     if ((a_out == nullptr) != (b_out == nullptr)) invalid_input("a_out and b_out should both be given or both be null");
     const DevMat X = ingest(c, x);
     nmf_reject(nmf_scan(c, X));
     const int64_t dp = X.dp, kp = nmf_padded_k(k);
-    std::vector<double> hw(size_t(n) * kp, 0.0), hp(size_t(kp) * dp, 0.0);
-    for (int64_t i = 0; i < n; ++i) std::copy(w_in + i * k, w_in + (i + 1) * k, hw.begin() + i * kp);
-    for (int64_t i = 0; i < k; ++i) std::copy(hh + i * d, hh + (i + 1) * d, hp.begin() + i * dp);
-    // W is formed inside a guard: a row in front and a row behind, every byte 0xFF beforehand.  The guard rows must come back
-    // untouched and the padding columns of W as zeros.
-    DBuf G(c.dev, sizeof(double) * size_t(n + 2) * kp), H(c.dev, sizeof(double) * hp.size()), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
+    const std::vector<double> hp = nmf_padded(hh, d, k, d, kp, dp);
+    const NmfGuarded G = nmf_guard_stage(c, w_in, n, k, kp, 1, 1);   // W between two guard rows
+    DBuf H(c.dev, sizeof(double) * hp.size()), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
     DBuf A, B;
     if (a_out) {
         A = DBuf(c.dev, sizeof(double) * size_t(kp) * dp);
         B = DBuf(c.dev, sizeof(double) * size_t(kp) * kp);
     }
-    double* W = G.f64() + kp;
-    dev_memset(c.dev, G.p, 0xFF, G.bytes);
-    dev_h2d(c.dev, W, hw.data(), sizeof(double) * hw.size());
     dev_h2d(c.dev, H.p, hp.data(), H.bytes);
     op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
-    const bool ran = nmf_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W, false, 0.0, spec.l1_w, spec.l2_w, inner, A.f64(), B.f64());
-    std::vector<double> hg(size_t(n + 2) * kp);
-    dev_d2h(c.dev, hg.data(), G.p, G.bytes);
-    dev_sync(c.dev);
-    for (int64_t i = 0; i < n + 2; ++i)
-        for (int64_t j = 0; j < kp; ++j) {
-            uint64_t bits = 0;
-            std::memcpy(&bits, &hg[size_t(i) * kp + j], 8);
-            const bool guard = i == 0 || i == n + 1;
-            if (guard ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_pass wrote outside the n x k block");
-        }
-    for (int64_t i = 0; i < n; ++i) std::copy(hg.begin() + (i + 1) * kp, hg.begin() + (i + 1) * kp + k, w_out + i * k);
+    const bool ran = nmf_pass_into(c, X, H.f64(), HHt.f64(), k, kp, G.block(), false, 0.0, spec.l1_w, spec.l2_w, inner, A.f64(), B.f64());
+    nmf_guard_collect(c, G, w_out, "nmf_pass wrote outside the n x k block", [] {});
     if (a_out) {
         dev_copy2d(c.dev, a_out, sizeof(double) * d, A.p, sizeof(double) * dp, sizeof(double) * d, size_t(k), 1);
         dev_copy2d(c.dev, b_out, sizeof(double) * k, B.p, sizeof(double) * kp, sizeof(double) * k, size_t(k), 1);
@@ -3644,6 +3761,13 @@ void nmf_transpose_in(const double* src, int64_t lds, int64_t k, int64_t cols, i
     for (int64_t i = 0; i < k; ++i)
         for (int64_t j = 0; j < cols; ++j) dst[size_t(j) * ks + i] = src[size_t(i) * lds + j];
 }
+// the reverse for a model's handle: H (kp x dp, zero padded) from a sweep's H^T (d x ks), k leading columns
+std::vector<double> nmf_transpose_out(const std::vector<double>& hht, int64_t d, int64_t ks, int64_t k, int64_t kp, int64_t dp) {
+    std::vector<double> hd(size_t(kp) * dp, 0.0);
+    for (int64_t i = 0; i < k; ++i)
+        for (int64_t j = 0; j < d; ++j) hd[size_t(i) * dp + j] = hht[size_t(j) * ks + i];
+    return hd;
+}
 
 // one sweep under the hot-kernel tag; a layer that refuses here has refused nothing else
 void nmf_sweep_into(petal_ctx& c, const petal_csr& x, int t, int64_t k, int64_t ks, const double* F, double* G, const double* S, bool from_const,
@@ -3670,9 +3794,7 @@ petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpe
         nmf_csr_densify(c, x, dense);
         return nmf_fit(c, dense.m, k, spec, w0, h0, seed, w_out);
     }
-    const Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
+    const Timer timer = start_unchecked_fit(c);
     const int64_t ks = nmf_csr_padded_k(k), kk1 = ks * ks + 1;
     DBuf W(c.dev, sizeof(double) * size_t(n) * ks), Ht(c.dev, sizeof(double) * size_t(d) * ks);
     DBuf B(c.dev, sizeof(double) * size_t(kk1)), HHt(c.dev, sizeof(double) * size_t(kk1));   // each: the Gram matrix, then the sweep's dot
@@ -3689,15 +3811,9 @@ petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpe
         dev_sync(c.dev);   // (W0 / H0 go back to the pool behind the kernels)
         nmf_transpose_in(hh.data(), d, k, d, ks, hht);
     } else {
-        // avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first, then H0, both in row-major order (nmf_fit's stream)
-        const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
-        NmfPcg rng(static_cast<uint64_t>(seed));
         std::vector<double> hw(size_t(n) * ks, 0.0);
         hht.assign(size_t(d) * ks, 0.0);
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t j = 0; j < k; ++j) hw[size_t(i) * ks + j] = std::fabs(avg * rng.standard_normal());
-        for (int64_t i = 0; i < k; ++i)
-            for (int64_t j = 0; j < d; ++j) hht[size_t(j) * ks + i] = std::fabs(avg * rng.standard_normal());
+        nmf_draw_start(sx, n, d, k, seed, hw.data(), ks, hht.data(), 1, ks);   // (nmf_fit's stream, H written transposed)
         dev_h2d(c.dev, W.p, hw.data(), W.bytes);
     }
     dev_h2d(c.dev, Ht.p, hht.data(), Ht.bytes);
@@ -3715,42 +3831,25 @@ petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpe
     if (!op_nmf_gram(c.dev, W.f64(), n, ks, nullptr, B.f64())) device_error("Nmf: the device-op layer refused the Gram product");
     nmf_sweep_into(c, x, 1, k, ks, W.f64(), Ht.f64(), B.f64(), false, 0.0, spec.l1_h, spec.l2_h, 0, HHt.f64());
     const double err_init = read_loss();
-    double err_prev = err_init, err = err_init;
-    int64_t n_iter = spec.max_iter;
-    bool read = false;   // `err` is the loss of the iteration just run
-    for (int64_t it = 1; it <= spec.max_iter; ++it) {
-        nmf_sweep_into(c, x, 0, k, ks, Ht.f64(), W.f64(), HHt.f64(), false, 0.0, spec.l1_w, spec.l2_w, 1, B.f64());
-        nmf_sweep_into(c, x, 1, k, ks, W.f64(), Ht.f64(), B.f64(), false, 0.0, spec.l1_h, spec.l2_h, 1, HHt.f64());
-        read = false;
-        if (spec.tol > 0 && it % 10 == 0) {
-            err = read_loss();
-            read = true;
-            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
-            err_prev = err;
-        }
-    }
-    if (!read) err = read_loss();
+    const NmfStop stop = nmf_mu_iterate(
+        spec, err_init,
+        [&]() {
+            nmf_sweep_into(c, x, 0, k, ks, Ht.f64(), W.f64(), HHt.f64(), false, 0.0, spec.l1_w, spec.l2_w, 1, B.f64());
+            nmf_sweep_into(c, x, 1, k, ks, W.f64(), Ht.f64(), B.f64(), false, 0.0, spec.l1_h, spec.l2_h, 1, HHt.f64());
+        },
+        read_loss);
     if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, ks, *w_out);
     // the handle is an ordinary petal_nmf: H as kp x dp and H H^T as kp x kp in the dense entries' padding
     const int64_t kp = nmf_padded_k(k), dp = round_up(d, 16);
     dev_d2h(c.dev, hht.data(), Ht.p, Ht.bytes);
     dev_sync(c.dev);
-    std::vector<double> hd(size_t(kp) * dp, 0.0), hg(size_t(kp) * kp, 0.0);
-    for (int64_t i = 0; i < k; ++i) {
-        for (int64_t j = 0; j < d; ++j) hd[size_t(i) * dp + j] = hht[size_t(j) * ks + i];
-        for (int64_t j = 0; j < k; ++j) hg[size_t(i) * kp + j] = hh2[size_t(i) * ks + j];
-    }
+    const std::vector<double> hd = nmf_transpose_out(hht, d, ks, k, kp, dp), hg = nmf_padded(hh2.data(), ks, k, k, kp, kp);
     DBuf H(c.dev, sizeof(double) * hd.size()), G(c.dev, sizeof(double) * hg.size());
     dev_h2d(c.dev, H.p, hd.data(), H.bytes);
     dev_h2d(c.dev, G.p, hg.data(), G.bytes);
-    std::unique_ptr<petal_nmf> h(new petal_nmf());
-    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
-    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = 1; h->err = err; h->err_init = err_init;
-    finish_stats(c, timer);
-    h->h = H.f64(); H.p = nullptr;
-    h->hht = G.f64(); G.p = nullptr;
+    petal_nmf* h = nmf_finish_handle(c, timer, {dt, n, d, dp, k, kp}, spec, err_init, stop, true, NMF_LOSS_FROBENIUS, 0, H, G);
     if (kernel_path) *kernel_path = 1;
-    return h.release();
+    return h;
 }
 
 void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, int64_t* kernel_path) {
@@ -3775,18 +3874,15 @@ void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const pet
         return;
     }
     if (m == 0) return;
-    const Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
+    const Timer timer = start_unchecked_fit(c);
     // H^T and H H^T in the sweep's padding, from the model's own blocks (a dense fit's among them)
     const int64_t ks = nmf_csr_padded_k(h.k);
-    std::vector<double> hd(size_t(h.kp) * h.dp), hg(size_t(h.kp) * h.kp), hht, hs(size_t(ks) * ks, 0.0);
+    std::vector<double> hd(size_t(h.kp) * h.dp), hg(size_t(h.kp) * h.kp), hht;
     dev_d2h(c.dev, hd.data(), h.h, sizeof(double) * hd.size());
     dev_d2h(c.dev, hg.data(), h.hht, sizeof(double) * hg.size());
     dev_sync(c.dev);
     nmf_transpose_in(hd.data(), h.dp, h.k, h.d, ks, hht);
-    for (int64_t i = 0; i < h.k; ++i)
-        for (int64_t j = 0; j < h.k; ++j) hs[size_t(i) * ks + j] = hg[size_t(i) * h.kp + j];
+    const std::vector<double> hs = nmf_padded(hg.data(), h.kp, h.k, h.k, ks, ks);
     DBuf Ht(c.dev, sizeof(double) * hht.size()), S(c.dev, sizeof(double) * hs.size()), W(c.dev, sizeof(double) * size_t(m) * ks);
     dev_h2d(c.dev, Ht.p, hht.data(), Ht.bytes);
     dev_h2d(c.dev, S.p, hs.data(), S.bytes);
@@ -3804,8 +3900,7 @@ void nmf_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k,
     if (info1) info1[0] = 0;
     if (k < 1) invalid_input("nmf_sweep: the number of components should be at least 1");
     if (inner < 0) invalid_input("negative parameter");
-    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0) || std::isinf(spec.l1_w) || std::isinf(spec.l2_w))
-        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    nmf_check_penalties(spec.l1_w, spec.l2_w);
     if (dot_out && !gram_out) invalid_input("dot_out comes with gram_out or not at all");
     const int t = transposed ? 1 : 0, dt = x.dtype;
     const int64_t R = transposed ? x.cols : x.rows, C = transposed ? x.rows : x.cols;
@@ -3848,30 +3943,18 @@ void nmf_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k,
     if (k > 64) invalid_input("nmf_sweep: the sparse kernel takes at most 64 components");
     if (R == 0) { if (gram_out) std::fill(gram_out, gram_out + k * k, 0.0); if (dot_out) *dot_out = 0.0; return; }
     const int64_t ks = nmf_csr_padded_k(k), kk1 = ks * ks + 1;
-    std::vector<double> hg(size_t(R) * ks, 0.0), hf(size_t(std::max<int64_t>(C, 1)) * ks, 0.0);
-    for (int64_t i = 0; i < R; ++i) std::copy(g_in + i * k, g_in + (i + 1) * k, hg.begin() + i * ks);
-    for (int64_t i = 0; i < C; ++i) std::copy(f + i * k, f + (i + 1) * k, hf.begin() + i * ks);
-    // G is formed inside a guard: one row more, every byte 0xFF beforehand.  The guard row must come back untouched and the padding
-    // columns of G as zeros.
-    DBuf Gd(c.dev, sizeof(double) * size_t(R + 1) * ks), F(c.dev, sizeof(double) * hf.size()), S(c.dev, sizeof(double) * size_t(kk1)), GD;
+    const std::vector<double> hf = nmf_padded(f, k, C, k, std::max<int64_t>(C, 1), ks);
+    const NmfGuarded Gd = nmf_guard_stage(c, g_in, R, k, ks, 0, 1);   // G with one guard row behind it
+    DBuf F(c.dev, sizeof(double) * hf.size()), S(c.dev, sizeof(double) * size_t(kk1)), GD;
     if (gram_out) GD = DBuf(c.dev, sizeof(double) * size_t(kk1));
-    dev_memset(c.dev, Gd.p, 0xFF, Gd.bytes);
-    dev_h2d(c.dev, Gd.p, hg.data(), sizeof(double) * hg.size());
     dev_h2d(c.dev, F.p, hf.data(), F.bytes);
     if (C == 0) dev_memset(c.dev, S.p, 0, S.bytes);
     else if (!op_nmf_gram(c.dev, F.f64(), C, ks, nullptr, S.f64())) device_error("Nmf: the device-op layer refused the Gram product");
-    nmf_sweep_into(c, x, t, k, ks, F.f64(), Gd.f64(), S.f64(), false, 0.0, l1, l2, inner, gram_out ? GD.f64() : nullptr);
-    std::vector<double> back(size_t(R + 1) * ks), hgd(gram_out ? size_t(kk1) : 0);
-    dev_d2h(c.dev, back.data(), Gd.p, Gd.bytes);
-    if (gram_out) dev_d2h(c.dev, hgd.data(), GD.p, GD.bytes);
-    dev_sync(c.dev);
-    for (int64_t i = 0; i <= R; ++i)
-        for (int64_t j = 0; j < ks; ++j) {
-            uint64_t bits = 0;
-            std::memcpy(&bits, &back[size_t(i) * ks + j], 8);
-            if (i == R ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_sweep wrote outside the R x k block");
-        }
-    for (int64_t i = 0; i < R; ++i) std::copy(back.begin() + i * ks, back.begin() + i * ks + k, g_out + i * k);
+    nmf_sweep_into(c, x, t, k, ks, F.f64(), Gd.block(), S.f64(), false, 0.0, l1, l2, inner, gram_out ? GD.f64() : nullptr);
+    std::vector<double> hgd(gram_out ? size_t(kk1) : 0);
+    nmf_guard_collect(c, Gd, g_out, "nmf_sweep wrote outside the R x k block", [&] {
+        if (gram_out) dev_d2h(c.dev, hgd.data(), GD.p, GD.bytes);
+    });
     if (gram_out)
         for (int64_t i = 0; i < k; ++i) std::copy(hgd.begin() + i * ks, hgd.begin() + i * ks + k, gram_out + i * k);
     if (dot_out) *dot_out = hgd[size_t(ks * ks)];
@@ -3893,8 +3976,6 @@ __attribute__((weak)) bool op_nmf_kl_colsum(Dev*, const double*, int64_t, int64_
 __attribute__((weak)) bool op_nmf_kl_vsum(Dev*, int, const void*, int64_t, double*) { return false; }
 
 namespace {
-constexpr int64_t NMF_LOSS_FROBENIUS = 0, NMF_LOSS_KL = 1;
-
 // an image on the host, values widened
 struct KlHostImage {
     int64_t rows = 0;
@@ -4088,24 +4169,16 @@ petal_nmf* nmf_kl_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const Nmf
     if (k > 64) invalid_input("Nmf: kullback-leibler takes at most 64 components");
     const NmfScan sx = nmf_csr_scan(c, x);
     nmf_reject(sx);
-    const Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
+    const Timer timer = start_unchecked_fit(c);
     KlEngine e(c, x, k);
     const int64_t ks = e.ks;
     std::vector<double> hw(size_t(n) * ks, 0.0), hht(size_t(d) * ks, 0.0);
     if (w0) {
         const std::vector<double> w = kl_to_host(c, dt, *w0, n, k), hh = kl_to_host(c, dt, *h0, k, d);
-        for (int64_t i = 0; i < n; ++i) std::copy(w.begin() + i * k, w.begin() + (i + 1) * k, hw.begin() + i * ks);
+        hw = nmf_padded(w.data(), k, n, k, n, ks);
         nmf_transpose_in(hh.data(), d, k, d, ks, hht);
     } else {
-        // avg = sqrt(mean(X) / k); W0 = |avg N(0,1)| drawn first, then H0, both in row-major order (nmf_fit's stream)
-        const double avg = std::sqrt(sx.sum / (double(n) * double(d)) / double(k));
-        NmfPcg rng(static_cast<uint64_t>(seed));
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t j = 0; j < k; ++j) hw[size_t(i) * ks + j] = std::fabs(avg * rng.standard_normal());
-        for (int64_t i = 0; i < k; ++i)
-            for (int64_t j = 0; j < d; ++j) hht[size_t(j) * ks + i] = std::fabs(avg * rng.standard_normal());
+        nmf_draw_start(sx, n, d, k, seed, hw.data(), ks, hht.data(), 1, ks);   // (nmf_fit's stream, H written transposed)
     }
     KlBuf W = e.make(n * ks), Ht = e.make(d * ks), cW = e.make(ks + 1), cH = e.make(ks + 1), L = e.make(ks + 1);
     e.upload(W, hw.data(), n * ks);
@@ -4123,49 +4196,32 @@ petal_nmf* nmf_kl_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const Nmf
     };
     e.colsum(Ht, d, cH);
     const double err_init = read_loss();
-    double err_prev = err_init, err = err_init;
-    int64_t n_iter = spec.max_iter;
-    bool read = false;   // `err` is the loss of the iteration just run
-    for (int64_t it = 1; it <= spec.max_iter; ++it) {
-        e.sweep(0, Ht, W, cH, false, 0.0, spec.l1_w, spec.l2_w, 1, &cW);
-        e.sweep(1, W, Ht, cW, false, 0.0, spec.l1_h, spec.l2_h, 1, &cH);
-        read = false;
-        if (spec.tol > 0 && it % 10 == 0) {
-            err = read_loss();
-            read = true;
-            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
-            err_prev = err;
-        }
-    }
-    if (!read) err = read_loss();
+    const NmfStop stop = nmf_mu_iterate(
+        spec, err_init,
+        [&]() {
+            e.sweep(0, Ht, W, cH, false, 0.0, spec.l1_w, spec.l2_w, 1, &cW);
+            e.sweep(1, W, Ht, cW, false, 0.0, spec.l1_h, spec.l2_h, 1, &cH);
+        },
+        read_loss);
     if (w_out) kl_emit_w(c, e, dt, W, n, *w_out);
     // the handle is an ordinary petal_nmf: H as kp x dp in the dense entries' padding (H H^T, which this loss never reads, as zeros)
     const int64_t kp = nmf_padded_k(k), dp = round_up(d, 16);
     e.download(Ht, hht.data(), d * ks);
-    std::vector<double> hd(size_t(kp) * dp, 0.0);
-    for (int64_t i = 0; i < k; ++i)
-        for (int64_t j = 0; j < d; ++j) hd[size_t(i) * dp + j] = hht[size_t(j) * ks + i];
+    const std::vector<double> hd = nmf_transpose_out(hht, d, ks, k, kp, dp);
     DBuf H(c.dev, sizeof(double) * hd.size()), G(c.dev, sizeof(double) * size_t(kp) * kp);
     dev_h2d(c.dev, H.p, hd.data(), H.bytes);
     dev_memset(c.dev, G.p, 0, G.bytes);
     dev_sync(c.dev);
-    std::unique_ptr<petal_nmf> h(new petal_nmf());
-    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
-    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = e.device ? 1 : 0; h->err = err; h->err_init = err_init; h->loss = NMF_LOSS_KL;
-    finish_stats(c, timer);
-    h->h = H.f64(); H.p = nullptr;
-    h->hht = G.f64(); G.p = nullptr;
+    petal_nmf* h = nmf_finish_handle(c, timer, {dt, n, d, dp, k, kp}, spec, err_init, stop, e.device, NMF_LOSS_KL, 0, H, G);
     if (kernel_path) *kernel_path = e.device ? 1 : 0;
-    return h.release();
+    return h;
 }
 
 // transform of a Kullback-Leibler model: W starts at the constant sqrt(mean(Xq) / k) and takes exactly max_iter updates with H fixed
 void nmf_kl_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, const NmfScan& sx, int64_t* kernel_path) {
     const int64_t m = x.rows;
     if (m == 0) return;
-    const Timer timer;
-    dev_reset_timing(c.dev);
-    c.stats = petal_stats{};
+    const Timer timer = start_unchecked_fit(c);
     KlEngine e(c, x, h.k);
     const int64_t ks = e.ks;
     std::vector<double> hd(size_t(h.kp) * h.dp), hht;
@@ -4198,8 +4254,7 @@ void nmf_kl_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t
     if (info1) info1[0] = 0;
     if (k < 1) invalid_input("nmf_kl_sweep: the number of components should be at least 1");
     if (inner < 0) invalid_input("negative parameter");
-    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0) || std::isinf(spec.l1_w) || std::isinf(spec.l2_w))
-        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    nmf_check_penalties(spec.l1_w, spec.l2_w);
     if (term_out && inner != 0) invalid_input("term_out comes with inner_iters = 0 only");
     const int t = transposed ? 1 : 0;
     const int64_t R = transposed ? x.cols : x.rows, C = transposed ? x.rows : x.cols;
@@ -4218,33 +4273,18 @@ void nmf_kl_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t
     if (k > 64) invalid_input("nmf_kl_sweep: kullback-leibler takes at most 64 components");
     if (R == 0) { if (colsum_out) std::fill(colsum_out, colsum_out + k, 0.0); if (term_out) *term_out = 0.0; return; }
     const int64_t ks = nmf_csr_padded_k(k);
-    std::vector<double> hg(size_t(R) * ks, 0.0), hf(size_t(std::max<int64_t>(C, 1)) * ks, 0.0);
-    for (int64_t i = 0; i < R; ++i) std::copy(g_in + i * k, g_in + (i + 1) * k, hg.begin() + i * ks);
-    for (int64_t i = 0; i < C; ++i) std::copy(f + i * k, f + (i + 1) * k, hf.begin() + i * ks);
-    // G is formed inside a guard: one row more, every byte 0xFF beforehand.  The guard row must come back untouched and the padding
-    // columns of G as zeros.
-    DBuf Gd(c.dev, sizeof(double) * size_t(R + 1) * ks), F(c.dev, sizeof(double) * hf.size()), cF(c.dev, sizeof(double) * size_t(ks + 1)),
-        CT(c.dev, sizeof(double) * size_t(ks + 1));
-    dev_memset(c.dev, Gd.p, 0xFF, Gd.bytes);
-    dev_h2d(c.dev, Gd.p, hg.data(), sizeof(double) * hg.size());
+    const std::vector<double> hf = nmf_padded(f, k, C, k, std::max<int64_t>(C, 1), ks);
+    const NmfGuarded Gd = nmf_guard_stage(c, g_in, R, k, ks, 0, 1);   // G with one guard row behind it
+    DBuf F(c.dev, sizeof(double) * hf.size()), cF(c.dev, sizeof(double) * size_t(ks + 1)), CT(c.dev, sizeof(double) * size_t(ks + 1));
     dev_h2d(c.dev, F.p, hf.data(), F.bytes);
     if (C == 0) dev_memset(c.dev, cF.p, 0, cF.bytes);
     else if (!op_nmf_kl_colsum(c.dev, F.f64(), C, ks, nullptr, cF.f64())) device_error("Nmf: the device-op layer refused the column sums");
     dev_set_tag(c.dev, TAG_POW);
-    const bool ran = op_nmf_kl_sweep_csr(c.dev, x.dtype, x.dev[t], k, ks, F.f64(), Gd.f64(), cF.f64(), false, 0.0, l1, l2, inner, CT.f64());
+    const bool ran = op_nmf_kl_sweep_csr(c.dev, x.dtype, x.dev[t], k, ks, F.f64(), Gd.block(), cF.f64(), false, 0.0, l1, l2, inner, CT.f64());
     dev_set_tag(c.dev, TAG_NONE);
     if (!ran) device_error("Nmf: the device-op layer refused the Kullback-Leibler sweep");
-    std::vector<double> back(size_t(R + 1) * ks), hct(size_t(ks) + 1);
-    dev_d2h(c.dev, back.data(), Gd.p, Gd.bytes);
-    dev_d2h(c.dev, hct.data(), CT.p, CT.bytes);
-    dev_sync(c.dev);
-    for (int64_t i = 0; i <= R; ++i)
-        for (int64_t j = 0; j < ks; ++j) {
-            uint64_t bits = 0;
-            std::memcpy(&bits, &back[size_t(i) * ks + j], 8);
-            if (i == R ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_kl_sweep wrote outside the R x k block");
-        }
-    for (int64_t i = 0; i < R; ++i) std::copy(back.begin() + i * ks, back.begin() + i * ks + k, g_out + i * k);
+    std::vector<double> hct(size_t(ks) + 1);
+    nmf_guard_collect(c, Gd, g_out, "nmf_kl_sweep wrote outside the R x k block", [&] { dev_d2h(c.dev, hct.data(), CT.p, CT.bytes); });
     if (colsum_out) std::copy(hct.begin(), hct.begin() + k, colsum_out);
     if (term_out) *term_out = hct[size_t(ks)];
     if (info1) info1[0] = 1;
@@ -4277,7 +4317,7 @@ bool nmf_kl_pass_into(petal_ctx& c, const DevMat& X, const double* H, const doub
         dev_set_tag(c.dev, TAG_NONE);
         if (ran) return true;
     }
-    const int64_t Bk = std::max<int64_t>(1, std::min(n, NMF_FALLBACK_BLOCK / ld));
+    const int64_t Bk = nmf_block_rows(n, ld);
     const size_t esz = dtype_size(X.dtype);
     DBuf Xb(c.dev, sizeof(double) * size_t((Bk - 1) * ld + dp)), Q(c.dev, sizeof(double) * size_t(Bk) * dp), Z(c.dev, sizeof(double) * size_t(Bk) * kp);
     std::vector<double> hx(size_t((Bk - 1) * ld + dp)), hq(size_t(Bk) * dp), hz(size_t(Bk) * kp), hw(size_t(Bk) * kp), hr(static_cast<size_t>(kp)),
@@ -4375,25 +4415,18 @@ void nmf_kl_hupdate_into(petal_ctx& c, int64_t kp, int64_t dp, const double* A, 
 
 petal_nmf* nmf_kl_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
                       int64_t seed, const petal_matrix* w_out) {
-    const Timer timer = start_fit(c, x);
-    if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
-    const int dt = x.dtype;
-    const int64_t n = x.rows, d = x.cols;
-    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
-    const DevMat X = ingest(c, x);
-    const NmfScan sx = nmf_scan(c, X);
-    nmf_reject(sx);
-    const int64_t dp = X.dp, kp = nmf_padded_k(k);
-    DBuf W(c.dev, sizeof(double) * size_t(n) * kp), H(c.dev, sizeof(double) * size_t(kp) * dp), G(c.dev, sizeof(double) * size_t(kp) * kp);
+    NmfDenseFit f = nmf_dense_fit_front(c, x, k, spec, w0, h0, seed, w_out);
+    const int64_t dp = f.dp, kp = f.kp;
+    double *W = f.W.f64(), *H = f.H.f64();
+    DBuf G(c.dev, sizeof(double) * size_t(kp) * kp);
     DBuf A(c.dev, sizeof(double) * size_t(kp) * dp), cts(c.dev, sizeof(double) * size_t(kp + 2)), rsum(c.dev, sizeof(double) * size_t(kp));
-    nmf_init_factors(c, dt, n, d, k, kp, dp, sx, w0, h0, seed, W, H);
     dev_memset(c.dev, G.p, 0, G.bytes);   // (H H^T, which this loss never reads, as zeros: the CSR fit's handle)
-    nmf_kl_rowsum_into(c, kp, dp, H.f64(), rsum.f64());
+    nmf_kl_rowsum_into(c, kp, dp, H, rsum.f64());
     // the loss = sqrt(2 max(0, term + <colsum W, rowsum H> - sum[x > eps] x)): a pass with inner = 0 leaves colsum(W), the term and the sum
     bool kernel = true;
     std::vector<double> hc(size_t(kp) + 2), hr(static_cast<size_t>(kp));
     const auto read_loss = [&]() {
-        kernel = nmf_kl_pass_into(c, X, H.f64(), rsum.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 0, A.f64(), cts.f64()) && kernel;
+        kernel = nmf_kl_pass_into(c, f.X, H, rsum.f64(), k, kp, W, false, 0.0, spec.l1_w, spec.l2_w, 0, A.f64(), cts.f64()) && kernel;
         dev_d2h(c.dev, hc.data(), cts.p, cts.bytes);
         dev_d2h(c.dev, hr.data(), rsum.p, rsum.bytes);
         dev_sync(c.dev);
@@ -4402,51 +4435,29 @@ petal_nmf* nmf_kl_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfS
         return std::sqrt(2.0 * std::max(0.0, (hc[size_t(kp)] + dot) - hc[size_t(kp) + 1]));
     };
     const double err_init = read_loss();
-    double err_prev = err_init, err = err_init;
-    int64_t n_iter = spec.max_iter;
-    bool read = false;   // `err` is the loss of the iteration just run
-    for (int64_t it = 1; it <= spec.max_iter; ++it) {
-        kernel = nmf_kl_pass_into(c, X, H.f64(), rsum.f64(), k, kp, W.f64(), false, 0.0, spec.l1_w, spec.l2_w, 1, A.f64(), cts.f64()) && kernel;
-        nmf_kl_hupdate_into(c, kp, dp, A.f64(), cts.f64(), H.f64(), spec.l1_h, spec.l2_h, rsum.f64());
-        read = false;
-        if (spec.tol > 0 && it % 10 == 0) {
-            err = read_loss();
-            read = true;
-            if ((err_prev - err) / err_init < spec.tol) { n_iter = it; break; }
-            err_prev = err;
-        }
-    }
-    if (!read) err = read_loss();
-    if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, kp, *w_out);
-    std::unique_ptr<petal_nmf> h(new petal_nmf());
-    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
-    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = kernel ? 1 : 0; h->err = err; h->err_init = err_init; h->loss = NMF_LOSS_KL;
-    finish_stats(c, timer);
-    h->h = H.f64(); H.p = nullptr;
-    h->hht = G.f64(); G.p = nullptr;
-    return h.release();
+    const NmfStop stop = nmf_mu_iterate(
+        spec, err_init,
+        [&]() {
+            kernel = nmf_kl_pass_into(c, f.X, H, rsum.f64(), k, kp, W, false, 0.0, spec.l1_w, spec.l2_w, 1, A.f64(), cts.f64()) && kernel;
+            nmf_kl_hupdate_into(c, kp, dp, A.f64(), cts.f64(), H, spec.l1_h, spec.l2_h, rsum.f64());
+        },
+        read_loss);
+    if (w_out) nmf_emit_w(c, f.dt, W, f.n, k, kp, *w_out);
+    return nmf_finish_handle(c, f.timer, nmf_dims(f), spec, err_init, stop, kernel, NMF_LOSS_KL, 0, f.H, G);
 }
 
 // transform of a Kullback-Leibler model on dense rows: W starts at the constant sqrt(mean(Xq) / k) and takes exactly max_iter updates
 // with H fixed -- one pass over X whatever max_iter is where the kernel runs
 void nmf_kl_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
     const Timer timer = start_fit(c, x);
+    // (this refusal is this transform's own: nmf_transform and nmf_cd_transform enter the frame without one)
     if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
-    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
-    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
-    const int64_t m = x.rows;
-    check_output(w_out, h.dtype, m, h.k);
-    if (m == 0) { finish_stats(c, timer); return; }
-    const DevMat X = ingest(c, x);
-    const NmfScan sx = nmf_scan(c, X);
-    nmf_reject(sx);
-    const double w0 = std::sqrt(sx.sum / (double(m) * double(h.d)) / double(h.k));
-    DBuf W(c.dev, sizeof(double) * size_t(m) * h.kp), rsum(c.dev, sizeof(double) * size_t(h.kp));
-    nmf_kl_rowsum_into(c, h.kp, h.dp, h.h, rsum.f64());
-    const bool ran = nmf_kl_pass_into(c, X, h.h, rsum.f64(), h.k, h.kp, W.f64(), true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr);
-    h.last_kernel = ran ? 1 : 0;
-    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, h.kp, w_out);
-    finish_stats(c, timer);
+    DBuf rsum;   // (allocated in the pass, released behind the frame's closing synchronisation: the pass that reads it is only queued)
+    nmf_dense_transform(c, h, timer, x, w_out, [&](const DevMat& X, double w0, double* W) {
+        rsum = DBuf(c.dev, sizeof(double) * size_t(h.kp));
+        nmf_kl_rowsum_into(c, h.kp, h.dp, h.h, rsum.f64());
+        return nmf_kl_pass_into(c, X, h.h, rsum.f64(), h.k, h.kp, W, true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr);
+    });
 }
 }  // namespace
 
@@ -4472,42 +4483,27 @@ void nmf_kl_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w
     if (n == 0 || d == 0) invalid_input("nmf_kl_pass: the input has no rows or no columns");
     if (k < 1) invalid_input("nmf_kl_pass: the number of components should be at least 1");
     if (inner < 0) invalid_input("negative parameter");
-    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0) || std::isinf(spec.l1_w) || std::isinf(spec.l2_w))
-        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    nmf_check_penalties(spec.l1_w, spec.l2_w);
     if (term_out && inner != 0) invalid_input("term_out comes with inner_iters = 0 only");
     const DevMat X = ingest(c, x);
     nmf_reject(nmf_scan(c, X));
     const int64_t dp = X.dp, kp = nmf_padded_k(k);
-    std::vector<double> hw(size_t(n) * kp, 0.0), hp(size_t(kp) * dp, 0.0);
-    for (int64_t i = 0; i < n; ++i) std::copy(w_in + i * k, w_in + (i + 1) * k, hw.begin() + i * kp);
-    for (int64_t i = 0; i < k; ++i) std::copy(hh + i * d, hh + (i + 1) * d, hp.begin() + i * dp);
-    // W is formed inside a guard: a row in front and a row behind, every byte 0xFF beforehand.  The guard rows must come back
-    // untouched and the padding columns of W as zeros.
-    DBuf G(c.dev, sizeof(double) * size_t(n + 2) * kp), H(c.dev, sizeof(double) * hp.size()), rsum(c.dev, sizeof(double) * size_t(kp));
+    const std::vector<double> hp = nmf_padded(hh, d, k, d, kp, dp);
+    const NmfGuarded G = nmf_guard_stage(c, w_in, n, k, kp, 1, 1);   // W between two guard rows
+    DBuf H(c.dev, sizeof(double) * hp.size()), rsum(c.dev, sizeof(double) * size_t(kp));
     const bool side = a_out || colsum_out || term_out || inner == 0;   // (the loss pass always forms A and the sums)
     DBuf A, cts;
     if (side) {
         A = DBuf(c.dev, sizeof(double) * size_t(kp) * dp);
         cts = DBuf(c.dev, sizeof(double) * size_t(kp + 2));
     }
-    double* W = G.f64() + kp;
-    dev_memset(c.dev, G.p, 0xFF, G.bytes);
-    dev_h2d(c.dev, W, hw.data(), sizeof(double) * hw.size());
     dev_h2d(c.dev, H.p, hp.data(), H.bytes);
     nmf_kl_rowsum_into(c, kp, dp, H.f64(), rsum.f64());
-    const bool ran = nmf_kl_pass_into(c, X, H.f64(), rsum.f64(), k, kp, W, false, 0.0, spec.l1_w, spec.l2_w, inner, A.f64(), cts.f64());
-    std::vector<double> hg(size_t(n + 2) * kp), hc(size_t(kp) + 2, 0.0);
-    dev_d2h(c.dev, hg.data(), G.p, G.bytes);
-    if (side) dev_d2h(c.dev, hc.data(), cts.p, cts.bytes);
-    dev_sync(c.dev);
-    for (int64_t i = 0; i < n + 2; ++i)
-        for (int64_t j = 0; j < kp; ++j) {
-            uint64_t bits = 0;
-            std::memcpy(&bits, &hg[size_t(i) * kp + j], 8);
-            const bool guard = i == 0 || i == n + 1;
-            if (guard ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_kl_pass wrote outside the n x k block");
-        }
-    for (int64_t i = 0; i < n; ++i) std::copy(hg.begin() + (i + 1) * kp, hg.begin() + (i + 1) * kp + k, w_out + i * k);
+    const bool ran = nmf_kl_pass_into(c, X, H.f64(), rsum.f64(), k, kp, G.block(), false, 0.0, spec.l1_w, spec.l2_w, inner, A.f64(), cts.f64());
+    std::vector<double> hc(size_t(kp) + 2, 0.0);
+    nmf_guard_collect(c, G, w_out, "nmf_kl_pass wrote outside the n x k block", [&] {
+        if (side) dev_d2h(c.dev, hc.data(), cts.p, cts.bytes);
+    });
     if (a_out) {
         dev_copy2d(c.dev, a_out, sizeof(double) * d, A.p, sizeof(double) * dp, sizeof(double) * d, size_t(k), 1);
         dev_sync(c.dev);
@@ -4566,36 +4562,26 @@ bool nmf_cd_pass_into(petal_ctx& c, const DevMat& X, const double* H, const doub
         dev_set_tag(c.dev, TAG_NONE);
         if (ran) return true;
     }
-    const int64_t Bk = std::max<int64_t>(1, std::min(n, NMF_FALLBACK_BLOCK / ld));
-    const size_t esz = dtype_size(X.dtype);
-    DBuf Xb(c.dev, sizeof(double) * size_t((Bk - 1) * ld + dp)), Z(c.dev, sizeof(double) * size_t(Bk) * kp);
+    const int64_t Bk = nmf_block_rows(n, ld);
+    DBuf Z(c.dev, sizeof(double) * size_t(Bk) * kp);
     std::vector<double> hz(size_t(Bk) * kp), hw(size_t(Bk) * kp), hv(size_t(std::max<int64_t>(inner, 1)), 0.0), s;
     if (inner > 0) s = nmf_cd_host_s(c, HHt, k, kp, l2);
-    if (A) {
-        dev_memset(c.dev, A, 0, sizeof(double) * size_t(kp) * dp);
-        dev_memset(c.dev, B, 0, sizeof(double) * size_t(kp) * kp);
-    }
-    for (int64_t r0 = 0; r0 < n; r0 += Bk) {
-        const int64_t b = std::min(Bk, n - r0);
-        double* Wb = W + r0 * kp;
-        op_cvt_to_f64(c.dev, X.dtype, Xb.f64(), static_cast<const char*>(X.p) + size_t(r0) * ld * esz, (b - 1) * ld + dp);
+    const auto fill = [&](double* Wb, int64_t b) {
         if (from_zero) dev_memset(c.dev, Wb, 0, sizeof(double) * size_t(b) * kp);
-        if (inner > 0) {
-            op_dgemm(c.dev, false, true, b, kp, dp, 1.0, Xb.f64(), ld, H, dp, 0.0, Z.f64(), kp);
-            dev_d2h(c.dev, hz.data(), Z.p, sizeof(double) * size_t(b) * kp);
-            dev_d2h(c.dev, hw.data(), Wb, sizeof(double) * size_t(b) * kp);
-            dev_sync(c.dev);
-            for (int64_t idx = 0; idx < b * kp; ++idx) hz[idx] -= l1;
-            for (int64_t it = 0; it < inner; ++it)
-                for (int64_t i = 0; i < b; ++i) hv[size_t(it)] += nmf_cd_sweep_host(&hw[size_t(i) * kp], 1, &hz[size_t(i) * kp], s.data(), kp);
-            dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
-        }
-        if (A) {   // the blocks' contributions are added in block order
-            op_dgemm(c.dev, true, false, kp, dp, b, 1.0, Wb, kp, Xb.f64(), ld, 1.0, A, dp);
-            op_dgemm(c.dev, true, false, kp, kp, b, 1.0, Wb, kp, Wb, kp, 1.0, B, kp);
-        }
-        dev_sync(c.dev);   // (hw goes up before the next block overwrites it)
-    }
+    };
+    const auto rule = [&](const double* Xb, double* Wb, int64_t b) {
+        if (inner <= 0) return;
+        op_dgemm(c.dev, false, true, b, kp, dp, 1.0, Xb, ld, H, dp, 0.0, Z.f64(), kp);
+        dev_d2h(c.dev, hz.data(), Z.p, sizeof(double) * size_t(b) * kp);
+        dev_d2h(c.dev, hw.data(), Wb, sizeof(double) * size_t(b) * kp);
+        dev_sync(c.dev);
+        for (int64_t idx = 0; idx < b * kp; ++idx) hz[idx] -= l1;
+        for (int64_t it = 0; it < inner; ++it)
+            for (int64_t i = 0; i < b; ++i) hv[size_t(it)] += nmf_cd_sweep_host(&hw[size_t(i) * kp], 1, &hz[size_t(i) * kp], s.data(), kp);
+        dev_h2d(c.dev, Wb, hw.data(), sizeof(double) * size_t(b) * kp);
+    };
+    // (a synchronisation behind every block: hw goes up before the next block overwrites it)
+    nmf_composed_pass(c, X, kp, W, A, B, fill, rule, /*sync_blocks=*/true);
     if (viol && inner > 0) dev_h2d(c.dev, viol, hv.data(), sizeof(double) * size_t(inner));
     dev_sync(c.dev);
     return false;
@@ -4629,37 +4615,22 @@ bool nmf_cd_hupdate_into(petal_ctx& c, int64_t k, int64_t kp, int64_t dp, const 
 
 petal_nmf* nmf_cd_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
                       int64_t seed, const petal_matrix* w_out) {
-    const Timer timer = start_fit(c, x);
-    if (sharded(c)) invalid_input("Nmf: a sharded ctx is not supported in this version");
-    const int dt = x.dtype;
-    const int64_t n = x.rows, d = x.cols;
-    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
-    const DevMat X = ingest(c, x);
-    const NmfScan sx = nmf_scan(c, X);
-    nmf_reject(sx);
-    const int64_t dp = X.dp, kp = nmf_padded_k(k);
-    DBuf W(c.dev, sizeof(double) * size_t(n) * kp), H(c.dev, sizeof(double) * size_t(kp) * dp), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
+    NmfDenseFit f = nmf_dense_fit_front(c, x, k, spec, w0, h0, seed, w_out);
+    const int64_t dp = f.dp, kp = f.kp;
+    double *W = f.W.f64(), *H = f.H.f64();
+    DBuf HHt(c.dev, sizeof(double) * size_t(kp) * kp);
     DBuf A(c.dev, sizeof(double) * size_t(kp) * dp), B(c.dev, sizeof(double) * size_t(kp) * kp), dots(c.dev, sizeof(double) * 2);
     DBuf viol(c.dev, sizeof(double) * 2);   // { the W sweep's violation, the H sweep's }
-    nmf_init_factors(c, dt, n, d, k, kp, dp, sx, w0, h0, seed, W, H);
-    op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
+    op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H, dp, H, dp, 0.0, HHt.f64(), kp);
     // the loss at the start: A = W^T X and B = W^T W from a pass that leaves W alone
-    bool kernel = nmf_cd_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, spec.l1_w, spec.l2_w, 0, A.f64(), B.f64(), nullptr);
-    double hd[2];
-    {
-        std::vector<double> a(size_t(kp) * dp), b(size_t(kp) * kp), h(size_t(kp) * dp), hht;
-        dev_d2h(c.dev, a.data(), A.p, A.bytes);
-        dev_d2h(c.dev, b.data(), B.p, B.bytes);
-        dev_d2h(c.dev, h.data(), H.p, H.bytes);
-        dev_sync(c.dev);
-        nmf_host_gram_dots(a, b, h, kp, dp, hht, hd);
-    }
-    const double err_init = nmf_loss(sx.sumsq, hd);
+    bool kernel = nmf_cd_pass_into(c, f.X, H, HHt.f64(), k, kp, W, false, spec.l1_w, spec.l2_w, 0, A.f64(), B.f64(), nullptr);
+    const double err_init = nmf_initial_loss_frobenius(c, f, A, B);
+    // (the stopping rule is this solver's own: the projected-gradient violation after every iteration, not nmf_mu_iterate's)
     int64_t n_iter = spec.max_iter;
     double viol_init = 0.0;
     for (int64_t it = 1; it <= spec.max_iter; ++it) {
-        kernel = nmf_cd_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W.f64(), false, spec.l1_w, spec.l2_w, 1, A.f64(), B.f64(), viol.f64()) && kernel;
-        nmf_cd_hupdate_into(c, k, kp, dp, A.f64(), B.f64(), H.f64(), HHt.f64(), spec.l1_h, spec.l2_h, dots.f64(), viol.f64() + 1);
+        kernel = nmf_cd_pass_into(c, f.X, H, HHt.f64(), k, kp, W, false, spec.l1_w, spec.l2_w, 1, A.f64(), B.f64(), viol.f64()) && kernel;
+        nmf_cd_hupdate_into(c, k, kp, dp, A.f64(), B.f64(), H, HHt.f64(), spec.l1_h, spec.l2_h, dots.f64(), viol.f64() + 1);
         if (spec.tol > 0) {   // (tol = 0 queues the whole fit without a host round trip)
             double hv[2];
             dev_d2h(c.dev, hv, viol.p, sizeof(hv));
@@ -4669,17 +4640,12 @@ petal_nmf* nmf_cd_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfS
             if (viol_init == 0.0 || v / viol_init <= spec.tol) { n_iter = it; break; }
         }
     }
+    double hd[2];
     dev_d2h(c.dev, hd, dots.p, sizeof(hd));
     dev_sync(c.dev);
-    const double err = nmf_loss(sx.sumsq, hd);
-    if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, kp, *w_out);
-    std::unique_ptr<petal_nmf> h(new petal_nmf());
-    h->owner = &c; h->n = n; h->d = d; h->dp = dp; h->k = k; h->kp = kp; h->max_iter = spec.max_iter; h->n_iter = n_iter; h->dtype = dt;
-    h->l1_w = spec.l1_w; h->l2_w = spec.l2_w; h->fit_kernel = kernel ? 1 : 0; h->err = err; h->err_init = err_init; h->solver = 1;
-    finish_stats(c, timer);
-    h->h = H.f64(); H.p = nullptr;
-    h->hht = HHt.f64(); HHt.p = nullptr;
-    return h.release();
+    const double err = nmf_loss(f.sx.sumsq, hd);
+    if (w_out) nmf_emit_w(c, f.dt, W, f.n, k, kp, *w_out);
+    return nmf_finish_handle(c, f.timer, nmf_dims(f), spec, err_init, {n_iter, err}, kernel, NMF_LOSS_FROBENIUS, 1, f.H, HHt);
 }
 }  // namespace
 
@@ -4693,19 +4659,11 @@ petal_nmf* nmf_fit_solver(petal_ctx& c, const petal_matrix& x, int64_t k, const 
 // transform of a coordinate-descent model: W starts at ZERO and takes exactly max_iter sweeps on the fixed Z; no tolerance stop
 void nmf_cd_transform(petal_ctx& c, petal_nmf& h, const petal_matrix& x, const petal_matrix& w_out) {
     nmf_usable(c, h);
+    // (no sharded refusal in front of the frame, as in nmf_transform: nmf_kl_transform alone has one)
     const Timer timer = start_fit(c, x);
-    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
-    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
-    const int64_t m = x.rows;
-    check_output(w_out, h.dtype, m, h.k);
-    if (m == 0) { finish_stats(c, timer); return; }
-    const DevMat X = ingest(c, x);
-    nmf_reject(nmf_scan(c, X));
-    DBuf W(c.dev, sizeof(double) * size_t(m) * h.kp);
-    const bool ran = nmf_cd_pass_into(c, X, h.h, h.hht, h.k, h.kp, W.f64(), true, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr, nullptr);
-    h.last_kernel = ran ? 1 : 0;
-    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, h.kp, w_out);
-    finish_stats(c, timer);
+    nmf_dense_transform(c, h, timer, x, w_out, [&](const DevMat& X, double, double* W) {   // (the constant start is not used: W starts at zero)
+        return nmf_cd_pass_into(c, X, h.h, h.hht, h.k, h.kp, W, true, h.l1_w, h.l2_w, h.max_iter, nullptr, nullptr, nullptr);
+    });
 }
 
 void nmf_cd_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w_in, const double* hh, const NmfSpec& spec, int64_t inner,
@@ -4717,42 +4675,26 @@ void nmf_cd_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w
     if (n == 0 || d == 0) invalid_input("nmf_cd_pass: the input has no rows or no columns");
     if (k < 1) invalid_input("nmf_cd_pass: the number of components should be at least 1");
     if (inner < 0) invalid_input("negative parameter");
-    if (!(spec.l1_w >= 0) || !(spec.l2_w >= 0) || std::isinf(spec.l1_w) || std::isinf(spec.l2_w))
-        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    nmf_check_penalties(spec.l1_w, spec.l2_w);
     if ((a_out == nullptr) != (b_out == nullptr)) invalid_input("a_out and b_out should both be given or both be null");
     const DevMat X = ingest(c, x);
     nmf_reject(nmf_scan(c, X));
     const int64_t dp = X.dp, kp = nmf_padded_k(k);
-    std::vector<double> hw(size_t(n) * kp, 0.0), hp(size_t(kp) * dp, 0.0);
-    for (int64_t i = 0; i < n; ++i) std::copy(w_in + i * k, w_in + (i + 1) * k, hw.begin() + i * kp);
-    for (int64_t i = 0; i < k; ++i) std::copy(hh + i * d, hh + (i + 1) * d, hp.begin() + i * dp);
-    // W is formed inside a guard: a row in front and a row behind, every byte 0xFF beforehand.  The guard rows must come back
-    // untouched and the padding columns of W as zeros.
-    DBuf G(c.dev, sizeof(double) * size_t(n + 2) * kp), H(c.dev, sizeof(double) * hp.size()), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
+    const std::vector<double> hp = nmf_padded(hh, d, k, d, kp, dp);
+    const NmfGuarded G = nmf_guard_stage(c, w_in, n, k, kp, 1, 1);   // W between two guard rows
+    DBuf H(c.dev, sizeof(double) * hp.size()), HHt(c.dev, sizeof(double) * size_t(kp) * kp);
     DBuf A, B, V;
     if (a_out) {
         A = DBuf(c.dev, sizeof(double) * size_t(kp) * dp);
         B = DBuf(c.dev, sizeof(double) * size_t(kp) * kp);
     }
     if (violation_out && inner > 0) V = DBuf(c.dev, sizeof(double) * size_t(inner));
-    double* W = G.f64() + kp;
-    dev_memset(c.dev, G.p, 0xFF, G.bytes);
-    dev_h2d(c.dev, W, hw.data(), sizeof(double) * hw.size());
     dev_h2d(c.dev, H.p, hp.data(), H.bytes);
     op_dgemm(c.dev, false, true, kp, kp, dp, 1.0, H.f64(), dp, H.f64(), dp, 0.0, HHt.f64(), kp);
-    const bool ran = nmf_cd_pass_into(c, X, H.f64(), HHt.f64(), k, kp, W, from_zero && inner > 0, spec.l1_w, spec.l2_w, inner, A.f64(), B.f64(), V.f64());
-    std::vector<double> hg(size_t(n + 2) * kp);
-    dev_d2h(c.dev, hg.data(), G.p, G.bytes);
-    if (V.p) dev_d2h(c.dev, violation_out, V.p, V.bytes);
-    dev_sync(c.dev);
-    for (int64_t i = 0; i < n + 2; ++i)
-        for (int64_t j = 0; j < kp; ++j) {
-            uint64_t bits = 0;
-            std::memcpy(&bits, &hg[size_t(i) * kp + j], 8);
-            const bool guard = i == 0 || i == n + 1;
-            if (guard ? bits != ~uint64_t(0) : (j >= k && bits != 0)) device_error("nmf_cd_pass wrote outside the n x k block");
-        }
-    for (int64_t i = 0; i < n; ++i) std::copy(hg.begin() + (i + 1) * kp, hg.begin() + (i + 1) * kp + k, w_out + i * k);
+    const bool ran = nmf_cd_pass_into(c, X, H.f64(), HHt.f64(), k, kp, G.block(), from_zero && inner > 0, spec.l1_w, spec.l2_w, inner, A.f64(), B.f64(), V.f64());
+    nmf_guard_collect(c, G, w_out, "nmf_cd_pass wrote outside the n x k block", [&] {
+        if (V.p) dev_d2h(c.dev, violation_out, V.p, V.bytes);
+    });
     if (a_out) {
         dev_copy2d(c.dev, a_out, sizeof(double) * d, A.p, sizeof(double) * dp, sizeof(double) * d, size_t(k), 1);
         dev_copy2d(c.dev, b_out, sizeof(double) * k, B.p, sizeof(double) * kp, sizeof(double) * k, size_t(k), 1);
@@ -4766,15 +4708,10 @@ void nmf_cd_hupdate(petal_ctx& c, int64_t k, int64_t d, const double* a, const d
     if (info1) info1[0] = 0;
     if (sharded(c)) invalid_input("nmf_cd_hupdate: a sharded ctx is not supported in this version");
     if (k < 1 || d < 1) invalid_input("nmf_cd_hupdate: k and d should be at least 1");
-    if (!(spec.l1_h >= 0) || !(spec.l2_h >= 0) || std::isinf(spec.l1_h) || std::isinf(spec.l2_h))
-        invalid_input("Nmf: the tolerance and the penalties should be finite and not negative");
+    nmf_check_penalties(spec.l1_h, spec.l2_h);
     const int64_t kp = nmf_padded_k(k), dp = (d + 15) / 16 * 16;
-    std::vector<double> ha(size_t(kp) * dp, 0.0), hb(size_t(kp) * kp, 0.0), hh(size_t(kp) * dp, 0.0);
-    for (int64_t i = 0; i < k; ++i) {
-        std::copy(a + i * d, a + (i + 1) * d, ha.begin() + i * dp);
-        std::copy(h_in + i * d, h_in + (i + 1) * d, hh.begin() + i * dp);
-        std::copy(b + i * k, b + (i + 1) * k, hb.begin() + i * kp);
-    }
+    const std::vector<double> ha = nmf_padded(a, d, k, d, kp, dp), hb = nmf_padded(b, k, k, k, kp, kp);
+    std::vector<double> hh = nmf_padded(h_in, d, k, d, kp, dp);
     DBuf A(c.dev, sizeof(double) * ha.size()), B(c.dev, sizeof(double) * hb.size()), H(c.dev, sizeof(double) * hh.size());
     DBuf HHt(c.dev, sizeof(double) * size_t(kp) * kp), dv(c.dev, sizeof(double) * 3);
     dev_h2d(c.dev, A.p, ha.data(), A.bytes);

@@ -12,7 +12,7 @@ SRCS = [os.path.join(ROOT, "petal-decomposition_amd", "csrc", "api.cpp"),
         os.path.join(ROOT, "petal-decomposition_amd", "csrc", "rccl.cpp"),
         os.path.join(ROOT, "oracle", "cpu_ops.cpp")]
 HDRS = [os.path.join(ROOT, "petal-decomposition_amd", "csrc", h) for h in ("ops.h", "ctx.h")] + \
-       [os.path.join(ROOT, "include", h) for h in ("petal_hip.h", "petal_hip_score.h", "petal_hip_probe.h")]
+       [os.path.join(ROOT, "include", h) for h in sorted(os.listdir(os.path.join(ROOT, "include"))) if h.endswith(".h")]
 
 
 def build() -> str:
