@@ -46,6 +46,29 @@ int petal_probe_jacobi_svd_rows(petal_ctx* ctx, const double* A, int64_t L, int6
 int petal_probe_dgemm(petal_ctx* ctx, int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const double* colscale);
 
+/* ---- the top-k subspace eigen-solver (topk_eigh: Pca, FastICA's whitening, IncrementalPca, the wide Pca and KernelPca take their
+ * eigenpairs from it) and its one-launch residual verdict.  A sharded ctx is PETAL_INVALID_INPUT. */
+
+/* op_ritz_residual by itself: CV (rows x ldc) and Vr (rows x ldv) go to the device with their WHOLE rows, nc <= ldc, ldv columns count;
+ * theta (nc).  flag / flag2: NULL = the operation gets no such word, else the value the device word starts at.
+ *   out3[0] = max_{j < nc} sum_i (CV_ij - theta_j Vr_ij)^2, out3[1] = theta[0] (0 when nc == 0), out3[2] = 1 if one of those nc sums is
+ *   not below 1e300 (NaN included) or a given flag word is non-zero, else 0
+ *   w_out (w_len >= max(nc, 1) words): theta[0 .. nc), NaN behind */
+int petal_probe_ritz_residual(petal_ctx* ctx, const double* CV, int64_t ldc, const double* Vr, int64_t ldv, int64_t rows, int64_t nc,
+                              const double* theta, const int* flag, const int* flag2, double* out3, double* w_out, int64_t w_len);
+
+/* C (d x d, ldc; 1 <= d <= 2048) staged as the dp x dp zero-padded matrix a fit holds, dp = d rounded up to 16; nc <= d pairs wanted;
+ * dtype PETAL_F32 | PETAL_F64: the type of the data C was formed from (closeness threshold 1e-8 | 1e-5, residual tolerance 1e-12 | 3e-14).
+ *   mode 0  gram_topk_eigh, synchronous: *delivered, w (nc), V (dp x nc, ldv), *checks = the Rayleigh-Ritz steps taken
+ *   mode 1  gram_topk_eigh, optimistic:  *delivered (the shape qualified), w, V, r3 (the verdict triple), *verdict = 1 when the
+ *           library's own reading of r3 accepts the result
+ *   mode 2  gram_eigen as Pca calls it:  *delivered (the iteration answered; 0: the full eigen-solver), w (dp), V (dp x dp, ldv),
+ *           diag (dp; may be NULL in modes 0 / 1)
+ * In modes 0 / 1 the device V and w hold NaN when the operation starts: a shape that does not qualify returns them so.  Outputs a mode
+ * does not produce: *checks = 0, *verdict = 0, r3 = NaN. */
+int petal_probe_topk_eigh(petal_ctx* ctx, const double* C, int64_t d, int64_t ldc, int64_t nc, int32_t dtype, int mode, int* delivered,
+                          double* w, double* V, int64_t ldv, int* checks, double* r3, int* verdict, double* diag);
+
 /* ---- the composite operations that steer the optimistic RandomizedPca fit, each called the way rpca_fit calls it ---------------------
  * X (n x K, ldx) and mu (K values) are HOST memory in `dtype` (PETAL_F32 | PETAL_F64); X goes to the device the way a fit's input does
  * (the row padding of PETAL_OPT_ROW_PAD included).  K and the column counts N / M are the PADDED extents a fit passes: multiples of 16.

@@ -353,7 +353,7 @@ void op_ritz_residual(Dev*, const double* CV, int64_t ldc, const double* Vr, int
     for (int64_t j = 0; j < nc; ++j) {
         double s2 = 0;
         for (int64_t i = 0; i < rows; ++i) { const double r = CV[i * ldc + j] - theta[j] * Vr[i * ldv + j]; s2 += r * r; }
-        if (!std::isfinite(s2)) bad = 1;
+        if (!(s2 < 1e300)) bad = 1;   // (ops.h: "not below 1e300", NaN and inf included)
         else worst = std::max(worst, s2);
     }
     if (flag && *flag != 0) bad = 1;

@@ -154,6 +154,8 @@ ABI_PROBE = [
     ("petal_probe_jacobi_svd_rows", C.c_int, [_P, _D, C.c_int64, C.c_int64, _D, C.c_int64, _D, _I]),
     ("petal_probe_dgemm", C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _D, C.c_int64, _D, C.c_int64,
                                     C.c_double, _D, C.c_int64, _D]),
+    ("petal_probe_ritz_residual", C.c_int, [_P, _D, C.c_int64, _D, C.c_int64, C.c_int64, C.c_int64, _D, _I, _I, _D, _D, C.c_int64]),
+    ("petal_probe_topk_eigh", C.c_int, [_P, _D, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int, _I, _D, _D, C.c_int64, _I, _D, _I, _D]),
     ("petal_probe_power_pass_means", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _D, C.c_int64, C.c_int64,
                                                C.c_int64, _I, _D, C.c_int64, _D, _D, _D, _D]),
     ("petal_probe_rebase", C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _D, C.c_int64, C.c_int64, C.c_double, _D,
@@ -2240,6 +2242,49 @@ def probe_eigh(a, tol_rel=1e-15, clustered=False, Lz=0, ncheck=0, verdict_mode=0
     ctx.check(ctx.lib.petal_probe_eigh(ctx._h, _dp(a), L, lda, float(tol_rel), int(bool(clustered)), int(Lz), int(ncheck), int(verdict_mode),
                                        int(verdict_in), float(gap_tol_override), _dp(w), _dp(v), lm, C.byref(vo)))
     return w, v, vo.value
+
+
+def probe_ritz_residual(cv, vr, nc, theta, flag=None, flag2=None, w_len=None, ctx: Optional[Context] = None):
+    """(out3, w_out) of petal_probe_ritz_residual: cv, vr (rows x leading dimension, the first nc columns count), theta (nc values);
+    flag / flag2: None = no such word, else its starting value; w_out has w_len (default nc + 8) words, NaN where nothing was written"""
+    ctx = ctx or default_context()
+    cv, vr = np.ascontiguousarray(cv, dtype=np.float64), np.ascontiguousarray(vr, dtype=np.float64)
+    if cv.ndim != 2 or vr.ndim != 2 or cv.shape[0] != vr.shape[0]:
+        raise InvalidInput("cv and vr should be 2-D arrays with the same number of rows")
+    th = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+    if th.size < nc:
+        raise InvalidInput(f"theta should hold {nc} values")
+    w_len = int(nc + 8 if w_len is None else w_len)
+    out3, w_out = np.full(3, np.nan), np.full(max(w_len, 1), np.nan)
+    f1 = C.c_int(int(flag)) if flag is not None else None
+    f2 = C.c_int(int(flag2)) if flag2 is not None else None
+    ctx.check(ctx.lib.petal_probe_ritz_residual(ctx._h, _dp(cv), cv.shape[1], _dp(vr), vr.shape[1], cv.shape[0], int(nc),
+                                                _dp(th) if nc > 0 else None, C.byref(f1) if f1 is not None else None,
+                                                C.byref(f2) if f2 is not None else None, _dp(out3), _dp(w_out), w_len))
+    return out3, w_out
+
+
+def probe_topk_eigh(c, nc, dtype=PETAL_F64, mode=0, ctx: Optional[Context] = None):
+    """petal_probe_topk_eigh on c (d x d float64).  Returns a dict: delivered, w, v, and by mode 0: checks; 1: r3, verdict; 2: diag
+    (w: dp values, v: dp x dp; modes 0 / 1: nc values, dp x nc)"""
+    ctx = ctx or default_context()
+    c, ldc = _f64_2d(c)
+    d = c.shape[0]
+    dp = (d + 15) // 16 * 16
+    cols = dp if mode == 2 else int(nc)
+    w, v = np.full(max(cols, 1), np.nan), np.full((dp, max(cols, 1)), np.nan)
+    r3, diag = np.full(3, np.nan), np.full(dp, np.nan)
+    delivered, checks, verdict = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    ctx.check(ctx.lib.petal_probe_topk_eigh(ctx._h, _dp(c), d, ldc, int(nc), int(dtype), int(mode), C.byref(delivered), _dp(w), _dp(v),
+                                            max(cols, 1), C.byref(checks), _dp(r3), C.byref(verdict), _dp(diag)))
+    out = {"delivered": delivered.value, "w": w[:cols], "v": v[:, :cols]}
+    if mode == 0:
+        out["checks"] = checks.value
+    elif mode == 1:
+        out["r3"], out["verdict"] = r3, verdict.value
+    else:
+        out["diag"] = diag
+    return out
 
 
 def probe_jacobi_svd_rows(a, ctx: Optional[Context] = None):

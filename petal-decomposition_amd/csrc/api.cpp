@@ -728,6 +728,32 @@ int petal_probe_dgemm(petal_ctx* ctx, int ta, int tb, int64_t M, int64_t N, int6
     });
 }
 
+int petal_probe_ritz_residual(petal_ctx* ctx, const double* CV, int64_t ldc, const double* Vr, int64_t ldv, int64_t rows, int64_t nc,
+                              const double* theta, const int* flag, const int* flag2, double* out3, double* w_out, int64_t w_len) {
+    return guarded(ctx, [&] {
+        need(CV, "CV");
+        need(Vr, "Vr");
+        if (nc > 0) need(theta, "theta");
+        need(out3, "out3");
+        need(w_out, "w_out");
+        probe_ritz_residual(*ctx, CV, ldc, Vr, ldv, rows, nc, theta, flag, flag2, out3, w_out, w_len);
+    });
+}
+
+int petal_probe_topk_eigh(petal_ctx* ctx, const double* C, int64_t d, int64_t ldc, int64_t nc, int32_t dtype, int mode, int* delivered,
+                          double* w, double* V, int64_t ldv, int* checks, double* r3, int* verdict, double* diag) {
+    return guarded(ctx, [&] {
+        need(C, "C");
+        need(delivered, "delivered");
+        need(w, "w");
+        need(V, "V");
+        need(checks, "checks");
+        need(r3, "r3");
+        need(verdict, "verdict");
+        probe_topk_eigh(*ctx, C, d, ldc, nc, dtype, mode, delivered, w, V, ldv, checks, r3, verdict, diag);
+    });
+}
+
 int petal_probe_power_pass_means(petal_ctx* ctx, const void* X, int32_t dtype, int64_t n, int64_t K, int64_t d, int64_t ldx, const double* P,
                                  int64_t N, int64_t ldp, int64_t L, int* done, double* Y, int64_t ldy, double* mu64, double* muT, double* mu0,
                                  double* tv) {

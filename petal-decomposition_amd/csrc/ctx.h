@@ -255,6 +255,11 @@ void probe_eigh(petal_ctx& c, const double* A, int64_t L, int64_t lda, double to
 void probe_jacobi_svd_rows(petal_ctx& c, const double* A, int64_t L, int64_t lda, double* U, int64_t ldu, double* s_inv, int* nonconv);
 void probe_dgemm(petal_ctx& c, bool ta, bool tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
                  const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const double* colscale);
+// ... the top-k subspace eigen-solver (topk_eigh through gram_topk_eigh / gram_eigen) and its residual verdict (op_ritz_residual)
+void probe_ritz_residual(petal_ctx& c, const double* CV, int64_t ldc, const double* Vr, int64_t ldv, int64_t rows, int64_t nc,
+                         const double* theta, const int* flag, const int* flag2, double* out3, double* w_out, int64_t w_len);
+void probe_topk_eigh(petal_ctx& c, const double* C, int64_t d, int64_t ldc, int64_t nc, int dtype, int mode, int* delivered, double* w,
+                     double* V, int64_t ldv, int* checks, double* r3, int* verdict, double* diag);
 // ... and the composite operations that steer the optimistic fit (op_power_pass_means; op_rebase_xp / op_rebase_power_pass)
 void probe_power_pass_means(petal_ctx& c, const void* X, int dtype, int64_t n, int64_t K, int64_t d, int64_t ldx, const double* P, int64_t N,
                             int64_t ldp, int64_t L, int* done, double* Y, int64_t ldy, double* mu64, double* muT, double* mu0, double* tv);
