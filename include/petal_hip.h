@@ -213,7 +213,9 @@ int petal_inverse_transform(petal_ctx* ctx, const petal_matrix* y, const void* c
 /* ---- FastIca<A,R>::fit / fit_transform  (src/ica.rs:105-112, 147-157, 167-221) ---------------- */
 /* n_components == 0 -> min(n, d) as the crate does (src/ica.rs:173).  w_init: HOST nc x nc row-major
  * StandardNormal draw (src/ica.rs:210-214).  Reference constants tol = 1e-4, max_iter = 200
- * (src/ica.rs:216).  components: nc x d, means: d (host).  y_out (nullable): n x nc sources. */
+ * (src/ica.rs:216).  components: nc x d, means: d (host).  y_out (nullable): n x nc sources.
+ * max_iter = 0 runs no iteration and returns components = polar(w_init) K, K the whitening matrix, with *n_iter = 0 (the crate's
+ * ica_par with an empty loop, src/ica.rs:329-361): the handle tests/whitening_cases.py holds the whitening stage by. */
 int petal_fastica_fit(petal_ctx* ctx, const petal_matrix* x, int64_t n_components, double tol, int64_t max_iter,
                       int mode, const void* w_init, void* components, void* means, int64_t* n_iter,
                       const petal_matrix* y_out);

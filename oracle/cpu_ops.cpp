@@ -510,7 +510,14 @@ void op_cvt_to_f64(Dev*, int dt, double* dst, const void* src, int64_t count) {
 
 void op_colmean(Dev* d, int dt, const void* X, int64_t n, int64_t dd, int64_t ldx, double n_total, double* mu64, void* muT, bool with_sq) {
     op_colsum(d, dt, X, n, dd, ldx, mu64, with_sq);
-    for (int64_t j = 0; j < dd; ++j) mu64[j] /= n_total;
+    if (dt == F64) {   // the device carries fp64 data's column sums as (high, low) pairs and rounds the mean once: extended precision here
+        std::vector<long double> acc(size_t(dd), 0.0L);
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t j = 0; j < dd; ++j) acc[size_t(j)] += static_cast<const double*>(X)[i * ldx + j];
+        for (int64_t j = 0; j < dd; ++j) mu64[j] = double(acc[size_t(j)] / (long double)n_total);
+    } else {
+        for (int64_t j = 0; j < dd; ++j) mu64[j] /= n_total;
+    }
     op_cvt_from_f64(d, dt, muT, mu64, dd);
 }
 void op_gemm_xp_prod(Dev* d, int dt, const void* X, int64_t n, int64_t K, int64_t ldx, const void* mu, const double* A, int64_t M,

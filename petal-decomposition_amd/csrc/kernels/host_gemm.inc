@@ -38,12 +38,12 @@ void op_unpack_strided(Dev* d, int dt, const void* src, int64_t n, int64_t dd, i
 
 // first stage of the column sums (a 16-byte-per-lane form measured the same: EXPERIMENTS.md round 4)
 static void launch_colsum_parts(Dev* d, int dt, const void* X, int64_t n, int64_t dd, int64_t ldx, int64_t rows, int64_t nparts,
-                                double* part, bool with_sq) {
+                                double* part, bool with_sq, double* part_lo = nullptr) {
     const dim3 grid((unsigned)nparts, cdiv(dd, 64));
     if (with_sq) {
-        DISPATCH_T(dt, hipLaunchKernelGGL((k_colsum_part2<T, true>), grid, dim3(256), 0, d->stream, (const T*)X, n, dd, ldx, rows, part));
+        DISPATCH_T(dt, hipLaunchKernelGGL((k_colsum_part2<T, true>), grid, dim3(256), 0, d->stream, (const T*)X, n, dd, ldx, rows, part, part_lo));
     } else {
-        DISPATCH_T(dt, hipLaunchKernelGGL((k_colsum_part2<T, false>), grid, dim3(256), 0, d->stream, (const T*)X, n, dd, ldx, rows, part));
+        DISPATCH_T(dt, hipLaunchKernelGGL((k_colsum_part2<T, false>), grid, dim3(256), 0, d->stream, (const T*)X, n, dd, ldx, rows, part, part_lo));
     }
     launch_check();
 }
@@ -64,13 +64,18 @@ void op_colmean(Dev* d, int dt, const void* X, int64_t n, int64_t dd, int64_t ld
     const int64_t w = with_sq ? 2 * dd : dd;
     if (n == 0) { dev_memset(d, mu64, 0, sizeof(double) * w); dev_memset(d, muT, 0, dtype_size(dt) * dd); return; }
     const int64_t rows = scan_rows_per_block(n, dd), nparts = cdiv(n, rows);
-    double* part = (double*)dev_alloc(d, sizeof(double) * nparts * w);
+    // fp64 data: the sums as (high, low) pairs, the mean one rounding of the exact one (k_colsum_part2); fp32 data's fp64 sums are
+    // rounded to fp32 once anyway
+    const bool pairs = dt == F64;
+    double* part = (double*)dev_alloc(d, sizeof(double) * nparts * w * (pairs ? 2 : 1));
+    double* part_lo = pairs ? part + nparts * w : nullptr;
     {
         TagScope ts(d);   // (the pass over X; bracketed when the caller tagged it)
-        launch_colsum_parts(d, dt, X, n, dd, ldx, rows, nparts, part, with_sq);
+        launch_colsum_parts(d, dt, X, n, dd, ldx, rows, nparts, part, with_sq, part_lo);
         ts.stop();
     }
-    DISPATCH_T(dt, hipLaunchKernelGGL(k_colmean_final<T>, dim3(cdiv(w, 8)), dim3(256), 0, d->stream, part, nparts, w, dd, 1.0 / n_total, mu64, (T*)muT));
+    DISPATCH_T(dt, hipLaunchKernelGGL(k_colmean_final<T>, dim3(cdiv(w, 8)), dim3(256), 0, d->stream, part, part_lo, nparts, w, dd, 1.0 / n_total,
+                                      n_total, mu64, (T*)muT));
     launch_check();
     dev_free(d, part);
 }

@@ -1537,22 +1537,44 @@ __global__ __launch_bounds__(256) void k_transpose_out(const double* __restrict_
 }
 // column means from the per-block partial sums of k_colsum_part2, in one launch: fixed-order fp64 sum of the parts,
 // mu64[j] = sum / n_total for j < d (the sums of squares at d <= j < w stay unscaled), muT[j] = (T)mu64[j]
+// part_lo (nullable): the low words of the parts (k_colsum_part2): the sum stays a (high, low) pair to the end and the mean is ONE
+// rounding of it -- quotient, exact remainder by fma, correction; n_total is then used, not its rounded reciprocal
 template <class T>
-__global__ __launch_bounds__(256) void k_colmean_final(const double* __restrict__ part, int64_t nparts, int64_t w, int64_t d,
-                                                       double inv_n, double* __restrict__ mu64, T* __restrict__ muT) {
-    __shared__ double red[32][9];
+__global__ __launch_bounds__(256) void k_colmean_final(const double* __restrict__ part, const double* __restrict__ part_lo, int64_t nparts,
+                                                       int64_t w, int64_t d, double inv_n, double n_total, double* __restrict__ mu64,
+                                                       T* __restrict__ muT) {
+    __shared__ double red[32][9], redc[32][9];
     const int e = threadIdx.x & 7, pl = threadIdx.x >> 3;  // 8 outputs x 32 part-lanes per block
     const int64_t j = (int64_t)blockIdx.x * 8 + e;
-    double acc = 0;
-    if (j < w)
-        for (int64_t p = pl; p < nparts; p += 32) acc += part[p * w + j];
-    red[pl][e] = acc;
+    const bool pairs = sizeof(T) == 8 && part_lo;
+    double acc = 0, lo = 0;
+    if (j < w) {
+        if (pairs) {
+            for (int64_t p = pl; p < nparts; p += 32) { two_sum_acc(acc, lo, part[p * w + j]); lo += part_lo[p * w + j]; }
+        } else {
+            for (int64_t p = pl; p < nparts; p += 32) acc += part[p * w + j];
+        }
+    }
+    red[pl][e] = acc; redc[pl][e] = lo;
     __syncthreads();
     if (pl == 0 && j < w) {
         double t = 0;
+        if (pairs) {
+            double c = 0;
 #pragma unroll
-        for (int k = 0; k < 32; ++k) t += red[k][e];
-        if (j < d) { t *= inv_n; muT[j] = (T)t; }
+            for (int k = 0; k < 32; ++k) { two_sum_acc(t, c, red[k][e]); c += redc[k][e]; }
+            if (j < d) {
+                const double q = t / n_total;
+                t = q + (fma(-q, n_total, t) + c) / n_total;
+                muT[j] = (T)t;
+            } else {
+                t += c;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 32; ++k) t += red[k][e];
+            if (j < d) { t *= inv_n; muT[j] = (T)t; }
+        }
         mu64[j] = t;
     }
 }
