@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
+from contextlib import contextmanager as _contextmanager
 from typing import Optional
 
 import numpy as np
@@ -258,6 +259,12 @@ ABI_NMF_CD = [
     ("petal_nmf_cd_hupdate", C.c_int, [_P, C.c_int64, C.c_int64, _D, _D, _D, _NS, _D, _D, _L]),
 ]
 
+# header file name (include/) -> its table, in the order the headers were added: what load_library types and the tests check
+ABI_TABLES = {"petal_hip.h": ABI, "petal_hip_score.h": ABI_SCORE, "petal_hip_segments.h": ABI_SEGMENTS, "petal_hip_probe.h": ABI_PROBE,
+              "petal_hip_sparse.h": ABI_SPARSE, "petal_hip_ipca.h": ABI_IPCA, "petal_hip_wide.h": ABI_WIDE, "petal_hip_kpca.h": ABI_KPCA,
+              "petal_hip_nmf.h": ABI_NMF, "petal_hip_nmf_sparse.h": ABI_NMF_SPARSE, "petal_hip_nmf_kl.h": ABI_NMF_KL,
+              "petal_hip_nmf_kl_dense.h": ABI_NMF_KL_DENSE, "petal_hip_nmf_cd.h": ABI_NMF_CD}
+
 
 def _preload_torch_hip_runtime():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64 and load them by the unversioned
@@ -275,7 +282,7 @@ def _preload_torch_hip_runtime():
 
 
 def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CDLL:
-    """dlopen a library implementing include/petal_hip.h, petal_hip_score.h, petal_hip_segments.h, petal_hip_sparse.h, petal_hip_ipca.h, petal_hip_wide.h, petal_hip_kpca.h, petal_hip_nmf.h, petal_hip_nmf_sparse.h, petal_hip_nmf_kl.h, petal_hip_nmf_kl_dense.h, petal_hip_nmf_cd.h and petal_hip_probe.h and type its entry points."""
+    """dlopen a library implementing every header in ``ABI_TABLES`` (include/) and type its entry points."""
     path = path or os.environ.get("PETAL_HIP_LIBRARY") or DEFAULT_LIBRARY
     if not os.path.exists(path):
         raise RuntimeError(
@@ -284,7 +291,7 @@ def load_library(path: Optional[str] = None, preload_torch: bool = True) -> C.CD
     if preload_torch:
         _preload_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, res, args in ABI + ABI_SCORE + ABI_SEGMENTS + ABI_PROBE + ABI_SPARSE + ABI_IPCA + ABI_WIDE + ABI_KPCA + ABI_NMF + ABI_NMF_SPARSE + ABI_NMF_KL + ABI_NMF_KL_DENSE + ABI_NMF_CD:
+    for name, res, args in (entry for table in ABI_TABLES.values() for entry in table):
         fn = getattr(lib, name)  # AttributeError if the library does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -359,11 +366,35 @@ def _alloc_like(x, rows, cols, dtype_code):
     return np.empty((rows, cols), dtype=_np_dtype(dtype_code))
 
 
+def _out_like(x, rows, cols, dtype_code, keep):
+    """(output array in the memory space of x, its petal_matrix)"""
+    y = _alloc_like(x, rows, cols, dtype_code)
+    return y, describe(y, keep)
+
+
 def _host(a, dtype_code, shape=None):
     out = np.ascontiguousarray(np.asarray(a, dtype=_np_dtype(dtype_code)))
     if shape is not None and out.shape != tuple(shape):
         raise InvalidInput(f"expected shape {tuple(shape)}, got {out.shape}")
     return out
+
+
+def _f64c(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def _dp(a):
+    """a float64 array as `double*`; None stays NULL"""
+    return a.ctypes.data_as(_D) if a is not None else None
+
+
+def _ref(m):
+    """byref of a ctypes value; None stays NULL"""
+    return C.byref(m) if m is not None else None
+
+
+def _with_info(out, info, want_info, keys=("kernel",)):
+    return (out, {k: int(v) for k, v in zip(keys, info)}) if want_info else out
 
 
 class Context:
@@ -378,15 +409,13 @@ class Context:
             raise DeviceError(f"petal_ctx_create(device={device}) failed with code {rc}: no usable gfx950 device? "
                               f"(library {getattr(self.lib, '_petal_path', '?')})")
         self.rank, self.world_size = 0, 1
-        self._csr = weakref.WeakSet()   # the sparse matrices resident with this ctx: released before it
-        self._ipca = weakref.WeakSet()  # ... and the IncrementalPca statistics
-        self._kpca = weakref.WeakSet()  # ... and the fitted KernelPca models
-        self._nmf = weakref.WeakSet()   # ... and the fitted Nmf models
+        self._owned = weakref.WeakSet()   # what lives with this ctx and is released before it: sparse matrices, IncrementalPca
+        #                                   statistics, fitted KernelPca and Nmf models (_HandleOwner._adopt)
+        self._nmf = self._owned           # (the name tests/nmf_kl_dense_cases.py registers a hand-made Nmf under: the same set)
 
     def close(self):
         if getattr(self, "_h", None):
-            for m in list(getattr(self, "_csr", ())) + list(getattr(self, "_ipca", ())) + list(getattr(self, "_kpca", ())) + \
-                    list(getattr(self, "_nmf", ())):
+            for m in list(getattr(self, "_owned", ())):
                 m.close()
             self.lib.petal_ctx_destroy(self._h)
             self._h = None
@@ -535,6 +564,68 @@ def default_context() -> Context:
     return _default_ctx
 
 
+class _CtxUser:
+    """what works on the ctx its constructor was given (``self.ctx``) or, failing that, on the default one from the first use on"""
+
+    def _ctx(self) -> Context:
+        if self.ctx is None:
+            self.ctx = default_context()
+        return self.ctx
+
+    @_contextmanager
+    def _sparse(self, x):
+        """x as a CsrMatrix on this model's ctx; one made here is released when the block is over."""
+        if isinstance(x, CsrMatrix):
+            if self.ctx is None:
+                self.ctx = x.ctx
+            yield x
+            return
+        sx = CsrMatrix.from_scipy_like(x, ctx=self._ctx())
+        try:
+            yield sx
+        finally:
+            sx.close()
+
+
+class _HandleOwner(_CtxUser):
+    """what owns a handle of the library that lives with its ctx; a subclass names the entry that destroys the handle and the message
+    of a missing one"""
+    _destroy = None     # "petal_..._destroy"
+    _no_handle = None   # the InvalidInput message when there is no handle
+
+    def _adopt(self, ctx, handle):
+        self.close()
+        self._h = handle
+        ctx._owned.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            getattr(self.ctx.lib, self._destroy)(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise InvalidInput(self._no_handle)
+        return self._h
+
+
+class _FitsWithY:
+    """fit / fit_transform of a model whose ``_inner_fit(x, want_y)`` takes nothing else"""
+
+    def fit(self, x):
+        self._inner_fit(x, False)
+        return self
+
+    def fit_transform(self, x):
+        return self._inner_fit(x, True)
+
+
 
 # ---- serde interchange (the crate's `serde` feature, Cargo.toml:41-47): models as the JSON serde_json writes for the
 # reference structs -- same field names and order (src/pca.rs:41-51, 317-329; src/ica.rs:41-50), ndarray's
@@ -566,12 +657,14 @@ def _is_sparse(x) -> bool:
     return all(hasattr(x, a) for a in ("data", "indices", "indptr", "shape"))
 
 
-class CsrMatrix:
+class CsrMatrix(_HandleOwner):
     """A sparse matrix in CSR form, resident with its ctx (``petal_csr``, include/petal_hip_sparse.h): the arrays are checked, the
     transposed image and the work items of both images are built on the host, and both images are uploaded once.  ``RandomizedPca.fit``,
     ``fit_transform`` and ``transform`` take it in place of a dense matrix.  An extension beyond the crate.
 
     ``indices`` inside a row need not be sorted, duplicates act as their sum, explicit zeros, empty rows and empty columns are legal."""
+
+    _destroy, _no_handle = "petal_csr_destroy", "the sparse matrix was closed (or its ctx was)"
 
     def __init__(self, data, indices, indptr, shape, ctx: Optional["Context"] = None):
         data = np.asarray(data)
@@ -595,11 +688,10 @@ class CsrMatrix:
         self.ctx = ctx if ctx is not None else default_context()
         self.shape, self.nnz, self.dtype = (rows, cols), int(data.size), data.dtype
         self._dt = PETAL_F32 if data.dtype == np.float32 else PETAL_F64
-        self._h = C.c_void_p()
-        lib = self.ctx.lib
-        self.ctx.check(lib.petal_csr_create(self.ctx._h, rows, cols, self.nnz, ptr.ctypes.data_as(_L), idx.ctypes.data_as(_I32),
-                                            data.ctypes.data, self._dt, C.byref(self._h)))
-        self.ctx._csr.add(self)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.petal_csr_create(self.ctx._h, rows, cols, self.nnz, ptr.ctypes.data_as(_L), idx.ctypes.data_as(_I32),
+                                                     data.ctypes.data, self._dt, C.byref(h)))
+        self._adopt(self.ctx, h)
 
     @classmethod
     def from_scipy_like(cls, obj, ctx: Optional["Context"] = None):
@@ -607,22 +699,6 @@ class CsrMatrix:
         if isinstance(obj, cls):
             return obj
         return cls(obj.data, obj.indices, obj.indptr, obj.shape, ctx=ctx)
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx.lib.petal_csr_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not self._h:
-            raise InvalidInput("the sparse matrix was closed (or its ctx was)")
-        return self._h
 
     def info(self) -> dict:
         out = (C.c_int64 * 8)()
@@ -651,7 +727,7 @@ class CsrMatrix:
 def csr_gemm(x: "CsrMatrix", p, transposed: bool = False, a=None, s=None):
     """Test aid (``petal_csr_gemm``): ``x @ p`` or ``x.T @ p`` through the sparse product, minus ``outer(a, s)`` when ``s`` is given
     (``a`` defaults to ones) -- the implicit centring.  float64 in and out; a float32 matrix rounds ``p`` and the result to float32."""
-    p = np.ascontiguousarray(np.asarray(p, dtype=np.float64))
+    p = _f64c(p)
     rows, inner = (x.shape[1], x.shape[0]) if transposed else x.shape
     if p.ndim != 2 or p.shape[0] != inner:
         raise InvalidInput(f"expected {inner} rows in p")
@@ -660,9 +736,7 @@ def csr_gemm(x: "CsrMatrix", p, transposed: bool = False, a=None, s=None):
     a = None if a is None else _host(a, PETAL_F64, (rows,))
     s = None if s is None else _host(s, PETAL_F64, (N,))
     ctx = x.ctx
-    ctx.check(ctx.lib.petal_csr_gemm(ctx._h, x._handle(), int(bool(transposed)), p.ctypes.data_as(_D), N,
-                                     a.ctypes.data_as(_D) if a is not None else None, s.ctypes.data_as(_D) if s is not None else None,
-                                     out.ctypes.data_as(_D)))
+    ctx.check(ctx.lib.petal_csr_gemm(ctx._h, x._handle(), int(bool(transposed)), _dp(p), N, _dp(a), _dp(s), _dp(out)))
     return out
 
 
@@ -676,9 +750,8 @@ def row_gram(x, centre=None, ctx: Optional["Context"] = None, want_info: bool = 
     cen = None if centre is None else _host(centre, PETAL_F64, (mx.cols,))
     out = np.zeros((mx.rows, mx.rows))
     info = (C.c_int64 * 2)()
-    ctx.check(ctx.lib.petal_row_gram(ctx._h, C.byref(mx), cen.ctypes.data_as(_D) if cen is not None else None, out.ctypes.data_as(_D),
-                                     info))
-    return (out, {"kernel": int(info[0]), "chunks": int(info[1])}) if want_info else out
+    ctx.check(ctx.lib.petal_row_gram(ctx._h, C.byref(mx), _dp(cen), _dp(out), info))
+    return _with_info(out, info, want_info, ("kernel", "chunks"))
 
 
 def _kernel_spec(kernel, gamma, degree, coef0) -> petal_kernel_spec:
@@ -704,12 +777,11 @@ def kernel_apply(xq, xt, a, kernel="linear", gamma=None, degree=3, coef0=1.0, ce
     cen = None if centre is None else _host(centre, PETAL_F64, (mt.cols,))
     out = np.zeros((mq.rows, a.shape[1]))
     info = (C.c_int64 * 1)()
-    ctx.check(ctx.lib.petal_kernel_apply(ctx._h, C.byref(mq), C.byref(mt), C.byref(spec), a.ctypes.data_as(_D), a.shape[1],
-                                         cen.ctypes.data_as(_D) if cen is not None else None, out.ctypes.data_as(_D), info))
-    return (out, {"kernel": int(info[0])}) if want_info else out
+    ctx.check(ctx.lib.petal_kernel_apply(ctx._h, C.byref(mq), C.byref(mt), C.byref(spec), _dp(a), a.shape[1], _dp(cen), _dp(out), info))
+    return _with_info(out, info, want_info)
 
 
-class KernelPca:
+class KernelPca(_HandleOwner, _FitsWithY):
     """Kernel PCA (``petal_kpca``, include/petal_hip_kpca.h; an extension beyond the crate, DESIGN.md sections 4 and 7) -- scikit-learn's
     ``KernelPCA`` with the kernels ``linear``, ``poly``, ``rbf``, ``sigmoid`` and ``cosine``.  ``gamma=None`` (or <= 0) means 1 / d.
     ``fit_transform`` = V sqrt(lambda); ``transform`` is one fused pass over the query rows whose m x n kernel matrix never touches
@@ -717,33 +789,14 @@ class KernelPca:
     (1e-6 float32, 1e-10 float64, on sqrt(lambda)) is a zero column of both outputs.  The fitted model lives with its ctx and keeps its
     own device copy of the training rows."""
 
+    _destroy, _no_handle = "petal_kpca_destroy", "the model has not been fitted (or its ctx was closed)"
+
     def __init__(self, n_components: int, kernel: str = "linear", gamma=None, degree: int = 3, coef0: float = 1.0,
                  ctx: Optional[Context] = None):
         self._k = int(n_components)
         self.kernel, self.gamma, self.degree, self.coef0 = kernel, gamma, int(degree), float(coef0)
         self.ctx = ctx
         self._h = None
-
-    def _ctx(self) -> Context:
-        if self.ctx is None:
-            self.ctx = default_context()
-        return self.ctx
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx.lib.petal_kpca_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not self._h:
-            raise InvalidInput("the model has not been fitted (or its ctx was closed)")
-        return self._h
 
     def n_components(self):
         return self._k
@@ -753,38 +806,24 @@ class KernelPca:
         mx = describe(x, keep)
         ctx = self._ctx()
         spec = _kernel_spec(self.kernel, self.gamma, self.degree, self.coef0)
-        y, my = None, None
-        if want_y:
-            y = _alloc_like(x, mx.rows, self._k, mx.dtype)
-            my = describe(y, keep)
+        y, my = _out_like(x, mx.rows, self._k, mx.dtype, keep) if want_y else (None, None)
         h = C.c_void_p()
-        ctx.check(ctx.lib.petal_kpca_fit(ctx._h, C.byref(mx), self._k, C.byref(spec), C.byref(h), C.byref(my) if my is not None else None))
-        self.close()
-        self._h = h
-        ctx._kpca.add(self)
+        ctx.check(ctx.lib.petal_kpca_fit(ctx._h, C.byref(mx), self._k, C.byref(spec), C.byref(h), _ref(my)))
+        self._adopt(ctx, h)
         return y
-
-    def fit(self, x):
-        self._inner_fit(x, False)
-        return self
-
-    def fit_transform(self, x):
-        return self._inner_fit(x, True)
 
     def transform(self, x):
         keep = []
         mx = describe(x, keep)
         ctx = self._ctx()
-        y = _alloc_like(x, mx.rows, self._k, mx.dtype)
-        my = describe(y, keep)
+        y, my = _out_like(x, mx.rows, self._k, mx.dtype, keep)
         ctx.check(ctx.lib.petal_kpca_transform(ctx._h, self._handle(), C.byref(mx), C.byref(my)))
         return y
 
     def _get(self, lam=None, vec=None):
         h = self._handle()   # (first: an unfitted model may have no ctx yet)
         out = (C.c_int64 * 8)()
-        if self._ctx().lib.petal_kpca_get(h, lam.ctypes.data_as(_D) if lam is not None else None,
-                                       vec.ctypes.data_as(_D) if vec is not None else None, out) != PETAL_OK:
+        if self._ctx().lib.petal_kpca_get(h, _dp(lam), _dp(vec), out) != PETAL_OK:
             raise InvalidInput("petal_kpca_get failed")
         return out
 
@@ -812,29 +851,39 @@ def _nmf_spec(max_iter, tol, l1_w, l2_w, l1_h=0.0, l2_h=0.0) -> petal_nmf_spec:
     return petal_nmf_spec(int(max_iter), float(tol), float(l1_w), float(l2_w), float(l1_h), float(l2_h))
 
 
+def _nmf_pass_operands(x, w, h, ctx):
+    """the operands the three dense pass aids share: (keep, x described, ctx, w and h as contiguous float64 of matching shapes, k)"""
+    keep = []
+    mx = describe(x, keep)
+    ctx = ctx or default_context()
+    w, h = _f64c(w), _f64c(h)
+    if w.ndim != 2 or h.ndim != 2 or w.shape[0] != mx.rows or h.shape != (w.shape[1], mx.cols):
+        raise InvalidInput(f"w should be {mx.rows} x k and h k x {mx.cols}")
+    return keep, mx, ctx, w, h, w.shape[1]
+
+
+def _nmf_sweep_operands(sx, g, f, transposed):
+    """the operands the two sweep aids share: (rows of the image swept, g and f as contiguous float64 of matching shapes, k)"""
+    rows, inner = (sx.shape[1], sx.shape[0]) if transposed else sx.shape
+    g, f = _f64c(g), _f64c(f)
+    if g.ndim != 2 or f.ndim != 2 or g.shape[0] != rows or f.shape != (inner, g.shape[1]):
+        raise InvalidInput(f"g should be {rows} x k and f {inner} x k")
+    return rows, g, f, g.shape[1]
+
+
 def nmf_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, want_ab=True, ctx: Optional["Context"] = None, want_info: bool = False):
     """Test aid (``petal_nmf_pass``, include/petal_hip_nmf.h): the fused pass of an ``Nmf`` iteration by itself, in float64.  ``x``
     (n x d): numpy or ``torch.cuda``, any strides; ``w`` (n x k), ``h`` (k x d): float64.  Z = x h^T once, then ``inner_iters`` times
     D = W (h h^T) + l1_w + l2_w W, D[D == 0] = 2^-23, W <- W o Z / D.  Returns ``(w_new, a, b)`` with a = w_new^T x and
     b = w_new^T w_new (``want_ab=False``: ``w_new`` alone).  ``want_info``: also ``{"kernel": k_nmf_pass ran}``."""
-    keep = []
-    mx = describe(x, keep)
-    ctx = ctx or default_context()
-    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
-    h = np.ascontiguousarray(np.asarray(h, dtype=np.float64))
-    if w.ndim != 2 or h.ndim != 2 or w.shape[0] != mx.rows or h.shape != (w.shape[1], mx.cols):
-        raise InvalidInput(f"w should be {mx.rows} x k and h k x {mx.cols}")
-    k = w.shape[1]
+    keep, mx, ctx, w, h, k = _nmf_pass_operands(x, w, h, ctx)
     spec = _nmf_spec(1, 0.0, l1_w, l2_w)
     wo = np.zeros((mx.rows, k))
     a = np.zeros((k, mx.cols)) if want_ab else None
     b = np.zeros((k, k)) if want_ab else None
     info = (C.c_int64 * 1)()
-    ctx.check(ctx.lib.petal_nmf_pass(ctx._h, C.byref(mx), k, w.ctypes.data_as(_D), h.ctypes.data_as(_D), C.byref(spec), int(inner_iters),
-                                     wo.ctypes.data_as(_D), a.ctypes.data_as(_D) if want_ab else None,
-                                     b.ctypes.data_as(_D) if want_ab else None, info))
-    out = (wo, a, b) if want_ab else wo
-    return (out, {"kernel": int(info[0])}) if want_info else out
+    ctx.check(ctx.lib.petal_nmf_pass(ctx._h, C.byref(mx), k, _dp(w), _dp(h), C.byref(spec), int(inner_iters), _dp(wo), _dp(a), _dp(b), info))
+    return _with_info((wo, a, b) if want_ab else wo, info, want_info)
 
 
 def nmf_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0, inner_iters=1, want_gram=True, want_info: bool = False):
@@ -843,23 +892,16 @@ def nmf_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0, i
     z_r = sum over the stored entries of row r of val f[idx], then ``inner_iters`` times D = g_r (f^T f) + l1 + l2 g_r,
     D[D == 0] = 2^-23, g_r <- g_r o z_r / D.  Returns ``(g_new, gram, dot)`` with gram = g_new^T g_new and dot = sum_r <z_r, g_new_r>
     (``want_gram=False``: ``g_new`` alone).  ``want_info``: also ``{"kernel": k_nmf_sweep ran}``."""
-    rows, inner = (sx.shape[1], sx.shape[0]) if transposed else sx.shape
-    g = np.ascontiguousarray(np.asarray(g, dtype=np.float64))
-    f = np.ascontiguousarray(np.asarray(f, dtype=np.float64))
-    if g.ndim != 2 or f.ndim != 2 or g.shape[0] != rows or f.shape != (inner, g.shape[1]):
-        raise InvalidInput(f"g should be {rows} x k and f {inner} x k")
-    k = g.shape[1]
+    rows, g, f, k = _nmf_sweep_operands(sx, g, f, transposed)
     spec = _nmf_spec(1, 0.0, l1, l2)
     go = np.zeros((rows, k))
     gram = np.zeros((k, k)) if want_gram else None
     dot = np.zeros(1) if want_gram else None
     info = (C.c_int64 * 1)()
     ctx = sx.ctx
-    ctx.check(ctx.lib.petal_nmf_sweep_csr(ctx._h, sx._handle(), int(bool(transposed)), k, g.ctypes.data_as(_D), f.ctypes.data_as(_D),
-                                          C.byref(spec), int(inner_iters), go.ctypes.data_as(_D),
-                                          gram.ctypes.data_as(_D) if want_gram else None, dot.ctypes.data_as(_D) if want_gram else None, info))
-    out = (go, gram, float(dot[0])) if want_gram else go
-    return (out, {"kernel": int(info[0])}) if want_info else out
+    ctx.check(ctx.lib.petal_nmf_sweep_csr(ctx._h, sx._handle(), int(bool(transposed)), k, _dp(g), _dp(f), C.byref(spec), int(inner_iters),
+                                          _dp(go), _dp(gram), _dp(dot), info))
+    return _with_info((go, gram, float(dot[0])) if want_gram else go, info, want_info)
 
 
 def nmf_kl_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0, inner_iters=1, want_term: Optional[bool] = None,
@@ -870,23 +912,16 @@ def nmf_kl_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0
     num = sum val / wh f[idx], den = c + l1 + l2 g_r, den[den == 0] = 2^-23, g_r <- g_r o num / den.  Returns ``(g_new, colsum)`` with
     colsum = the column sums of g_new; with ``inner_iters=0`` (``want_term`` defaults to that) ``(g, colsum, term)`` with
     term = sum [val > 2^-23] val log(val / wh).  ``want_info``: also ``{"kernel": k_nmf_kl_sweep ran}``."""
-    rows, inner = (sx.shape[1], sx.shape[0]) if transposed else sx.shape
-    g = np.ascontiguousarray(np.asarray(g, dtype=np.float64))
-    f = np.ascontiguousarray(np.asarray(f, dtype=np.float64))
-    if g.ndim != 2 or f.ndim != 2 or g.shape[0] != rows or f.shape != (inner, g.shape[1]):
-        raise InvalidInput(f"g should be {rows} x k and f {inner} x k")
-    k = g.shape[1]
+    rows, g, f, k = _nmf_sweep_operands(sx, g, f, transposed)
     if want_term is None:
         want_term = int(inner_iters) == 0
     spec = _nmf_spec(1, 0.0, l1, l2)
     go, colsum, term = np.zeros((rows, k)), np.zeros(k), np.zeros(1)
     info = (C.c_int64 * 1)()
     ctx = sx.ctx
-    ctx.check(ctx.lib.petal_nmf_kl_sweep_csr(ctx._h, sx._handle(), int(bool(transposed)), k, g.ctypes.data_as(_D), f.ctypes.data_as(_D),
-                                             C.byref(spec), int(inner_iters), go.ctypes.data_as(_D), colsum.ctypes.data_as(_D),
-                                             term.ctypes.data_as(_D) if want_term else None, info))
-    out = (go, colsum, float(term[0])) if want_term else (go, colsum)
-    return (out, {"kernel": int(info[0])}) if want_info else out
+    ctx.check(ctx.lib.petal_nmf_kl_sweep_csr(ctx._h, sx._handle(), int(bool(transposed)), k, _dp(g), _dp(f), C.byref(spec), int(inner_iters),
+                                             _dp(go), _dp(colsum), _dp(term) if want_term else None, info))
+    return _with_info((go, colsum, float(term[0])) if want_term else (go, colsum), info, want_info)
 
 
 def nmf_kl_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, want_a=True, want_term: Optional[bool] = None,
@@ -897,24 +932,16 @@ def nmf_kl_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, want_a=True, want_te
     W <- W o (((x / WH) h^T) / den).  Returns ``(w_new, a, colsum)`` with a = w_new^T (x / max(w_new h, 2^-23)) and colsum = the column
     sums of w_new (``want_a=False``: ``w_new`` alone); with ``inner_iters=0`` (``want_term`` defaults to that) ``(w, a, colsum, term)``
     with term = sum [x > 2^-23] x log(x / WH).  ``want_info``: also ``{"kernel": k_nmf_kl_pass ran}``."""
-    keep = []
-    mx = describe(x, keep)
-    ctx = ctx or default_context()
-    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
-    h = np.ascontiguousarray(np.asarray(h, dtype=np.float64))
-    if w.ndim != 2 or h.ndim != 2 or w.shape[0] != mx.rows or h.shape != (w.shape[1], mx.cols):
-        raise InvalidInput(f"w should be {mx.rows} x k and h k x {mx.cols}")
-    k = w.shape[1]
+    keep, mx, ctx, w, h, k = _nmf_pass_operands(x, w, h, ctx)
     if want_term is None:
         want_term = int(inner_iters) == 0
     spec = _nmf_spec(1, 0.0, l1_w, l2_w)
     wo, a, colsum, term = np.zeros((mx.rows, k)), np.zeros((k, mx.cols)), np.zeros(k), np.zeros(1)
     info = (C.c_int64 * 1)()
-    ctx.check(ctx.lib.petal_nmf_kl_pass(ctx._h, C.byref(mx), k, w.ctypes.data_as(_D), h.ctypes.data_as(_D), C.byref(spec), int(inner_iters),
-                                        wo.ctypes.data_as(_D), a.ctypes.data_as(_D) if want_a else None,
-                                        colsum.ctypes.data_as(_D) if want_a else None, term.ctypes.data_as(_D) if want_term else None, info))
+    ctx.check(ctx.lib.petal_nmf_kl_pass(ctx._h, C.byref(mx), k, _dp(w), _dp(h), C.byref(spec), int(inner_iters), _dp(wo),
+                                        _dp(a) if want_a else None, _dp(colsum) if want_a else None, _dp(term) if want_term else None, info))
     out = ((wo, a, colsum, float(term[0])) if want_term else (wo, a, colsum)) if want_a or want_term else wo
-    return (out, {"kernel": int(info[0])}) if want_info else out
+    return _with_info(out, info, want_info)
 
 
 def nmf_cd_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, from_zero: bool = False, want_ab=True, ctx: Optional["Context"] = None,
@@ -924,25 +951,16 @@ def nmf_cd_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, from_zero: bool = Fa
     then ``inner_iters`` Gauss-Seidel sweeps of every row of W with S = h h^T + l2_w I and z = Z - l1_w (``from_zero``: W starts as
     zeros).  Returns ``(w_new, a, b, violation)`` with a = w_new^T x, b = w_new^T w_new and violation = one sum of |pg| per sweep
     (``want_ab=False``: ``(w_new, violation)``).  ``want_info``: also ``{"kernel": k_nmf_cd_pass ran}``."""
-    keep = []
-    mx = describe(x, keep)
-    ctx = ctx or default_context()
-    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
-    h = np.ascontiguousarray(np.asarray(h, dtype=np.float64))
-    if w.ndim != 2 or h.ndim != 2 or w.shape[0] != mx.rows or h.shape != (w.shape[1], mx.cols):
-        raise InvalidInput(f"w should be {mx.rows} x k and h k x {mx.cols}")
-    k = w.shape[1]
+    keep, mx, ctx, w, h, k = _nmf_pass_operands(x, w, h, ctx)
     spec = _nmf_spec(1, 0.0, l1_w, l2_w)
     wo = np.zeros((mx.rows, k))
     a = np.zeros((k, mx.cols)) if want_ab else None
     b = np.zeros((k, k)) if want_ab else None
     viol = np.zeros(max(int(inner_iters), 0))
     info = (C.c_int64 * 1)()
-    ctx.check(ctx.lib.petal_nmf_cd_pass(ctx._h, C.byref(mx), k, w.ctypes.data_as(_D), h.ctypes.data_as(_D), C.byref(spec), int(inner_iters),
-                                        int(bool(from_zero)), wo.ctypes.data_as(_D), a.ctypes.data_as(_D) if want_ab else None,
-                                        b.ctypes.data_as(_D) if want_ab else None, viol.ctypes.data_as(_D) if viol.size else None, info))
-    out = (wo, a, b, viol) if want_ab else (wo, viol)
-    return (out, {"kernel": int(info[0])}) if want_info else out
+    ctx.check(ctx.lib.petal_nmf_cd_pass(ctx._h, C.byref(mx), k, _dp(w), _dp(h), C.byref(spec), int(inner_iters), int(bool(from_zero)),
+                                        _dp(wo), _dp(a), _dp(b), _dp(viol) if viol.size else None, info))
+    return _with_info((wo, a, b, viol) if want_ab else (wo, viol), info, want_info)
 
 
 def nmf_cd_hupdate(a, b, h, l1_h=0.0, l2_h=0.0, ctx: Optional["Context"] = None, want_info: bool = False):
@@ -950,17 +968,15 @@ def nmf_cd_hupdate(a, b, h, l1_h=0.0, l2_h=0.0, ctx: Optional["Context"] = None,
     in float64: one sweep of every row of h^T with S = b + l2_h I and z = a[:, j] - l1_h.  ``a``, ``h`` (k x d), ``b`` (k x k).
     Returns ``(h_new, violation)``.  ``want_info``: also ``{"kernel": k_nmf_cd_hrule ran}``."""
     ctx = ctx or default_context()
-    a, b, h = (np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for v in (a, b, h))
+    a, b, h = _f64c(a), _f64c(b), _f64c(h)
     if a.ndim != 2 or a.shape != h.shape or b.shape != (a.shape[0], a.shape[0]):
         raise InvalidInput("a and h should be k x d and b k x k")
     k, d = a.shape
     spec = _nmf_spec(1, 0.0, 0.0, 0.0, l1_h, l2_h)
     ho, viol = np.zeros((k, d)), np.zeros(1)
     info = (C.c_int64 * 1)()
-    ctx.check(ctx.lib.petal_nmf_cd_hupdate(ctx._h, k, d, a.ctypes.data_as(_D), b.ctypes.data_as(_D), h.ctypes.data_as(_D), C.byref(spec),
-                                           ho.ctypes.data_as(_D), viol.ctypes.data_as(_D), info))
-    out = (ho, float(viol[0]))
-    return (out, {"kernel": int(info[0])}) if want_info else out
+    ctx.check(ctx.lib.petal_nmf_cd_hupdate(ctx._h, k, d, _dp(a), _dp(b), _dp(h), C.byref(spec), _dp(ho), _dp(viol), info))
+    return _with_info((ho, float(viol[0])), info, want_info)
 
 
 def _like_input(x, w):
@@ -997,7 +1013,7 @@ class _DenseAsCsr:
         self.data, self.indices, self.shape = x[r, c], c.astype(np.int32), x.shape
 
 
-class Nmf:
+class Nmf(_HandleOwner):
     """Non-negative matrix factorisation X ~ W H (``petal_nmf``, include/petal_hip_nmf.h; an extension beyond the crate, DESIGN.md
     sections 4 and 7) -- scikit-learn's ``NMF(solver="mu", beta_loss="frobenius")``.  ``fit``, ``fit_transform`` and ``transform``
     also take a ``CsrMatrix`` or any object with ``.data / .indices / .indptr / .shape`` (include/petal_hip_nmf_sparse.h).  ``init="random"`` draws W0 and H0 from
@@ -1024,6 +1040,8 @@ class Nmf:
     iterations), ``transform`` from W = 0 with exactly ``max_iter`` sweeps.  ``"cd"`` with the Kullback-Leibler loss or with sparse
     input is ``InvalidInput``.  ``solver`` is readable."""
 
+    _destroy, _no_handle = "petal_nmf_destroy", "the model has not been fitted (or its ctx was closed)"
+
     def __init__(self, n_components: int, max_iter: int = 200, tol: float = 1e-4, init: str = "random", seed: int = 0,
                  alpha_W: float = 0.0, alpha_H="same", l1_ratio: float = 0.0, ctx: Optional[Context] = None, beta_loss="frobenius",
                  dense_path: str = "compress", solver: str = "mu"):
@@ -1046,27 +1064,6 @@ class Nmf:
         self._h = None
         self.kernel_path = None   # the last fit / transform on sparse input: 1 the sweep kernel ran, 0 the call densified
 
-    def _ctx(self) -> Context:
-        if self.ctx is None:
-            self.ctx = default_context()
-        return self.ctx
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx.lib.petal_nmf_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not self._h:
-            raise InvalidInput("the model has not been fitted (or its ctx was closed)")
-        return self._h
-
     def n_components(self):
         return self._k
 
@@ -1077,14 +1074,6 @@ class Nmf:
             raise InvalidInput("alpha_H should be a number or 'same'")
         rho = self.l1_ratio
         return _nmf_spec(self.max_iter, self.tol, d * a_w * rho, d * a_w * (1.0 - rho), n * a_h * rho, n * a_h * (1.0 - rho))
-
-    def _sparse(self, x):
-        """x as a CsrMatrix on this model's ctx, and whether it was made here (and is released when the call is over)."""
-        if isinstance(x, CsrMatrix):
-            if self.ctx is None:
-                self.ctx = x.ctx
-            return x, False
-        return CsrMatrix.from_scipy_like(x, ctx=self._ctx()), True
 
     def _start(self, dtype_code, W, H, keep):
         """(w0, h0) as petal_matrix descriptions (init="custom") or (None, None)"""
@@ -1101,8 +1090,7 @@ class Nmf:
     def _inner_fit_sparse(self, x, W, H, want_w: bool):
         """fit / fit_transform on sparse input (include/petal_hip_nmf_sparse.h): X is never densified where the sweep kernel runs;
         ``kernel_path`` says whether it did (1) or the library densified and ran the dense fit (0)."""
-        sx, mine = self._sparse(x)
-        try:
+        with self._sparse(x) as sx:
             ctx = self._ctx()
             rows, cols = sx.shape
             spec = self._spec(rows, cols)
@@ -1113,20 +1101,14 @@ class Nmf:
                 w = np.empty((rows, self._k), dtype=_np_dtype(sx._dt))
                 mo = describe(w, keep)
             h, path = C.c_void_p(), C.c_int64(0)
-            args = (C.byref(mw) if mw is not None else None, C.byref(mh) if mh is not None else None,
-                    C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h), C.byref(mo) if mo is not None else None, C.byref(path))
+            args = (_ref(mw), _ref(mh), C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h), _ref(mo), C.byref(path))
             if self._loss == NMF_LOSS_FROBENIUS:
                 ctx.check(ctx.lib.petal_nmf_fit_csr(ctx._h, sx._handle(), self._k, C.byref(spec), *args))
             else:
                 ctx.check(ctx.lib.petal_nmf_fit_csr_loss(ctx._h, sx._handle(), self._k, C.byref(spec), self._loss, *args))
-            self.close()
-            self._h = h
-            ctx._nmf.add(self)
+            self._adopt(ctx, h)
             self.kernel_path = int(path.value)
             return w
-        finally:
-            if mine:
-                sx.close()
 
     def _inner_fit(self, x, W, H, want_w: bool):
         if self.solver == "cd" and _is_sparse(x):
@@ -1141,22 +1123,16 @@ class Nmf:
         ctx = self._ctx()
         spec = self._spec(mx.rows, mx.cols)
         mw, mh = self._start(mx.dtype, W, H, keep)
-        w, mo = None, None
-        if want_w:
-            w = _alloc_like(x, mx.rows, self._k, mx.dtype)
-            mo = describe(w, keep)
+        w, mo = _out_like(x, mx.rows, self._k, mx.dtype, keep) if want_w else (None, None)
         h = C.c_void_p()
-        args = (C.byref(mw) if mw is not None else None, C.byref(mh) if mh is not None else None,
-                C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h), C.byref(mo) if mo is not None else None)
+        args = (_ref(mw), _ref(mh), C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h), _ref(mo))
         if self.solver == "cd":   # include/petal_hip_nmf_cd.h
             ctx.check(ctx.lib.petal_nmf_fit_solver(ctx._h, C.byref(mx), self._k, C.byref(spec), NMF_SOLVER_CD, *args))
         elif self._loss == NMF_LOSS_FROBENIUS:
             ctx.check(ctx.lib.petal_nmf_fit(ctx._h, C.byref(mx), self._k, C.byref(spec), *args))
         else:   # dense_path="fused" (include/petal_hip_nmf_kl_dense.h)
             ctx.check(ctx.lib.petal_nmf_fit_loss(ctx._h, C.byref(mx), self._k, C.byref(spec), self._loss, *args))
-        self.close()
-        self._h = h
-        ctx._nmf.add(self)
+        self._adopt(ctx, h)
         if self._loss != NMF_LOSS_FROBENIUS:
             self.kernel_path = self.info()["fit_kernel"]
         return w
@@ -1176,8 +1152,7 @@ class Nmf:
         if dense_kl and self.dense_path == "compress":
             return _like_input(x, self.transform(_DenseAsCsr(x)))
         if _is_sparse(x):
-            sx, mine = self._sparse(x)
-            try:
+            with self._sparse(x) as sx:
                 ctx = self._ctx()
                 keep = []
                 w = np.empty((sx.shape[0], self._k), dtype=_np_dtype(sx._dt))
@@ -1186,14 +1161,10 @@ class Nmf:
                 ctx.check(ctx.lib.petal_nmf_transform_csr(ctx._h, self._handle(), sx._handle(), C.byref(mo), C.byref(path)))
                 self.kernel_path = int(path.value)
                 return w
-            finally:
-                if mine:
-                    sx.close()
         keep = []
         mx = describe(x, keep)
         ctx = self._ctx()
-        w = _alloc_like(x, mx.rows, self._k, mx.dtype)
-        mo = describe(w, keep)
+        w, mo = _out_like(x, mx.rows, self._k, mx.dtype, keep)
         if dense_kl:   # dense_path="fused" (include/petal_hip_nmf_kl_dense.h)
             ctx.check(ctx.lib.petal_nmf_transform_loss(ctx._h, self._handle(), C.byref(mx), C.byref(mo)))
             self.kernel_path = self.info()["transform_kernel"] if mx.rows else self.kernel_path
@@ -1205,16 +1176,14 @@ class Nmf:
         keep = []
         mw = describe(w, keep)
         ctx = self._ctx()
-        x = _alloc_like(w, mw.rows, self.info()["d"], mw.dtype)
-        mo = describe(x, keep)
+        x, mo = _out_like(w, mw.rows, self.info()["d"], mw.dtype, keep)
         ctx.check(ctx.lib.petal_nmf_inverse_transform(ctx._h, self._handle(), C.byref(mw), C.byref(mo)))
         return x
 
     def _get(self, comp=None, err=None):
         h = self._handle()   # (first: an unfitted model may have no ctx yet)
         out = (C.c_int64 * 6)()
-        if self._ctx().lib.petal_nmf_get(h, comp.ctypes.data_as(_D) if comp is not None else None, out,
-                                      err.ctypes.data_as(_D) if err is not None else None) != PETAL_OK:
+        if self._ctx().lib.petal_nmf_get(h, _dp(comp), out, _dp(err)) != PETAL_OK:
             raise InvalidInput("petal_nmf_get failed")
         return out
 
@@ -1256,7 +1225,7 @@ class Nmf:
 
 
 # ------------------------------------------------------------------------------------------------
-class _PcaModel:
+class _PcaModel(_CtxUser):
     """State shared by Pca and RandomizedPca (src/pca.rs:41-51, 317-329)."""
 
     def __init__(self, n_components: int, centering: bool = True, ctx: Optional[Context] = None):
@@ -1269,11 +1238,6 @@ class _PcaModel:
         self._total_variance = 0.0
         self.n_samples = 0
         self._dt = PETAL_F64
-
-    def _ctx(self) -> Context:
-        if self.ctx is None:
-            self.ctx = default_context()
-        return self.ctx
 
     # accessors (src/pca.rs:78-105, 392-419)
     def components(self):
@@ -1369,8 +1333,7 @@ class _PcaModel:
         d = self._means.shape[0]
         if mx.cols != d:
             raise InvalidInput(f"# of columns should be {d}")
-        y = _alloc_like(x, mx.rows, self._k, mx.dtype)
-        my = describe(y, keep)
+        y, my = _out_like(x, mx.rows, self._k, mx.dtype, keep)
         comp = _host(self._components, mx.dtype)
         mu = _host(self._means, mx.dtype)
         ctx.check(ctx.lib.petal_transform(ctx._h, C.byref(mx), comp.ctypes.data, mu.ctypes.data, self._k, d,
@@ -1385,8 +1348,7 @@ class _PcaModel:
         d = self._means.shape[0]
         if my.cols != self._k:
             raise InvalidInput(f"# of columns should be {self._k}")
-        x = _alloc_like(y, my.rows, d, my.dtype)
-        mx = describe(x, keep)
+        x, mx = _out_like(y, my.rows, d, my.dtype, keep)
         comp = _host(self._components, my.dtype)
         mu = _host(self._means, my.dtype)
         ctx.check(ctx.lib.petal_inverse_transform(ctx._h, C.byref(my), comp.ctypes.data, mu.ctypes.data, self._k, d,
@@ -1394,7 +1356,7 @@ class _PcaModel:
         return x
 
 
-class Pca(_PcaModel):
+class Pca(_PcaModel, _FitsWithY):
     """``Pca<A>`` (src/pca.rs:41-232)."""
 
     @classmethod
@@ -1419,25 +1381,14 @@ class Pca(_PcaModel):
         means = np.zeros(mx.cols, dtype=npdt)
         sing = np.zeros(self._k, dtype=npdt)
         tv = np.zeros(1, dtype=npdt)
-        y, my = None, None
-        if want_y:
-            y = _alloc_like(x, mx.rows, self._k, mx.dtype)
-            my = describe(y, keep)
+        y, my = _out_like(x, mx.rows, self._k, mx.dtype, keep) if want_y else (None, None)
         ctx.check(ctx.lib.petal_pca_fit(ctx._h, C.byref(mx), self._k, int(self.centering), comp.ctypes.data,
-                                        means.ctypes.data, sing.ctypes.data, tv.ctypes.data,
-                                        C.byref(my) if my is not None else None))
+                                        means.ctypes.data, sing.ctypes.data, tv.ctypes.data, _ref(my)))
         if not (self.centering and mx.rows == 0 and ctx.world_size == 1):
             self._store(comp, means, sing, tv, mx.rows)
         if want_y and mx.rows == 0 and self.centering:
             y = _alloc_like(x, 0, mx.cols if self._k else 0, mx.dtype)[:, : self._k]  # src/pca.rs:210
         return y
-
-    def fit(self, x):
-        self._inner_fit(x, False)
-        return self
-
-    def fit_transform(self, x):
-        return self._inner_fit(x, True)
 
     def last_route(self) -> dict:
         """``petal_pca_last_route`` (include/petal_hip_wide.h): facts of the last ``Pca`` fit on this model's ctx -- ``route`` (0 the
@@ -1460,7 +1411,7 @@ def _lazy_field(name):
     return property(get, put)
 
 
-class IncrementalPca(_PcaModel):
+class IncrementalPca(_HandleOwner, _PcaModel):
     """The exact ``Pca`` fitted batch by batch (``petal_ipca``, include/petal_hip_ipca.h; an extension beyond the crate, DESIGN.md
     section 7): ``partial_fit`` folds a batch into the float64 statistic (rows seen, mean, M2) resident with the ctx, and the model is
     what ``Pca.fit`` returns on the concatenation of the batches -- up to the SIGN of each component, which is decided from the
@@ -1481,28 +1432,14 @@ class IncrementalPca(_PcaModel):
         super().__init__(n_components, centering, ctx)
 
     # ---- the handle -------------------------------------------------------------------------------------------------------------------
+    _destroy, _no_handle = "petal_ipca_destroy", "no batch has been seen yet (or the model's ctx was closed)"
+
     def _open(self, d: int, dtype_code: int):
         ctx = self._ctx()
-        self._h = C.c_void_p()
-        ctx.check(ctx.lib.petal_ipca_create(ctx._h, int(d), int(dtype_code), int(self.centering), C.byref(self._h)))
-        ctx._ipca.add(self)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.petal_ipca_create(ctx._h, int(d), int(dtype_code), int(self.centering), C.byref(h)))
+        self._adopt(ctx, h)
         self._d, self._dt = int(d), int(dtype_code)
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx.lib.petal_ipca_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _handle(self):
-        if not self._h:
-            raise InvalidInput("no batch has been seen yet (or the model's ctx was closed)")
-        return self._h
 
     def info(self) -> dict:
         """d, dtype, centering, rows seen, batches, batches the streaming kernel took, merges."""
@@ -1567,7 +1504,7 @@ class IncrementalPca(_PcaModel):
         ctx, d = self._ctx(), self._d
         self._handle()
         n, mean, m2 = C.c_double(0), np.zeros(d), np.zeros((d, d))
-        ctx.check(ctx.lib.petal_ipca_get_state(ctx._h, self._h, C.byref(n), mean.ctypes.data_as(_D), m2.ctypes.data_as(_D)))
+        ctx.check(ctx.lib.petal_ipca_get_state(ctx._h, self._h, C.byref(n), _dp(mean), _dp(m2)))
         return {"n": float(n.value), "mean": mean, "m2": m2, "dtype": _np_dtype(self._dt), "centering": self.centering}
 
     @classmethod
@@ -1579,7 +1516,7 @@ class IncrementalPca(_PcaModel):
             raise InvalidInput("m2 should be d x d")
         m._open(mean.shape[0], PETAL_F32 if np.dtype(state["dtype"]) == np.float32 else PETAL_F64)
         c = m._ctx()
-        c.check(c.lib.petal_ipca_set_state(c._h, m._h, float(state["n"]), mean.ctypes.data_as(_D), m2.ctypes.data_as(_D)))
+        c.check(c.lib.petal_ipca_set_state(c._h, m._h, float(state["n"]), _dp(mean), _dp(m2)))
         m._dirty = True
         return m
 
@@ -1602,7 +1539,7 @@ class IncrementalPca(_PcaModel):
             self._store(comp, means, sing, tv, self.info()["n_samples_seen"])
 
 
-class SegmentedPca:
+class SegmentedPca(_CtxUser):
     """One exact Pca per row segment of a row-sorted matrix, in one call (include/petal_hip_segments.h; an extension beyond the crate,
     DESIGN.md section 7).  Segment b is rows offsets[b] .. offsets[b + 1] - 1; it gets what ``Pca.fit`` gives on those rows alone.  For
     d <= 64 the batch is one launch, a workgroup per segment; a very long segment is correct and not fast (fit it with ``Pca``)."""
@@ -1618,11 +1555,6 @@ class SegmentedPca:
         self._total_variance = np.zeros(0)
         self._status = np.zeros(0, dtype=np.int32)
         self._kernel_segments = 0
-
-    def _ctx(self) -> Context:
-        if self.ctx is None:
-            self.ctx = default_context()
-        return self.ctx
 
     components = property(lambda self: self._components, doc="(B, k, d), svd_flip's sign applied")
     mean = property(lambda self: self._means, doc="(B, d)")
@@ -1674,14 +1606,10 @@ class SegmentedPca:
         tv = np.zeros(nseg, dtype=npdt)
         status = np.zeros(nseg, dtype=np.int32)
         ks = C.c_int64(0)
-        y, my = None, None
-        if want_y:
-            y = _alloc_like(x, mx.rows, k, mx.dtype)
-            my = describe(y, keep)
+        y, my = _out_like(x, mx.rows, k, mx.dtype, keep) if want_y else (None, None)
         ctx.check(ctx.lib.petal_pca_fit_segments(
             ctx._h, C.byref(mx), off.ctypes.data_as(_L), nseg, k, int(self.centering), comp.ctypes.data, means.ctypes.data,
-            sing.ctypes.data, tv.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(my) if my is not None else None,
-            C.byref(ks)))
+            sing.ctypes.data, tv.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32)), _ref(my), C.byref(ks)))
         self._components, self._means, self._singular, self._total_variance = comp, means, sing, tv
         self._status, self._kernel_segments, self._dt = status, int(ks.value), mx.dtype
         return None if y is None else self._shaped(y, lead)
@@ -1703,8 +1631,7 @@ class SegmentedPca:
             raise InvalidInput(f"# of columns should be {cols_in}")
         if off.size - 1 != nseg:
             raise InvalidInput(f"the model holds {nseg} segments, offsets describe {off.size - 1}")
-        out = _alloc_like(a, ma.rows, cols_out, ma.dtype)
-        mo = describe(out, keep)
+        out, mo = _out_like(a, ma.rows, cols_out, ma.dtype, keep)
         comp = _host(self._components, ma.dtype)
         mu = _host(self._means, ma.dtype)
         ctx.check(entry(ctx._h, C.byref(ma), off.ctypes.data_as(_L), nseg, comp.ctypes.data, mu.ctypes.data, self._k, d,
@@ -1785,19 +1712,10 @@ class RandomizedPca(_PcaModel):
         size = self._k + self.n_oversample
         return self.rng.standard_normal((d, size)).astype(_np_dtype(dtype_code))  # f64 draw cast to A::Real
 
-    def _sparse(self, x):
-        """x as a CsrMatrix on this model's ctx, and whether it was made here (and is released when the call is over)."""
-        if isinstance(x, CsrMatrix):
-            if self.ctx is None:
-                self.ctx = x.ctx
-            return x, False
-        return CsrMatrix.from_scipy_like(x, ctx=self._ctx()), True
-
     def _inner_fit_sparse(self, x, want_y: bool, omega=None):
         """fit / fit_transform on sparse input (include/petal_hip_sparse.h): X is never densified; ``kernel_path`` says whether the
         sparse product kernel ran (1) or the library's densifying fall-back (0: a device-op layer without the kernel)."""
-        sx, mine = self._sparse(x)
-        try:
+        with self._sparse(x) as sx:
             ctx = self._ctx()
             rows, cols = sx.shape
             npdt = _np_dtype(sx._dt)
@@ -1813,21 +1731,17 @@ class RandomizedPca(_PcaModel):
             path = C.c_int64(0)
             ctx.check(ctx.lib.petal_rpca_fit_csr(ctx._h, sx._handle(), self._k, self.n_oversample, self.n_iter, int(self.centering),
                                                  omega.ctypes.data, comp.ctypes.data, means.ctypes.data, sing.ctypes.data, tv.ctypes.data,
-                                                 C.byref(my) if my is not None else None, C.byref(path)))
+                                                 _ref(my), C.byref(path)))
             self.kernel_path = int(path.value)
             if not (self.centering and rows == 0):
                 self._store(comp, means, sing, tv, rows)
             return y
-        finally:
-            if mine:
-                sx.close()
 
     def transform(self, x):
         """src/pca.rs:444-449; sparse input (a CsrMatrix or an object with .data / .indices / .indptr / .shape) goes through the sparse product."""
         if not _is_sparse(x):
             return super().transform(x)
-        sx, mine = self._sparse(x)
-        try:
+        with self._sparse(x) as sx:
             ctx = self._ctx()
             d = self._means.shape[0]
             if sx.shape[1] != d:
@@ -1841,9 +1755,6 @@ class RandomizedPca(_PcaModel):
                                                   C.byref(my), C.byref(path)))
             self.kernel_path = int(path.value)
             return y
-        finally:
-            if mine:
-                sx.close()
 
     def _inner_fit(self, x, want_y: bool, omega=None):
         if _is_sparse(x):
@@ -1859,13 +1770,10 @@ class RandomizedPca(_PcaModel):
         means = np.zeros(mx.cols, dtype=npdt)            # (an empty input without centering returns before the means are written)
         sing = np.empty(self._k, dtype=npdt)
         tv = np.zeros(1, dtype=npdt)
-        y, my = None, None
-        if want_y:
-            y = _alloc_like(x, mx.rows, self._k, mx.dtype)
-            my = describe(y, keep)
+        y, my = _out_like(x, mx.rows, self._k, mx.dtype, keep) if want_y else (None, None)
         ctx.check(ctx.lib.petal_rpca_fit(ctx._h, C.byref(mx), self._k, self.n_oversample, self.n_iter,
                                          int(self.centering), omega.ctypes.data, comp.ctypes.data, means.ctypes.data,
-                                         sing.ctypes.data, tv.ctypes.data, C.byref(my) if my is not None else None))
+                                         sing.ctypes.data, tv.ctypes.data, _ref(my)))
         if not (self.centering and mx.rows == 0 and ctx.world_size == 1):
             self._store(comp, means, sing, tv, mx.rows)
         return y
@@ -1918,7 +1826,7 @@ class RandomizedPcaBuilder:
         return RandomizedPca(self._k, self._centering, self._rng, self._ctx, self._n_oversample, self._n_iter)
 
 
-class FastIca:
+class FastIca(_CtxUser):
     """``FastIca<A, R>`` (src/ica.rs:41-221)."""
 
     TOL, MAX_ITER = 1e-4, 200  # src/ica.rs:216
@@ -1969,11 +1877,6 @@ class FastIca:
     def with_rng(cls, rng, ctx=None):
         return cls(rng, ctx)
 
-    def _ctx(self) -> Context:
-        if self.ctx is None:
-            self.ctx = default_context()
-        return self.ctx
-
     def _mode_word(self) -> int:
         """the ABI's `mode`: the semantics with the contrast of `fun` in bits 4-7"""
         mode, g = int(self.mode), _ica_contrast(self.fun)
@@ -1996,13 +1899,10 @@ class FastIca:
         comp = np.zeros((nc, mx.cols), dtype=npdt)
         means = np.zeros(mx.cols, dtype=npdt)
         n_iter = C.c_int64(0)
-        y, my = None, None
-        if want_y:
-            y = _alloc_like(x, mx.rows, nc, mx.dtype)
-            my = describe(y, keep)
+        y, my = _out_like(x, mx.rows, nc, mx.dtype, keep) if want_y else (None, None)
         ctx.check(ctx.lib.petal_fastica_fit(ctx._h, C.byref(mx), self.n_components, float(self.tol),
                                             int(self.max_iter), word, w_init.ctypes.data, comp.ctypes.data,
-                                            means.ctypes.data, C.byref(n_iter), C.byref(my) if my is not None else None))
+                                            means.ctypes.data, C.byref(n_iter), _ref(my)))
         self.components, self.means, self.n_iter = comp, means, int(n_iter.value)
         return y
 
@@ -2022,8 +1922,7 @@ class FastIca:
         if mx.cols != d:
             raise InvalidInput("too many columns")  # src/ica.rs:124-128
         nc = self.components.shape[0]
-        y = _alloc_like(x, mx.rows, nc, mx.dtype)
-        my = describe(y, keep)
+        y, my = _out_like(x, mx.rows, nc, mx.dtype, keep)
         comp = _host(self.components, mx.dtype)
         mu = _host(self.means, mx.dtype)
         ctx.check(ctx.lib.petal_transform(ctx._h, C.byref(mx), comp.ctypes.data, mu.ctypes.data, nc, d, 1, C.byref(my)))
@@ -2103,8 +2002,7 @@ def logcosh(x, ctx: Optional[Context] = None):
     ctx = ctx or default_context()
     keep = []
     mx = describe(x, keep)
-    g = _alloc_like(x, mx.rows, mx.cols, mx.dtype)
-    mg = describe(g, keep)
+    g, mg = _out_like(x, mx.rows, mx.cols, mx.dtype, keep)
     gp = np.zeros(mx.rows, dtype=_np_dtype(mx.dtype))
     ctx.check(ctx.lib.petal_logcosh(ctx._h, C.byref(mx), C.byref(mg), gp.ctypes.data))
     return g, gp
@@ -2150,12 +2048,10 @@ def score_rows(x, components, means, weights=None, centering=True, want_y=False,
     k, d = comp.shape
     mu = _host(means, mx.dtype, (d,)) if means is not None else np.zeros(d, dtype=_np_dtype(mx.dtype))
     wh = _host(weights, mx.dtype, (k,)) if weights is not None else None
-    out = _alloc_like(x, mx.rows, 2, mx.dtype)
-    mo = describe(out, keep)
-    y = _alloc_like(x, mx.rows, k, mx.dtype) if want_y else None
-    my = describe(y, keep) if want_y else None
+    out, mo = _out_like(x, mx.rows, 2, mx.dtype, keep)
+    y, my = _out_like(x, mx.rows, k, mx.dtype, keep) if want_y else (None, None)
     ctx.check(ctx.lib.petal_score_rows(ctx._h, C.byref(mx), comp.ctypes.data, mu.ctypes.data, k, d, int(bool(centering)),
-                                       wh.ctypes.data if wh is not None else None, C.byref(mo), C.byref(my) if want_y else None))
+                                       wh.ctypes.data if wh is not None else None, C.byref(mo), _ref(my)))
     return out, y
 
 
@@ -2171,11 +2067,10 @@ def power_pass(x, p, mu=None, want_z=False, ctx: Optional[Context] = None):
     N = ph.shape[1]
     muh = _host(mu, mx.dtype, (mx.cols,)) if mu is not None else None
     y = np.zeros((mx.cols, N), dtype=np.float64)
-    z = _alloc_like(x, mx.rows, N, mx.dtype) if want_z else None
-    mz = describe(z, keep) if want_z else None
+    z, mz = _out_like(x, mx.rows, N, mx.dtype, keep) if want_z else (None, None)
     fused = C.c_int(0)
     ctx.check(ctx.lib.petal_power_pass(ctx._h, C.byref(mx), muh.ctypes.data if muh is not None else None, ph.ctypes.data, N,
-                                       y.ctypes.data_as(C.POINTER(C.c_double)), C.byref(mz) if want_z else None, C.byref(fused)))
+                                       _dp(y), _ref(mz), C.byref(fused)))
     return y, z, bool(fused.value)
 
 
@@ -2208,10 +2103,6 @@ def _f64_2d(a):
     return a, (a.strides[0] // 8 if a.shape[0] > 1 else max(a.shape[1], 1))
 
 
-def _dp(a):
-    return a.ctypes.data_as(_D)
-
-
 def probe_chol(g, rel_tol, Lz=0, ndead_cols=0, route=0, b=None, ndead_in=0, ctx: Optional[Context] = None):
     """(out, ndead, rt) of petal_probe_chol: route 0 out = T (Lz x Lz); 1 out = b R^-1 (b: rows x Lz, None = identity); 2 out = R^-1 b"""
     ctx = ctx or default_context()
@@ -2226,7 +2117,7 @@ def probe_chol(g, rel_tol, Lz=0, ndead_cols=0, route=0, b=None, ndead_in=0, ctx:
     out = np.full(shape, np.nan)
     nd, rt = C.c_int(int(ndead_in)), C.c_int(-1)
     ctx.check(ctx.lib.petal_probe_chol(ctx._h, _dp(g), L, ldg, float(rel_tol), int(Lz), int(ndead_cols), int(route),
-                                       _dp(bb) if bb is not None else None, br, bc, ldb, _dp(out), shape[1], C.byref(nd), C.byref(rt)))
+                                       _dp(bb), br, bc, ldb, _dp(out), shape[1], C.byref(nd), C.byref(rt)))
     return out, nd.value, rt.value
 
 
@@ -2259,8 +2150,7 @@ def probe_ritz_residual(cv, vr, nc, theta, flag=None, flag2=None, w_len=None, ct
     f1 = C.c_int(int(flag)) if flag is not None else None
     f2 = C.c_int(int(flag2)) if flag2 is not None else None
     ctx.check(ctx.lib.petal_probe_ritz_residual(ctx._h, _dp(cv), cv.shape[1], _dp(vr), vr.shape[1], cv.shape[0], int(nc),
-                                                _dp(th) if nc > 0 else None, C.byref(f1) if f1 is not None else None,
-                                                C.byref(f2) if f2 is not None else None, _dp(out3), _dp(w_out), w_len))
+                                                _dp(th) if nc > 0 else None, _ref(f1), _ref(f2), _dp(out3), _dp(w_out), w_len))
     return out3, w_out
 
 
@@ -2308,7 +2198,7 @@ def probe_dgemm(ta, tb, M, N, K, alpha, a, b, beta, c, colscale=None, ctx: Optio
     ldc = c.strides[0] // 8 if M > 1 else N
     cs = np.ascontiguousarray(colscale, dtype=np.float64) if colscale is not None else None
     ctx.check(ctx.lib.petal_probe_dgemm(ctx._h, int(bool(ta)), int(bool(tb)), M, N, K, float(alpha), _dp(aa), lda, _dp(bb), ldb, float(beta),
-                                        _dp(c), ldc, _dp(cs) if cs is not None else None))
+                                        _dp(c), ldc, _dp(cs)))
     return c
 
 
@@ -2359,6 +2249,6 @@ def probe_rebase(x, mu, g, a, rel_tol=1e-15, p_planes=2, steering=False, route=0
     done, nd = C.c_int(-1), C.c_int(int(ndead_in))
     ctx.check(ctx.lib.petal_probe_rebase(ctx._h, x.ctypes.data, dt, n, K, ldx, muh.ctypes.data if muh is not None else None, _dp(gg), L, ldg,
                                          float(rel_tol), _dp(aa), M, lda, int(p_planes), int(bool(steering)), int(route), C.byref(done),
-                                         _dp(p_out), M, _dp(z) if z is not None else None, M, _dp(y) if y is not None else None, M,
+                                         _dp(p_out), M, _dp(z), M, _dp(y), M,
                                          C.byref(nd)))
     return {"done": done.value, "p_out": p_out, "z": z, "y": y, "ndead": nd.value}

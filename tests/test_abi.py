@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import header_kit as kit
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -19,11 +21,7 @@ def _declared():
 
 @pytest.fixture(scope="module")
 def lib_path():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("petal_build", os.path.join(ROOT, "petal-decomposition_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.build()
+    return kit.built_library()
 
 
 def test_header_symbols_exported(lib_path):

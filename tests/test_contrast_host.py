@@ -1,18 +1,17 @@
 """The FastICA contrast functions (exp, cube) without a GPU: tests/contrast_cases.py's references and models against their own bounds on
 the reduced table; what the host simulation -- which has the logcosh step only -- answers to the contrast field of `mode`; the
 constants of the header, the Python facade and the Rust bindings; the register budgets of the new step kernels."""
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import contrast_cases as cc
+import header_kit as kit
 import hostsim
 import kernel_entry_cases as kc
-from kernel_resources import kernel_resources
+from header_kit import resources  # noqa: F401  (the fixture)
 import petal_decomposition_amd as petal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -159,26 +158,10 @@ def test_json_form_is_untouched():
 
 
 def test_cpp_facade_on_host_simulation():
-    src = os.path.join(ROOT, "tests", "cpp", "contrast_facade_tests.cpp")
-    out = os.path.join(ROOT, "tests", "_build", "contrast_facade_tests_hostsim")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(hostsim.build())
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", out,
-                           "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "refuses"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "contrast facade tests passed" in res.stdout
+    kit.run_cpp_facade("contrast", "refuses", hostsim.build(), "hostsim")
 
 
 # ------------------------------------------------------------------------------------------- kernel budgets
-@pytest.fixture(scope="module")
-def resources():
-    spec = importlib.util.spec_from_file_location("petal_build", os.path.join(ROOT, "petal-decomposition_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return kernel_resources(mod.build())
-
-
 # the budgets of the logcosh kernels (tests/test_kernel_budgets.py): 32 components 4 waves / SIMD, 64 components the whole file
 BUDGETS = [
     (r"k_ica3g<2, [12]>$", 128, 2), (r"k_ica3pg<2, [12]>$", 128, 2),

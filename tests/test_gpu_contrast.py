@@ -5,6 +5,7 @@ Run with -m gpu."""
 import numpy as np
 import pytest
 
+import header_kit as kit
 import contrast_cases as cc
 
 pytestmark = pytest.mark.gpu
@@ -92,20 +93,7 @@ def test_step_statistics_are_unchanged(ctx):
 
 def test_cpp_facade_fits_on_gpu():
     """tests/cpp/contrast_facade_tests.cpp against libpetal_hip.so: exp and cube fits through the C++ facade's `contrast` member"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "petal-decomposition_amd", "libpetal_hip.so")
-    assert os.path.exists(lib), "libpetal_hip.so missing: run python __graft_entry__.py build"
-    src = os.path.join(root, "tests", "cpp", "contrast_facade_tests.cpp")
-    out = os.path.join(root, "tests", "_build", "contrast_facade_tests_hip")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(lib)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"), src, "-o", out,
-                           "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "fits"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "contrast facade tests passed (fits)" in res.stdout
+    kit.run_cpp_facade("contrast", "fits", kit.HIP_LIBRARY, "hip")
 
 
 def test_sharded_path_single_rank(ctx):

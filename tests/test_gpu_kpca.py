@@ -6,6 +6,7 @@ fallback, every error."""
 import numpy as np
 import pytest
 
+import header_kit as kit
 import kpca_cases as kc
 import petal_decomposition_amd as petal
 
@@ -120,16 +121,4 @@ def test_wide_a_and_many_rows(ctx):
 def test_cpp_facade_on_gpu():
     """tests/cpp/kpca_facade_tests.cpp against libpetal_hip.so: the C++ facade's KernelPca with k_kmap and k_kapply (the CPU suite runs
     the same program against the host simulation's fallback)"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "petal-decomposition_amd", "libpetal_hip.so")
-    assert os.path.exists(lib), "libpetal_hip.so missing: run python __graft_entry__.py build"
-    out = os.path.join(root, "tests", "_build", "kpca_facade_tests_hip")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(lib)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "kpca_facade_tests.cpp"),
-                           "-o", out, "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "kernel"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "kpca facade tests passed (kernel)" in res.stdout
+    kit.run_cpp_facade("kpca", "kernel", kit.HIP_LIBRARY, "hip")

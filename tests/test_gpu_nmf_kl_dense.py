@@ -4,11 +4,10 @@ the H side at 64 padded components and more than 256 padded columns among them),
 model-tied bound -- and Nmf(dense_path="fused") itself: fit, fit_transform and transform against the numpy model and against the CSR
 route, the stopping rule, the random initialisation, the same bytes twice, the forced composed path, shapes outside the kernel's
 envelope, device tensors, what did not move, every error."""
-import os
-import subprocess
 
 import pytest
 
+import header_kit as kit
 import nmf_kl_dense_cases as dc
 import petal_decomposition_amd as petal
 
@@ -113,15 +112,4 @@ def test_errors(ctx):
 def test_cpp_facade_on_gpu():
     """tests/cpp/nmf_kl_dense_facade_tests.cpp against libpetal_hip.so: the C++ facade's Nmf<A>::dense_path with k_nmf_kl_pass (the CPU
     suite runs the same program against the host simulation's composed path)"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "petal-decomposition_amd", "libpetal_hip.so")
-    assert os.path.exists(lib), "libpetal_hip.so missing: run python __graft_entry__.py build"
-    out = os.path.join(root, "tests", "_build", "nmf_kl_dense_facade_tests_hip")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(lib)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "nmf_kl_dense_facade_tests.cpp"), "-o", out, "-L", libdir, f"-l:{libname}",
-                           f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "kernel"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "nmf kl dense facade tests passed (kernel)" in res.stdout
+    kit.run_cpp_facade("nmf_kl_dense", "kernel", kit.HIP_LIBRARY, "hip")

@@ -3,12 +3,11 @@ through petal_nmf_sweep_csr -- exact operands bit for bit over the load, item an
 numpy.longdouble inside the model-tied bound -- and Nmf itself on a resident CsrMatrix: fit, fit_transform and transform against the
 numpy model on the densified matrix, the stopping rule, the random initialisation, the same bytes twice and on a second handle, the
 forced fall-back, k > 64, the densify limit, every error, the workspace count."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_kit as kit
 import nmf_sparse_cases as ns
 import petal_decomposition_amd as petal
 from sparse_cases import densify, to_csr
@@ -198,15 +197,4 @@ def test_errors_and_workspace(ctx):
 def test_cpp_facade_on_gpu():
     """tests/cpp/nmf_sparse_facade_tests.cpp against libpetal_hip.so: the C++ facade's Nmf on a CsrMatrix with k_nmf_sweep (the CPU suite
     runs the same program against the host simulation's densifying path)"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "petal-decomposition_amd", "libpetal_hip.so")
-    assert os.path.exists(lib), "libpetal_hip.so missing: run python __graft_entry__.py build"
-    out = os.path.join(root, "tests", "_build", "nmf_sparse_facade_tests_hip")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(lib)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "nmf_sparse_facade_tests.cpp"), "-o", out, "-L", libdir, f"-l:{libname}",
-                           f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "kernel"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "nmf sparse facade tests passed (kernel)" in res.stdout
+    kit.run_cpp_facade("nmf_sparse", "kernel", kit.HIP_LIBRARY, "hip")

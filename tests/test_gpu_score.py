@@ -5,6 +5,7 @@ Run with -m gpu."""
 import numpy as np
 import pytest
 
+import header_kit as kit
 import score_cases as sc
 
 pytestmark = pytest.mark.gpu
@@ -178,16 +179,4 @@ def test_model_scores(ctx, model):
 def test_cpp_facade_on_gpu():
     """tests/cpp/score_facade_tests.cpp against libpetal_hip.so: the five members of the C++ facade's Pca / RandomizedPca against their
     definitions (the CPU suite runs the same program against the host simulation, where the op refuses)"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "petal-decomposition_amd", "libpetal_hip.so")
-    assert os.path.exists(lib), "libpetal_hip.so missing: run python __graft_entry__.py build"
-    out = os.path.join(root, "tests", "_build", "score_facade_tests_hip")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(lib)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "score_facade_tests.cpp"),
-                           "-o", out, "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "scores"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "score facade tests passed (scores)" in res.stdout
+    kit.run_cpp_facade("score", "scores", kit.HIP_LIBRARY, "hip")

@@ -5,6 +5,7 @@ petal_transform_segments and the round trip at k = d; a planted NaN segment.  Ru
 import numpy as np
 import pytest
 
+import header_kit as kit
 import segments_cases as sg
 
 pytestmark = pytest.mark.gpu
@@ -194,16 +195,4 @@ def test_a_nan_segment_is_a_status_and_touches_nothing_else(ctx, dt):
 
 def test_cpp_facade_on_gpu():
     """the C++ SegmentedPca over the HIP library: the batch against Pca per segment, the round trip, a NaN segment, the messages"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "petal-decomposition_amd", "libpetal_hip.so")
-    assert os.path.exists(lib), "libpetal_hip.so missing: run python __graft_entry__.py build"
-    out = os.path.join(root, "tests", "_build", "segments_facade_tests_hip")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(lib)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "segments_facade_tests.cpp"),
-                           "-o", out, "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "kernel"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "segments facade tests passed (kernel)" in res.stdout
+    kit.run_cpp_facade("segments", "kernel", kit.HIP_LIBRARY, "hip")

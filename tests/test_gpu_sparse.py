@@ -5,6 +5,7 @@ dense fit, determinism to the byte, the argument and error contract, and a handl
 import numpy as np
 import pytest
 
+import header_kit as kit
 import sparse_cases as sc
 
 pytestmark = pytest.mark.gpu
@@ -93,19 +94,7 @@ def test_gemm_mode_and_plane_options_do_not_reach_a_sparse_fit():
 
 def test_cpp_facade_on_gpu():
     """the C++ CsrMatrix and the sparse overloads of RandomizedPca over the HIP library: resident, kernel_path == 1, close to the dense fit"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "petal-decomposition_amd", "libpetal_hip.so")
-    assert os.path.exists(lib), "libpetal_hip.so missing: run python __graft_entry__.py build"
-    out = os.path.join(root, "tests", "_build", "sparse_facade_tests_hip")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(lib)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "sparse_facade_tests.cpp"),
-                           "-o", out, "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "kernel"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "sparse facade tests passed (kernel)" in res.stdout
+    kit.run_cpp_facade("sparse", "kernel", kit.HIP_LIBRARY, "hip")
 
 
 # ------------------------------------------------------------------------------------------- determinism

@@ -4,15 +4,11 @@ Round 3 lost 4 -> 2 waves per SIMD on the dominant kernel (`k_atb3<5, true, 8, 2
 in the 1e6-row instantiation) to a branch inside the software-pipelined loop, and nothing noticed until the judge recompiled
 with `-Rpass-analysis=kernel-resource-usage`.  These budgets fail the CPU suite when an edit costs an occupancy step.
 """
-import importlib.util
-import os
 import re
 
 import pytest
 
-from kernel_resources import kernel_resources
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from header_kit import resources  # noqa: F401  (the fixture)
 
 # kernel (regex on the demangled name) -> (max VGPRs (unified: VGPR + AGPR), max scratch bytes, who uses it)
 BUDGETS = [
@@ -45,14 +41,6 @@ BUDGETS = [
 
 # kernels that were retired (round 6: reachable only through environment switches until then) and must not come back into the shipped library
 RETIRED = [r"k_chol_inv$", r"k_xp4<", r"k_gram3", r"k_gram4$", r"k_presplit_t", r"k_tridiag<", r"k_chol_rt<"]
-
-
-@pytest.fixture(scope="module")
-def resources():
-    spec = importlib.util.spec_from_file_location("petal_build", os.path.join(ROOT, "petal-decomposition_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return kernel_resources(mod.build())
 
 
 def test_notes_are_readable(resources):

@@ -5,18 +5,16 @@ cap), the whole host sequencing of fit / fit_transform / transform against the n
 built libraries, the Python table, the Rust binding and the C++ facade; the register / scratch budget of the kernels in the built
 library."""
 import ctypes as C
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_kit as kit
 import hostsim
 import kpca_cases as kc
-from kernel_resources import kernel_resources
-from test_rust_ffi_matches_header import _c_class, _rust_class, _strip_c_comments
+from header_kit import resources  # noqa: F401  (the fixture)
 import petal_decomposition_amd as petal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -171,32 +169,13 @@ def test_option_round_trip(ctx):
 
 # ------------------------------------------------------------------------------------------- the header, Python, Rust, C++
 def _header_functions():
-    text = re.sub(r"^\s*#.*$", "", _strip_c_comments(open(HEADER).read()), flags=re.M)
-    text = text.replace('extern "C" {', "")
-    text = re.sub(r"typedef struct petal_kernel_spec \{.*?\} petal_kernel_spec;", "", text, flags=re.S)
-    fns = {}
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(petal_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        params = [_c_class(re.match(r"(.*?)(\w+)$", a.strip(), flags=re.S).group(1)) for a in m.group(3).split(",")]
-        fns[m.group(2)] = (_c_class(m.group(1).strip().replace("typedef struct petal_kpca petal_kpca;", "").strip()), params)
-    return fns
+    return kit.header_functions(HEADER, drop=(r"typedef struct petal_kernel_spec \{.*?\} petal_kernel_spec;", r"typedef struct petal_kpca petal_kpca;"))
 
 
 def test_header_is_exported_and_bound_by_python():
     fns = _header_functions()
-    assert sorted(fns) == ENTRIES == sorted(n for n, _, _ in petal.ABI_KPCA)
-    assert not {n for n, _, _ in petal.ABI + petal.ABI_SCORE + petal.ABI_SEGMENTS + petal.ABI_SPARSE + petal.ABI_IPCA + petal.ABI_WIDE} & set(fns)
-    libs = [hostsim.build()]
-    hip = os.path.join(ROOT, "petal-decomposition_amd", "libpetal_hip.so")
-    if os.path.exists(hip):
-        libs.append(hip)
-    for path in libs:
-        lib = C.CDLL(path)
-        for name in fns:
-            assert hasattr(lib, name), (path, name)
-    cls = {C.c_void_p: "ptr", petal._M: "ptr", petal._L: "ptr", petal._D: "ptr", petal._KS: "ptr", C.POINTER(C.c_void_p): "ptr",
-           C.c_int: "i32", C.c_int64: "i64", C.c_double: "f64", None: "void"}
-    for name, res, args in petal.ABI_KPCA:
-        assert (cls[res], [cls[a] for a in args]) == fns[name], name
+    kit.check_python_table("petal_hip_kpca.h", fns, ENTRIES)
+    kit.check_exported(fns)
     assert fns["petal_kpca_fit"] == ("i32", ["ptr", "ptr", "i64", "ptr", "ptr", "ptr"])
     assert fns["petal_kernel_apply"] == ("i32", ["ptr", "ptr", "ptr", "ptr", "ptr", "i64", "ptr", "ptr", "ptr"])
     text = open(HEADER).read()
@@ -212,12 +191,7 @@ def test_header_is_exported_and_bound_by_python():
 
 def test_rust_binding_and_cpp_facade_match_the_header():
     text = re.sub(r"//.*$", "", open(FFI).read(), flags=re.M)
-    block = re.search(r'extern\s+"C"\s*\{(.*)\}', text, flags=re.S).group(1)
-    rust = {}
-    for m in re.finditer(r"pub\s+fn\s+(\w+)\s*\((.*?)\)\s*(->\s*([^;]+))?;", block, flags=re.S):
-        rust[m.group(1)] = ("void" if m.group(4) is None else _rust_class(m.group(4)),
-                            [_rust_class(a.split(":", 1)[1]) for a in m.group(2).split(",") if a.strip()])
-    assert rust == _header_functions()
+    assert kit.rust_functions(FFI) == _header_functions()
     assert int(re.search(r"PETAL_OPT_KPCA_FALLBACK:\s*c_int\s*=\s*(\d+)", text).group(1)) == petal.OPTIONS["kpca_fallback"]
     for name, code in petal.KERNELS.items():
         assert int(re.search(rf"PETAL_KERNEL_{name.upper()}:\s*i32\s*=\s*(\d+)", text).group(1)) == code
@@ -237,26 +211,10 @@ def test_rust_binding_and_cpp_facade_match_the_header():
 
 
 def test_cpp_facade_on_host_simulation():
-    src = os.path.join(ROOT, "tests", "cpp", "kpca_facade_tests.cpp")
-    out = os.path.join(ROOT, "tests", "_build", "kpca_facade_tests_hostsim")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(hostsim.build())
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", out,
-                           "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "fallback"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "kpca facade tests passed (fallback)" in res.stdout
+    kit.run_cpp_facade("kpca", "fallback", hostsim.build(), "hostsim")
 
 
 # ------------------------------------------------------------------------------------------- D: kernel budgets
-@pytest.fixture(scope="module")
-def resources():
-    spec = importlib.util.spec_from_file_location("petal_build", os.path.join(ROOT, "petal-decomposition_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return kernel_resources(mod.build())
-
-
 def test_kapply_kernel_budget(resources):
     """the figures DESIGN.md section 4 quotes, read from the built library's code-object notes: all twenty instantiations of the fused
     pass (float / double, five kernels, a 32- or a 64-column panel) without scratch, spills or LDS; the two output tiles of a panel live

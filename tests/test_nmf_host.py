@@ -5,18 +5,16 @@ sequencing of fit / fit_transform / transform / inverse_transform against the nu
 initialisation, every error; the model itself against scikit-learn; the new header against the built libraries, the Python table, the
 Rust binding and the C++ facade; the register / scratch budget of the kernels in the built library."""
 import ctypes as C
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_kit as kit
 import hostsim
 import nmf_cases as nc
-from kernel_resources import kernel_resources
-from test_rust_ffi_matches_header import _c_class, _rust_class, _strip_c_comments
+from header_kit import resources  # noqa: F401  (the fixture)
 import petal_decomposition_amd as petal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -209,33 +207,13 @@ def test_model_stops_where_sklearn_stops():
 
 # ------------------------------------------------------------------------------------------- 11: the header, Python, Rust, C++
 def _header_functions():
-    text = re.sub(r"^\s*#.*$", "", _strip_c_comments(open(HEADER).read()), flags=re.M)
-    text = text.replace('extern "C" {', "")
-    text = re.sub(r"typedef struct petal_nmf_spec \{.*?\} petal_nmf_spec;", "", text, flags=re.S)
-    fns = {}
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(petal_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        params = [_c_class(re.match(r"(.*?)(\w+)$", a.strip(), flags=re.S).group(1)) for a in m.group(3).split(",")]
-        fns[m.group(2)] = (_c_class(m.group(1).strip().replace("typedef struct petal_nmf petal_nmf;", "").strip()), params)
-    return fns
+    return kit.header_functions(HEADER, drop=(r"typedef struct petal_nmf_spec \{.*?\} petal_nmf_spec;", r"typedef struct petal_nmf petal_nmf;"))
 
 
 def test_header_is_exported_and_bound_by_python():
     fns = _header_functions()
-    assert sorted(fns) == ENTRIES == sorted(n for n, _, _ in petal.ABI_NMF)
-    assert not {n for n, _, _ in petal.ABI + petal.ABI_SCORE + petal.ABI_SEGMENTS + petal.ABI_SPARSE + petal.ABI_IPCA + petal.ABI_WIDE +
-                petal.ABI_KPCA} & set(fns)
-    libs = [hostsim.build()]
-    hip = os.path.join(ROOT, "petal-decomposition_amd", "libpetal_hip.so")
-    if os.path.exists(hip):
-        libs.append(hip)
-    for path in libs:
-        lib = C.CDLL(path)
-        for name in fns:
-            assert hasattr(lib, name), (path, name)
-    cls = {C.c_void_p: "ptr", petal._M: "ptr", petal._L: "ptr", petal._D: "ptr", petal._NS: "ptr", C.POINTER(C.c_void_p): "ptr",
-           C.c_int: "i32", C.c_int64: "i64", C.c_double: "f64", None: "void"}
-    for name, res, args in petal.ABI_NMF:
-        assert (cls[res], [cls[a] for a in args]) == fns[name], name
+    kit.check_python_table("petal_hip_nmf.h", fns, ENTRIES)
+    kit.check_exported(fns)
     assert fns["petal_nmf_fit"] == ("i32", ["ptr", "ptr", "i64", "ptr", "ptr", "ptr", "i64", "ptr", "ptr"])
     assert fns["petal_nmf_pass"] == ("i32", ["ptr", "ptr", "i64", "ptr", "ptr", "ptr", "i64", "ptr", "ptr", "ptr", "ptr"])
     text = open(HEADER).read()
@@ -249,12 +227,7 @@ def test_header_is_exported_and_bound_by_python():
 
 def test_rust_binding_and_cpp_facade_match_the_header():
     text = re.sub(r"//.*$", "", open(FFI).read(), flags=re.M)
-    block = re.search(r'extern\s+"C"\s*\{(.*)\}', text, flags=re.S).group(1)
-    rust = {}
-    for m in re.finditer(r"pub\s+fn\s+(\w+)\s*\((.*?)\)\s*(->\s*([^;]+))?;", block, flags=re.S):
-        rust[m.group(1)] = ("void" if m.group(4) is None else _rust_class(m.group(4)),
-                            [_rust_class(a.split(":", 1)[1]) for a in m.group(2).split(",") if a.strip()])
-    assert rust == _header_functions()
+    assert kit.rust_functions(FFI) == _header_functions()
     assert int(re.search(r"PETAL_OPT_NMF_FALLBACK:\s*c_int\s*=\s*(\d+)", text).group(1)) == petal.OPTIONS["nmf_fallback"]
     fields = re.search(r"pub struct PetalNmfSpec \{(.*?)\}", text, flags=re.S).group(1)
     assert re.findall(r"pub (\w+): (\w+)", fields) == [("max_iter", "i64"), ("tol", "f64"), ("l1_w", "f64"), ("l2_w", "f64"), ("l1_h", "f64"),
@@ -273,26 +246,10 @@ def test_rust_binding_and_cpp_facade_match_the_header():
 
 
 def test_cpp_facade_on_host_simulation():
-    src = os.path.join(ROOT, "tests", "cpp", "nmf_facade_tests.cpp")
-    out = os.path.join(ROOT, "tests", "_build", "nmf_facade_tests_hostsim")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(hostsim.build())
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", out,
-                           "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "fallback"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "nmf facade tests passed (fallback)" in res.stdout
+    kit.run_cpp_facade("nmf", "fallback", hostsim.build(), "hostsim")
 
 
 # ------------------------------------------------------------------------------------------- kernel budgets
-@pytest.fixture(scope="module")
-def resources():
-    spec = importlib.util.spec_from_file_location("petal_build", os.path.join(ROOT, "petal-decomposition_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return kernel_resources(mod.build())
-
-
 def test_pass_kernel_budget(resources):
     """all 48 instantiations of the fused pass (float / double; 16, 32 or 64 padded components; 1, 2, 4 or 8 feature tiles per wave;
     with and without the accumulators of A and B) without scratch and without spilled registers; four waves per workgroup"""

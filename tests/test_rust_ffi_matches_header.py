@@ -6,47 +6,18 @@ machine type (pointer vs integer vs double, and the integer width: c_int <-> int
 import os
 import re
 
+from header_kit import _c_class, _rust_class, _strip_c_comments, header_functions, rust_functions
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "petal_hip.h")
 FFI = os.path.join(ROOT, "rust", "petal-decomposition-hip", "src", "ffi.rs")
 
 
-def _strip_c_comments(text):
-    return re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-
-
-def _c_class(t):
-    """machine class of a C parameter type"""
-    t = t.strip()
-    if "*" in t or re.search(r"\bpetal_allreduce_fn\b", t):
-        return "ptr"
-    t = re.sub(r"\bconst\b", "", t).strip()
-    return {"int": "i32", "int32_t": "i32", "int64_t": "i64", "double": "f64", "void": "void", "size_t": "u64"}[t]
-
-
-def _rust_class(t):
-    t = t.strip()
-    if t.startswith("*"):
-        return "ptr"
-    return {"c_int": "i32", "i32": "i32", "i64": "i64", "f64": "f64", "c_double": "f64", "usize": "u64"}[t]
-
-
 def parse_header():
     text = _strip_c_comments(open(HEADER).read())
     text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    fns = {}
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(petal_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
-        if "typedef" in ret or "(" in ret:
-            continue
-        params = []
-        if args and args != "void":
-            for a in args.split(","):
-                a = a.strip()
-                mm = re.match(r"(.*?)(\w+)$", a, flags=re.S)   # type, then the parameter name
-                params.append(_c_class(mm.group(1)))
-        fns[name] = (_c_class(ret), params)
-    st = re.search(r"typedef\s+struct\s+petal_matrix\s*\{(.*?)\}\s*petal_matrix\s*;", text, flags=re.S).group(1)
+    fns = header_functions(HEADER)
+    st =re.search(r"typedef\s+struct\s+petal_matrix\s*\{(.*?)\}\s*petal_matrix\s*;", text, flags=re.S).group(1)
     fields = []
     for decl in st.split(";"):
         decl = decl.strip()
@@ -63,13 +34,8 @@ def parse_header():
 
 def parse_ffi():
     text = re.sub(r"//.*$", "", open(FFI).read(), flags=re.M)
-    block = re.search(r'extern\s+"C"\s*\{(.*)\}', text, flags=re.S).group(1)
-    fns = {}
-    for m in re.finditer(r"pub\s+fn\s+(\w+)\s*\((.*?)\)\s*(->\s*([^;]+))?;", block, flags=re.S):
-        name, args, ret = m.group(1), m.group(2), m.group(4)
-        params = [_rust_class(a.split(":", 1)[1]) for a in args.split(",") if a.strip()]
-        fns[name] = ("void" if ret is None else _rust_class(ret), params)
-    st = re.search(r"pub\s+struct\s+PetalMatrix\s*\{(.*?)\}", text, flags=re.S).group(1)
+    fns = rust_functions(FFI)
+    st =re.search(r"pub\s+struct\s+PetalMatrix\s*\{(.*?)\}", text, flags=re.S).group(1)
     fields = [(m.group(1), _rust_class(m.group(2))) for m in re.finditer(r"pub\s+(\w+)\s*:\s*([^,\n]+),", st)]
     consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"pub\s+const\s+(PETAL_\w+)\s*:\s*c_int\s*=\s*(\d+)", text)}
     return fns, fields, consts

@@ -3,19 +3,17 @@ reduced table; what the host simulation -- whose device-op layer has no score op
 against the built library, the Python table and the Rust binding; the facade's formulas against a float64 restatement of the
 probabilistic-PCA log-density; the JSON form; the register budgets of the new kernels; the C++ facade."""
 import ctypes as C
-import importlib.util
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_kit as kit
 import hostsim
 import score_cases as sc
-from kernel_resources import kernel_resources
-from test_rust_ffi_matches_header import _c_class, _rust_class, _strip_c_comments
+from header_kit import resources  # noqa: F401  (the fixture)
 import petal_decomposition_amd as petal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,37 +120,15 @@ def test_no_rows_is_legal(ctx):
 
 
 # ------------------------------------------------------------------------------------------- the header, Python, Rust
-def _header_functions():
-    text = re.sub(r"^\s*#.*$", "", _strip_c_comments(open(HEADER).read()), flags=re.M)
-    fns = {}
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(petal_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        params = [_c_class(re.match(r"(.*?)(\w+)$", a.strip(), flags=re.S).group(1)) for a in m.group(3).split(",")]
-        fns[m.group(2)] = (_c_class(m.group(1).replace('extern "C" {', "").strip()), params)
-    return fns
-
-
 def test_header_is_exported_and_bound_by_python():
-    fns = _header_functions()
-    assert sorted(fns) == ["petal_score_rows"] == sorted(n for n, _, _ in petal.ABI_SCORE)
-    assert not {n for n, _, _ in petal.ABI} & set(fns)          # the mirrored set stays what it was
-    for path in (hostsim.build(), os.path.join(ROOT, "petal-decomposition_amd", "libpetal_hip.so")):
-        lib = C.CDLL(path)
-        for name in fns:
-            assert hasattr(lib, name), (path, name)
-    cls = {C.c_void_p: "ptr", petal._M: "ptr", C.c_int: "i32", C.c_int64: "i64", C.c_double: "f64"}
-    for name, res, args in petal.ABI_SCORE:
-        assert (cls[res], [cls[a] for a in args]) == fns[name], name
+    fns = kit.header_functions(HEADER)
+    kit.check_python_table("petal_hip_score.h", fns, ["petal_score_rows"])
+    kit.check_exported(fns, want_hip=True)
     assert '#include "petal_hip.h"' in open(HEADER).read()
 
 
 def test_rust_binding_matches_the_header():
-    text = re.sub(r"//.*$", "", open(FFI).read(), flags=re.M)
-    block = re.search(r'extern\s+"C"\s*\{(.*)\}', text, flags=re.S).group(1)
-    rust = {}
-    for m in re.finditer(r"pub\s+fn\s+(\w+)\s*\((.*?)\)\s*(->\s*([^;]+))?;", block, flags=re.S):
-        rust[m.group(1)] = ("void" if m.group(4) is None else _rust_class(m.group(4)),
-                            [_rust_class(a.split(":", 1)[1]) for a in m.group(2).split(",") if a.strip()])
-    assert rust == _header_functions()
+    assert kit.rust_functions(FFI) == kit.header_functions(HEADER)
     src = os.path.join(ROOT, "rust", "petal-decomposition-hip", "src")
     assert "mod ffi_score;" in open(os.path.join(src, "lib.rs")).read()
     pca = open(os.path.join(src, "pca.rs")).read()
@@ -224,26 +200,10 @@ def test_json_form_is_unchanged(ctx):
 
 
 def test_cpp_facade_on_host_simulation():
-    src = os.path.join(ROOT, "tests", "cpp", "score_facade_tests.cpp")
-    out = os.path.join(ROOT, "tests", "_build", "score_facade_tests_hostsim")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(hostsim.build())
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", out,
-                           "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "refuses"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "score facade tests passed" in res.stdout
+    kit.run_cpp_facade("score", "refuses", hostsim.build(), "hostsim")
 
 
 # ------------------------------------------------------------------------------------------- kernel budgets
-@pytest.fixture(scope="module")
-def resources():
-    spec = importlib.util.spec_from_file_location("petal_build", os.path.join(ROOT, "petal-decomposition_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return kernel_resources(mod.build())
-
-
 # the new kernel -> the kernel it derives from, in the instantiation petal_transform launches (no sum of squares): no occupancy step lost
 # against it, no scratch, no spills.  The fp32-MFMA form has no uncentred 3-tile instantiation: it would take 194 registers, two waves per
 # SIMD against three of k_xp_mfma<4, 3, false, false>, so the launcher never forms such a panel (test_no_uncentred_three_tile_form).

@@ -5,18 +5,16 @@ petal_csr_gemm is a plain host loop -- against the oracle, against petal_rpca_fi
 argument contract; the new header against the built libraries, the Python table and the Rust binding; the C++ facade; the resource
 notes of the new kernels."""
 import ctypes as C
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_kit as kit
 import hostsim
 import sparse_cases as sc
-from kernel_resources import kernel_resources
-from test_rust_ffi_matches_header import _c_class, _rust_class, _strip_c_comments
+from header_kit import resources  # noqa: F401  (the fixture)
 import petal_decomposition_amd as petal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -235,26 +233,13 @@ def test_scipy_is_imported_nowhere():
 
 # ------------------------------------------------------------------------------------------- the header, Python, Rust, C++
 def _header_functions():
-    text = re.sub(r"^\s*#.*$", "", _strip_c_comments(open(HEADER).read()), flags=re.M)
-    fns = {}
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(petal_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        params = [_c_class(re.match(r"(.*?)(\w+)$", a.strip(), flags=re.S).group(1)) for a in m.group(3).split(",")]
-        fns[m.group(2)] = (_c_class(m.group(1).replace('extern "C" {', "").replace("typedef struct petal_csr petal_csr;", "").strip()), params)
-    return fns
+    return kit.header_functions(HEADER, drop=(r"typedef struct petal_csr petal_csr;",))
 
 
 def test_header_is_exported_and_bound_by_python():
     fns = _header_functions()
-    assert sorted(fns) == ENTRIES == sorted(n for n, _, _ in petal.ABI_SPARSE)
-    assert not {n for n, _, _ in petal.ABI + petal.ABI_SCORE + petal.ABI_SEGMENTS} & set(fns)          # the mirrored set stays what it was
-    for path in (hostsim.build(), os.path.join(ROOT, "petal-decomposition_amd", "libpetal_hip.so")):
-        lib = C.CDLL(path)
-        for name in fns:
-            assert hasattr(lib, name), (path, name)
-    cls = {C.c_void_p: "ptr", petal._M: "ptr", petal._L: "ptr", petal._I32: "ptr", petal._D: "ptr", C.POINTER(C.c_void_p): "ptr",
-           C.c_int: "i32", C.c_int32: "i32", C.c_int64: "i64", None: "void"}
-    for name, res, args in petal.ABI_SPARSE:
-        assert (cls[res], [cls[a] for a in args]) == fns[name], name
+    kit.check_python_table("petal_hip_sparse.h", fns, ENTRIES)
+    kit.check_exported(fns, want_hip=True)
     assert fns["petal_rpca_fit_csr"] == ("i32", ["ptr", "ptr", "i64", "i64", "i64", "i32"] + ["ptr"] * 7)
     assert fns["petal_csr_create"] == ("i32", ["ptr", "i64", "i64", "i64", "ptr", "ptr", "ptr", "i32", "ptr"])
     text = open(HEADER).read()
@@ -264,12 +249,7 @@ def test_header_is_exported_and_bound_by_python():
 
 def test_rust_binding_matches_the_header():
     text = re.sub(r"//.*$", "", open(FFI).read(), flags=re.M)
-    block = re.search(r'extern\s+"C"\s*\{(.*)\}', text, flags=re.S).group(1)
-    rust = {}
-    for m in re.finditer(r"pub\s+fn\s+(\w+)\s*\((.*?)\)\s*(->\s*([^;]+))?;", block, flags=re.S):
-        rust[m.group(1)] = ("void" if m.group(4) is None else _rust_class(m.group(4)),
-                            [_rust_class(a.split(":", 1)[1]) for a in m.group(2).split(",") if a.strip()])
-    assert rust == _header_functions()
+    assert kit.rust_functions(FFI) == _header_functions()
     assert int(re.search(r"PETAL_CSR_ITEM_NNZ:\s*i64\s*=\s*(\d+)", text).group(1)) == petal.CSR_ITEM_NNZ
     src = os.path.join(ROOT, "rust", "petal-decomposition-hip", "src")
     lib = open(os.path.join(src, "lib.rs")).read()
@@ -283,26 +263,10 @@ def test_rust_binding_matches_the_header():
 
 
 def test_cpp_facade_on_host_simulation():
-    src = os.path.join(ROOT, "tests", "cpp", "sparse_facade_tests.cpp")
-    out = os.path.join(ROOT, "tests", "_build", "sparse_facade_tests_hostsim")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(hostsim.build())
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", out,
-                           "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "fallback"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "sparse facade tests passed (fallback)" in res.stdout
+    kit.run_cpp_facade("sparse", "fallback", hostsim.build(), "hostsim")
 
 
 # ------------------------------------------------------------------------------------------- kernel budgets
-@pytest.fixture(scope="module")
-def resources():
-    spec = importlib.util.spec_from_file_location("petal_build", os.path.join(ROOT, "petal-decomposition_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return kernel_resources(mod.build())
-
-
 SPMM_KERNELS = [("float", g) for g in (4, 8, 16, 32)] + [("double", g) for g in (8, 16, 32)]
 
 

@@ -4,18 +4,16 @@ statements of the row Gram matrix (exact integers, the long-double bound and its
 against the oracle and against its numpy model, the auto rule, k = n, non-finite input, the options; the new header against the built
 libraries, the Python table, the Rust binding and the C++ facade."""
 import ctypes as C
-import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import header_kit as kit
 import hostsim
 import wide_cases as wc
-from kernel_resources import kernel_resources
-from test_rust_ffi_matches_header import _c_class, _rust_class, _strip_c_comments
+from header_kit import resources  # noqa: F401  (the fixture)
 import petal_decomposition_amd as petal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -177,31 +175,10 @@ def test_options_round_trip(ctx):
 
 
 # ------------------------------------------------------------------------------------------- the header, Python, Rust, C++
-def _header_functions():
-    text = re.sub(r"^\s*#.*$", "", _strip_c_comments(open(HEADER).read()), flags=re.M)
-    text = text.replace('extern "C" {', "")
-    fns = {}
-    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(petal_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        params = [_c_class(re.match(r"(.*?)(\w+)$", a.strip(), flags=re.S).group(1)) for a in m.group(3).split(",")]
-        fns[m.group(2)] = (_c_class(m.group(1).strip()), params)
-    return fns
-
-
 def test_header_is_exported_and_bound_by_python():
-    fns = _header_functions()
-    assert sorted(fns) == ENTRIES == sorted(n for n, _, _ in petal.ABI_WIDE)
-    assert not {n for n, _, _ in petal.ABI + petal.ABI_SCORE + petal.ABI_SEGMENTS + petal.ABI_SPARSE + petal.ABI_IPCA} & set(fns)
-    libs = [hostsim.build()]
-    hip = os.path.join(ROOT, "petal-decomposition_amd", "libpetal_hip.so")
-    if os.path.exists(hip):
-        libs.append(hip)
-    for path in libs:
-        lib = C.CDLL(path)
-        for name in fns:
-            assert hasattr(lib, name), (path, name)
-    cls = {C.c_void_p: "ptr", petal._M: "ptr", petal._L: "ptr", petal._D: "ptr", C.c_int: "i32", C.c_int64: "i64", C.c_double: "f64", None: "void"}
-    for name, res, args in petal.ABI_WIDE:
-        assert (cls[res], [cls[a] for a in args]) == fns[name], name
+    fns = kit.header_functions(HEADER)
+    kit.check_python_table("petal_hip_wide.h", fns, ENTRIES)
+    kit.check_exported(fns)
     assert fns["petal_pca_last_route"] == ("i32", ["ptr", "ptr"])
     assert fns["petal_row_gram"] == ("i32", ["ptr", "ptr", "ptr", "ptr", "ptr"])
     text = open(HEADER).read()
@@ -216,12 +193,7 @@ def test_header_is_exported_and_bound_by_python():
 
 def test_rust_binding_and_cpp_facade_match_the_header():
     text = re.sub(r"//.*$", "", open(FFI).read(), flags=re.M)
-    block = re.search(r'extern\s+"C"\s*\{(.*)\}', text, flags=re.S).group(1)
-    rust = {}
-    for m in re.finditer(r"pub\s+fn\s+(\w+)\s*\((.*?)\)\s*(->\s*([^;]+))?;", block, flags=re.S):
-        rust[m.group(1)] = ("void" if m.group(4) is None else _rust_class(m.group(4)),
-                            [_rust_class(a.split(":", 1)[1]) for a in m.group(2).split(",") if a.strip()])
-    assert rust == _header_functions()
+    assert kit.rust_functions(FFI) == kit.header_functions(HEADER)
     assert int(re.search(r"PETAL_OPT_PCA_DUAL:\s*c_int\s*=\s*(\d+)", text).group(1)) == petal.OPTIONS["pca_dual"]
     assert int(re.search(r"PETAL_OPT_PCA_DUAL_FALLBACK:\s*c_int\s*=\s*(\d+)", text).group(1)) == petal.OPTIONS["pca_dual_fallback"]
     src = os.path.join(ROOT, "rust", "petal-decomposition-hip", "src")
@@ -235,26 +207,10 @@ def test_rust_binding_and_cpp_facade_match_the_header():
 
 
 def test_cpp_facade_on_host_simulation():
-    src = os.path.join(ROOT, "tests", "cpp", "wide_facade_tests.cpp")
-    out = os.path.join(ROOT, "tests", "_build", "wide_facade_tests_hostsim")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    libdir, libname = os.path.split(hostsim.build())
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", out,
-                           "-L", libdir, f"-l:{libname}", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    res = subprocess.run([out, "fallback"], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert "wide facade tests passed (fallback)" in res.stdout
+    kit.run_cpp_facade("wide", "fallback", hostsim.build(), "hostsim")
 
 
 # ------------------------------------------------------------------------------------------- kernel budgets
-@pytest.fixture(scope="module")
-def resources():
-    spec = importlib.util.spec_from_file_location("petal_build", os.path.join(ROOT, "petal-decomposition_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return kernel_resources(mod.build())
-
-
 def test_row_gram_kernel_budget(resources):
     """the figures DESIGN.md section 4 quotes, read from the built library's code-object notes: no scratch, no spills, no LDS, four waves
     per SIMD in all four instantiations (float / double, centred or not); the slab sum likewise at eight"""
