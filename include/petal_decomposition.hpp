@@ -32,6 +32,7 @@
 #include "petal_hip_nmf_kl.h"
 #include "petal_hip_nmf_kl_dense.h"
 #include "petal_hip_nmf_cd.h"
+#include "petal_hip_nmf_cd_sparse.h"
 
 namespace petal_decomposition {
 
@@ -583,6 +584,11 @@ enum class NmfDensePath : int { Compress = 0, Fused = 1 };
 // above, byte for byte; CoordinateDescent is scikit-learn's NMF(solver="cd") (its default, shuffle=False) under the Frobenius loss:
 // the stopping rule runs after every iteration, transform starts from W = 0.  With the Kullback-Leibler loss or a CsrMatrix it throws.
 enum class NmfSolver : int64_t { MultiplicativeUpdate = PETAL_NMF_SOLVER_MU, CoordinateDescent = PETAL_NMF_SOLVER_CD };
+// extension beyond the crate (petal_hip_nmf_cd_sparse.h): what the CsrMatrix overloads do under CoordinateDescent.  Refuse (the default)
+// keeps them throwing "does not take a CsrMatrix"; Sweep sends the matrix to the coordinate-descent sweeps k_nmf_cd_sweep
+// (petal_nmf_fit_csr_solver, petal_nmf_transform_csr_solver; at most 64 components on the kernel, otherwise the library densifies).
+// Under MultiplicativeUpdate it changes nothing.
+enum class NmfSparsePath : int { Refuse = 0, Sweep = 1 };
 
 template <class A>
 class Nmf {
@@ -595,7 +601,8 @@ class Nmf {
     Nmf& operator=(const Nmf&) = delete;
     Nmf(Nmf&& o) noexcept
         : k_(o.k_), max_iter_(o.max_iter_), tol_(o.tol_), seed_(o.seed_), alpha_w_(o.alpha_w_), alpha_h_(o.alpha_h_), l1_ratio_(o.l1_ratio_),
-          ctx_(o.ctx_), h_(o.h_), kernel_path_(o.kernel_path_), loss_(o.loss_), dense_path_(o.dense_path_), solver_(o.solver_) { o.h_ = nullptr; }
+          ctx_(o.ctx_), h_(o.h_), kernel_path_(o.kernel_path_), loss_(o.loss_), dense_path_(o.dense_path_), solver_(o.solver_),
+          sparse_path_(o.sparse_path_) { o.h_ = nullptr; }
     ~Nmf() { petal_nmf_destroy(h_); }
     Nmf& loss(NmfLoss l) { loss_ = l; return *this; }   // the loss of the NEXT fit on a CsrMatrix (petal_hip_nmf_kl.h)
     NmfLoss loss() const { return loss_; }
@@ -603,6 +610,8 @@ class Nmf {
     NmfDensePath dense_path() const { return dense_path_; }
     Nmf& solver(NmfSolver s) { solver_ = s; return *this; }   // the solver of the NEXT dense fit (petal_hip_nmf_cd.h)
     NmfSolver solver() const { return solver_; }
+    Nmf& sparse_path(NmfSparsePath p) { sparse_path_ = p; return *this; }   // the route of the NEXT CsrMatrix call under CoordinateDescent
+    NmfSparsePath sparse_path() const { return sparse_path_; }
     // the solver the fitted model remembers
     NmfSolver model_solver() const {
         int64_t v = 0;
@@ -662,7 +671,10 @@ class Nmf {
     Array2<A> transform(const CsrMatrix<A>& input) {
         Array2<A> w(input.nrows(), k_);
         petal_matrix mw = w.view();
-        context().check(petal_nmf_transform_csr(context().get(), handle(), input.get(), &mw, &kernel_path_));
+        if (sparse_path_ == NmfSparsePath::Sweep)   // dispatches on the model's solver; a multiplicative model: petal_nmf_transform_csr's bytes
+            context().check(petal_nmf_transform_csr_solver(context().get(), handle(), input.get(), &mw, &kernel_path_));
+        else
+            context().check(petal_nmf_transform_csr(context().get(), handle(), input.get(), &mw, &kernel_path_));
         return w;
     }
     // the last sparse call: 1 the sweep kernel, 0 the densifying fall-back; the last fused dense Kullback-Leibler call: 1 k_nmf_kl_pass, 0 the composed path
@@ -704,8 +716,11 @@ class Nmf {
                                      "Nmf: the kullback-leibler loss takes a CsrMatrix (compress the dense rows to the CSR of their non-zero entries)");
     }
     void no_sparse_cd() const {
-        if (solver_ == NmfSolver::CoordinateDescent)
+        if (solver_ != NmfSolver::CoordinateDescent) return;
+        if (sparse_path_ != NmfSparsePath::Sweep)
             throw DecompositionError(DecompositionError::InvalidInput, "Nmf: the coordinate-descent solver does not take a CsrMatrix in this version");
+        if (loss_ != NmfLoss::Frobenius)
+            throw DecompositionError(DecompositionError::InvalidInput, "Nmf: the coordinate-descent solver does not take the kullback-leibler loss");
     }
     void inner_fit(const Array2<A>& input, const Array2<A>* w0, const Array2<A>* h0, Array2<A>* w) {
         const bool cd = solver_ == NmfSolver::CoordinateDescent;
@@ -746,7 +761,10 @@ class Nmf {
         spec.l1_w = d * alpha_w_ * l1_ratio_; spec.l2_w = d * alpha_w_ * (1.0 - l1_ratio_);
         spec.l1_h = n * alpha_h_ * l1_ratio_; spec.l2_h = n * alpha_h_ * (1.0 - l1_ratio_);
         petal_nmf* h = nullptr;
-        if (loss_ == NmfLoss::Frobenius)
+        if (solver_ == NmfSolver::CoordinateDescent)   // sparse_path(Sweep): petal_hip_nmf_cd_sparse.h
+            context().check(petal_nmf_fit_csr_solver(context().get(), input.get(), k_, &spec, static_cast<int64_t>(solver_), w0 ? &m0 : nullptr,
+                                                     w0 ? &m1 : nullptr, int64_t(seed_), &h, w ? &mw : nullptr, &kernel_path_));
+        else if (loss_ == NmfLoss::Frobenius)
             context().check(petal_nmf_fit_csr(context().get(), input.get(), k_, &spec, w0 ? &m0 : nullptr, w0 ? &m1 : nullptr, int64_t(seed_), &h,
                                               w ? &mw : nullptr, &kernel_path_));
         else
@@ -765,6 +783,7 @@ class Nmf {
     NmfLoss loss_ = NmfLoss::Frobenius;
     NmfDensePath dense_path_ = NmfDensePath::Compress;
     NmfSolver solver_ = NmfSolver::MultiplicativeUpdate;
+    NmfSparsePath sparse_path_ = NmfSparsePath::Refuse;
 };
 
 class PcaBuilder {  // src/pca.rs:246-283

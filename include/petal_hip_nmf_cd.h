@@ -42,7 +42,8 @@
  *
  * Not in this version: coordinate descent with the Kullback-Leibler loss (scikit-learn refuses it too), coordinate descent on CSR input
  * (a k_nmf_sweep variant is the natural follow-up), sharded fits, shuffle=True, a tolerance stop in transform, a kernel for 48 padded
- * components or more than 512 padded columns.
+ * components or more than 512 padded columns.  (Coordinate descent on CSR input has since been added beside this header:
+ * petal_hip_nmf_cd_sparse.h.)
  */
 #ifndef PETAL_HIP_NMF_CD_H
 #define PETAL_HIP_NMF_CD_H

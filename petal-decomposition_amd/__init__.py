@@ -258,12 +258,18 @@ ABI_NMF_CD = [
     ("petal_nmf_cd_pass", C.c_int, [_P, _M, C.c_int64, _D, _D, _NS, C.c_int64, C.c_int, _D, _D, _D, _D, _L]),
     ("petal_nmf_cd_hupdate", C.c_int, [_P, C.c_int64, C.c_int64, _D, _D, _D, _NS, _D, _D, _L]),
 ]
+# every symbol include/petal_hip_nmf_cd_sparse.h declares (the coordinate-descent solver on sparse CSR data and its sweep by itself)
+ABI_NMF_CD_SPARSE = [
+    ("petal_nmf_fit_csr_solver", C.c_int, [_P, _P, C.c_int64, _NS, C.c_int64, _M, _M, C.c_int64, C.POINTER(C.c_void_p), _M, _L]),
+    ("petal_nmf_transform_csr_solver", C.c_int, [_P, _P, _P, _M, _L]),
+    ("petal_nmf_cd_sweep_csr", C.c_int, [_P, _P, C.c_int, C.c_int64, _D, _D, _NS, C.c_int64, C.c_int, _D, _D, _D, _D, _L]),
+]
 
 # header file name (include/) -> its table, in the order the headers were added: what load_library types and the tests check
 ABI_TABLES = {"petal_hip.h": ABI, "petal_hip_score.h": ABI_SCORE, "petal_hip_segments.h": ABI_SEGMENTS, "petal_hip_probe.h": ABI_PROBE,
               "petal_hip_sparse.h": ABI_SPARSE, "petal_hip_ipca.h": ABI_IPCA, "petal_hip_wide.h": ABI_WIDE, "petal_hip_kpca.h": ABI_KPCA,
               "petal_hip_nmf.h": ABI_NMF, "petal_hip_nmf_sparse.h": ABI_NMF_SPARSE, "petal_hip_nmf_kl.h": ABI_NMF_KL,
-              "petal_hip_nmf_kl_dense.h": ABI_NMF_KL_DENSE, "petal_hip_nmf_cd.h": ABI_NMF_CD}
+              "petal_hip_nmf_kl_dense.h": ABI_NMF_KL_DENSE, "petal_hip_nmf_cd.h": ABI_NMF_CD, "petal_hip_nmf_cd_sparse.h": ABI_NMF_CD_SPARSE}
 
 
 def _preload_torch_hip_runtime():
@@ -963,6 +969,27 @@ def nmf_cd_pass(x, w, h, l1_w=0.0, l2_w=0.0, inner_iters=1, from_zero: bool = Fa
     return _with_info((wo, a, b, viol) if want_ab else (wo, viol), info, want_info)
 
 
+def nmf_cd_sweep(sx: "CsrMatrix", g, f, transposed: bool = False, l1=0.0, l2=0.0, inner_iters=1, from_zero: bool = False, want_gram=True,
+                 want_info: bool = False):
+    """Test aid (``petal_nmf_cd_sweep_csr``, include/petal_hip_nmf_cd_sparse.h): one coordinate-descent sweep of sparse ``Nmf`` by
+    itself, in float64, over the matrix (``transposed=False``: R x C = ``sx.shape``) or its transposed image.  ``g`` (R x k) is updated
+    (``from_zero``: from zeros), ``f`` (C x k) gathered: z_r = sum over the stored entries of row r of val f[idx], then ``inner_iters``
+    Gauss-Seidel sweeps of g_r with S = f^T f + l2 I and z = z_r - l1.  Returns ``(g_new, gram, dot, violation)`` with
+    gram = g_new^T g_new, dot = sum_r <z_r, g_new_r> and one violation per sweep (``want_gram=False``: ``(g_new, violation)``).
+    ``want_info``: also ``{"kernel": k_nmf_cd_sweep ran}``."""
+    rows, g, f, k = _nmf_sweep_operands(sx, g, f, transposed)
+    spec = _nmf_spec(1, 0.0, l1, l2)
+    go = np.zeros((rows, k))
+    gram = np.zeros((k, k)) if want_gram else None
+    dot = np.zeros(1) if want_gram else None
+    viol = np.zeros(max(int(inner_iters), 0))
+    info = (C.c_int64 * 1)()
+    ctx = sx.ctx
+    ctx.check(ctx.lib.petal_nmf_cd_sweep_csr(ctx._h, sx._handle(), int(bool(transposed)), k, _dp(g), _dp(f), C.byref(spec), int(inner_iters),
+                                             int(bool(from_zero)), _dp(go), _dp(gram), _dp(dot), _dp(viol), info))
+    return _with_info((go, gram, float(dot[0]), viol) if want_gram else (go, viol), info, want_info)
+
+
 def nmf_cd_hupdate(a, b, h, l1_h=0.0, l2_h=0.0, ctx: Optional["Context"] = None, want_info: bool = False):
     """Test aid (``petal_nmf_cd_hupdate``, include/petal_hip_nmf_cd.h): the H side of a coordinate-descent ``Nmf`` iteration by itself,
     in float64: one sweep of every row of h^T with S = b + l2_h I and z = a[:, j] - l1_h.  ``a``, ``h`` (k x d), ``b`` (k x k).
@@ -1038,21 +1065,31 @@ class Nmf(_HandleOwner):
     coordinate-descent solver (its default, ``shuffle=False``) on dense input under the Frobenius loss: one fused pass k_nmf_cd_pass
     per iteration, scikit-learn's stopping rule after every iteration when ``tol > 0`` (``tol = 0``: exactly ``max_iter``
     iterations), ``transform`` from W = 0 with exactly ``max_iter`` sweeps.  ``"cd"`` with the Kullback-Leibler loss or with sparse
-    input is ``InvalidInput``.  ``solver`` is readable."""
+    input is ``InvalidInput``.  ``solver`` is readable.
+
+    ``sparse_path`` chooses what ``solver="cd"`` does with sparse input (include/petal_hip_nmf_cd_sparse.h).  ``"refuse"``, the
+    default, is the refusal above; ``"sweep"`` lets ``fit``, ``fit_transform`` and ``transform`` take a ``CsrMatrix`` or an object with
+    ``.data / .indices / .indptr / .shape``: two fused gather sweeps k_nmf_cd_sweep per iteration, X never densified, at most 64
+    components on the kernel (more, or ``nmf_fallback``, densify), and ``kernel_path`` says whether the sweep ran (1) or the call
+    densified (0).  The default stays ``"refuse"`` only because existing callers are pinned to its messages; it may move in a later
+    change.  Under ``solver="mu"`` the keyword is read and changes nothing."""
 
     _destroy, _no_handle = "petal_nmf_destroy", "the model has not been fitted (or its ctx was closed)"
 
     def __init__(self, n_components: int, max_iter: int = 200, tol: float = 1e-4, init: str = "random", seed: int = 0,
                  alpha_W: float = 0.0, alpha_H="same", l1_ratio: float = 0.0, ctx: Optional[Context] = None, beta_loss="frobenius",
-                 dense_path: str = "compress", solver: str = "mu"):
+                 dense_path: str = "compress", solver: str = "mu", sparse_path: str = "refuse"):
         if init not in ("random", "custom"):
             raise InvalidInput(f"unknown init {init!r} (random or custom)")
         if dense_path not in ("compress", "fused"):
             raise InvalidInput(f"unknown dense_path {dense_path!r} (compress or fused)")
         if not isinstance(solver, str) or solver not in ("mu", "cd"):
             raise InvalidInput(f"unknown solver {solver!r} (mu or cd)")
+        if not isinstance(sparse_path, str) or sparse_path not in ("refuse", "sweep"):
+            raise InvalidInput(f"unknown sparse_path {sparse_path!r} (refuse or sweep)")
         self.dense_path = dense_path
         self.solver = solver
+        self.sparse_path = sparse_path
         self._loss = _beta_loss_code(beta_loss)
         if solver == "cd" and self._loss != NMF_LOSS_FROBENIUS:
             raise InvalidInput("solver='cd' does not take the kullback-leibler loss (the coordinate-descent solver is for the frobenius loss)")
@@ -1102,7 +1139,9 @@ class Nmf(_HandleOwner):
                 mo = describe(w, keep)
             h, path = C.c_void_p(), C.c_int64(0)
             args = (_ref(mw), _ref(mh), C.c_int64(self.seed & ((1 << 64) - 1)), C.byref(h), _ref(mo), C.byref(path))
-            if self._loss == NMF_LOSS_FROBENIUS:
+            if self.solver == "cd":   # sparse_path="sweep" (include/petal_hip_nmf_cd_sparse.h)
+                ctx.check(ctx.lib.petal_nmf_fit_csr_solver(ctx._h, sx._handle(), self._k, C.byref(spec), NMF_SOLVER_CD, *args))
+            elif self._loss == NMF_LOSS_FROBENIUS:
                 ctx.check(ctx.lib.petal_nmf_fit_csr(ctx._h, sx._handle(), self._k, C.byref(spec), *args))
             else:
                 ctx.check(ctx.lib.petal_nmf_fit_csr_loss(ctx._h, sx._handle(), self._k, C.byref(spec), self._loss, *args))
@@ -1111,7 +1150,7 @@ class Nmf(_HandleOwner):
             return w
 
     def _inner_fit(self, x, W, H, want_w: bool):
-        if self.solver == "cd" and _is_sparse(x):
+        if self.solver == "cd" and self.sparse_path != "sweep" and _is_sparse(x):
             raise InvalidInput("solver='cd' does not take sparse (CSR) input in this version")
         if _is_sparse(x):
             return self._inner_fit_sparse(x, W, H, want_w)
@@ -1158,7 +1197,8 @@ class Nmf(_HandleOwner):
                 w = np.empty((sx.shape[0], self._k), dtype=_np_dtype(sx._dt))
                 mo = describe(w, keep)
                 path = C.c_int64(0)
-                ctx.check(ctx.lib.petal_nmf_transform_csr(ctx._h, self._handle(), sx._handle(), C.byref(mo), C.byref(path)))
+                entry = ctx.lib.petal_nmf_transform_csr_solver if self.sparse_path == "sweep" else ctx.lib.petal_nmf_transform_csr
+                ctx.check(entry(ctx._h, self._handle(), sx._handle(), C.byref(mo), C.byref(path)))
                 self.kernel_path = int(path.value)
                 return w
         keep = []

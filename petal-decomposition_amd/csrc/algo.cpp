@@ -3838,27 +3838,42 @@ void nmf_sweep_into(petal_ctx& c, const petal_csr& x, int t, int64_t k, int64_t 
     if (!ran) device_error("Nmf: the device-op layer refused the sparse sweep");
 }
 void nmf_kl_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, const NmfScan& sx, int64_t* kernel_path);
-}  // namespace
 
-petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
-                       int64_t seed, const petal_matrix* w_out, int64_t* kernel_path) {
+// The front of a sparse fit (multiplicative updates, coordinate descent): the checks and the one look at the stored values.
+NmfScan nmf_csr_fit_checks(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                           const petal_matrix* w_out, int64_t* kernel_path) {
     csr_usable(c, x);
     if (kernel_path) *kernel_path = 0;
-    const int dt = x.dtype;
-    const int64_t n = x.rows, d = x.cols;
-    nmf_check_fit(n, d, dt, k, spec, w0, h0, w_out);
+    nmf_check_fit(x.rows, x.cols, x.dtype, k, spec, w0, h0, w_out);
     const NmfScan sx = nmf_csr_scan(c, x);
     nmf_reject(sx);
-    if (!nmf_csr_sweeps(c, x, k)) {
-        NmfCsrDense dense;
-        nmf_csr_densify(c, x, dense);
-        return nmf_fit(c, dense.m, k, spec, w0, h0, seed, w_out);
-    }
-    const Timer timer = start_unchecked_fit(c);
-    const int64_t ks = nmf_csr_padded_k(k), kk1 = ks * ks + 1;
-    DBuf W(c.dev, sizeof(double) * size_t(n) * ks), Ht(c.dev, sizeof(double) * size_t(d) * ks);
-    DBuf B(c.dev, sizeof(double) * size_t(kk1)), HHt(c.dev, sizeof(double) * size_t(kk1));   // each: the Gram matrix, then the sweep's dot
-    std::vector<double> hht;
+    return sx;
+}
+// The state of a fit on the sweeps: W (n x ks) and H^T (d x ks) at their start in the sweep's padding, and the two Gram blocks B and HHt
+// -- each the Gram matrix, then the sweep's dot, then `tail` doubles of the solver's own -- with Gram(W0) already in B.
+struct NmfCsrFit {
+    Timer timer;
+    NmfScan sx;
+    int dt = 0;
+    int64_t n = 0, d = 0, k = 0, ks = 0;
+    DBuf W, Ht, B, HHt;
+    std::vector<double> hht, hb, hh2;   // host copies: H^T, and the two Gram blocks as read_loss last read them
+};
+NmfCsrFit nmf_csr_fit_start(petal_ctx& c, const petal_csr& x, int64_t k, const NmfScan& sx, const petal_matrix* w0, const petal_matrix* h0,
+                            int64_t seed, int64_t tail) {
+    NmfCsrFit f;
+    f.timer = start_unchecked_fit(c);
+    f.sx = sx;
+    const int dt = f.dt = x.dtype;
+    const int64_t n = f.n = x.rows, d = f.d = x.cols;
+    f.k = k;
+    const int64_t ks = f.ks = nmf_csr_padded_k(k), kk1 = ks * ks + 1 + tail;
+    f.W = DBuf(c.dev, sizeof(double) * size_t(n) * ks);
+    f.Ht = DBuf(c.dev, sizeof(double) * size_t(d) * ks);
+    f.B = DBuf(c.dev, sizeof(double) * size_t(kk1));
+    f.HHt = DBuf(c.dev, sizeof(double) * size_t(kk1));
+    DBuf &W = f.W, &Ht = f.Ht;
+    std::vector<double>& hht = f.hht;
     if (w0) {
         const DevMat W0 = ingest(c, *w0), H0 = ingest(c, *h0);
         nmf_reject(nmf_scan(c, W0));
@@ -3877,18 +3892,74 @@ petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpe
         dev_h2d(c.dev, W.p, hw.data(), W.bytes);
     }
     dev_h2d(c.dev, Ht.p, hht.data(), Ht.bytes);
-    // the loss = sqrt(max(0, |X|^2 - 2 <W^T X, H> + <W^T W, H H^T>)) from the two Gram blocks as the sweeps left them
-    std::vector<double> hb(static_cast<size_t>(kk1)), hh2(static_cast<size_t>(kk1));
-    const auto read_loss = [&]() {
-        dev_d2h(c.dev, hb.data(), B.p, B.bytes);
-        dev_d2h(c.dev, hh2.data(), HHt.p, HHt.bytes);
-        dev_sync(c.dev);
-        double dots[2] = {hh2[size_t(ks * ks)], 0.0};
-        for (int64_t i = 0; i < ks * ks; ++i) dots[1] += hb[i] * hh2[i];
-        return nmf_loss(sx.sumsq, dots);
-    };
-    // the loss at the start: Gram(W0), and a column sweep that leaves H alone
-    if (!op_nmf_gram(c.dev, W.f64(), n, ks, nullptr, B.f64())) device_error("Nmf: the device-op layer refused the Gram product");
+    f.hb.resize(static_cast<size_t>(kk1));
+    f.hh2.resize(static_cast<size_t>(kk1));
+    // the loss at the start: Gram(W0), and (the caller's) column sweep that leaves H alone
+    if (!op_nmf_gram(c.dev, W.f64(), n, ks, nullptr, f.B.f64())) device_error("Nmf: the device-op layer refused the Gram product");
+    return f;
+}
+// the loss = sqrt(max(0, |X|^2 - 2 <W^T X, H> + <W^T W, H H^T>)) from the two Gram blocks as the sweeps left them
+double nmf_csr_read_loss(petal_ctx& c, NmfCsrFit& f) {
+    const int64_t ks = f.ks;
+    dev_d2h(c.dev, f.hb.data(), f.B.p, f.B.bytes);
+    dev_d2h(c.dev, f.hh2.data(), f.HHt.p, f.HHt.bytes);
+    dev_sync(c.dev);
+    double dots[2] = {f.hh2[size_t(ks * ks)], 0.0};
+    for (int64_t i = 0; i < ks * ks; ++i) dots[1] += f.hb[i] * f.hh2[i];
+    return nmf_loss(f.sx.sumsq, dots);
+}
+// W out, and the handle: an ordinary petal_nmf with H as kp x dp and H H^T as kp x kp in the dense entries' padding (H H^T: the host
+// copy of the last nmf_csr_read_loss)
+petal_nmf* nmf_csr_fit_finish(petal_ctx& c, NmfCsrFit& f, const NmfSpec& spec, double err_init, const NmfStop& stop, int64_t solver,
+                              const petal_matrix* w_out) {
+    const int64_t n = f.n, d = f.d, k = f.k, ks = f.ks;
+    if (w_out) nmf_emit_w(c, f.dt, f.W.f64(), n, k, ks, *w_out);
+    const int64_t kp = nmf_padded_k(k), dp = round_up(d, 16);
+    dev_d2h(c.dev, f.hht.data(), f.Ht.p, f.Ht.bytes);
+    dev_sync(c.dev);
+    const std::vector<double> hd = nmf_transpose_out(f.hht, d, ks, k, kp, dp), hg = nmf_padded(f.hh2.data(), ks, k, k, kp, kp);
+    DBuf H(c.dev, sizeof(double) * hd.size()), G(c.dev, sizeof(double) * hg.size());
+    dev_h2d(c.dev, H.p, hd.data(), H.bytes);
+    dev_h2d(c.dev, G.p, hg.data(), G.bytes);
+    return nmf_finish_handle(c, f.timer, {f.dt, n, d, dp, k, kp}, spec, err_init, stop, true, NMF_LOSS_FROBENIUS, solver, H, G);
+}
+// H^T (d x ks) and H H^T (ks x ks) on the device in the sweep's padding, from a model's own blocks (a dense fit's among them)
+void nmf_csr_model_operands(petal_ctx& c, const petal_nmf& h, int64_t ks, DBuf& Ht, DBuf& S) {
+    std::vector<double> hd(size_t(h.kp) * h.dp), hg(size_t(h.kp) * h.kp), hht;
+    dev_d2h(c.dev, hd.data(), h.h, sizeof(double) * hd.size());
+    dev_d2h(c.dev, hg.data(), h.hht, sizeof(double) * hg.size());
+    dev_sync(c.dev);
+    nmf_transpose_in(hd.data(), h.dp, h.k, h.d, ks, hht);
+    const std::vector<double> hs = nmf_padded(hg.data(), h.kp, h.k, h.k, ks, ks);
+    Ht = DBuf(c.dev, sizeof(double) * hht.size());
+    S = DBuf(c.dev, sizeof(double) * hs.size());
+    dev_h2d(c.dev, Ht.p, hht.data(), Ht.bytes);
+    dev_h2d(c.dev, S.p, hs.data(), S.bytes);
+    dev_sync(c.dev);   // (the host arrays end with this call)
+}
+// the checks of a sparse transform behind the handles' own, and the one look at the stored values
+NmfScan nmf_csr_transform_checks(petal_ctx& c, const petal_nmf& h, const petal_csr& x, const petal_matrix& w_out) {
+    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
+    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    check_output(w_out, h.dtype, x.rows, h.k);
+    const NmfScan sx = nmf_csr_scan(c, x);
+    nmf_reject(sx);
+    return sx;
+}
+}  // namespace
+
+petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                       int64_t seed, const petal_matrix* w_out, int64_t* kernel_path) {
+    const NmfScan sx = nmf_csr_fit_checks(c, x, k, spec, w0, h0, w_out, kernel_path);
+    if (!nmf_csr_sweeps(c, x, k)) {
+        NmfCsrDense dense;
+        nmf_csr_densify(c, x, dense);
+        return nmf_fit(c, dense.m, k, spec, w0, h0, seed, w_out);
+    }
+    NmfCsrFit f = nmf_csr_fit_start(c, x, k, sx, w0, h0, seed, 0);
+    const int64_t ks = f.ks;
+    DBuf &W = f.W, &Ht = f.Ht, &B = f.B, &HHt = f.HHt;
+    const auto read_loss = [&]() { return nmf_csr_read_loss(c, f); };
     nmf_sweep_into(c, x, 1, k, ks, W.f64(), Ht.f64(), B.f64(), false, 0.0, spec.l1_h, spec.l2_h, 0, HHt.f64());
     const double err_init = read_loss();
     const NmfStop stop = nmf_mu_iterate(
@@ -3898,16 +3969,7 @@ petal_nmf* nmf_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpe
             nmf_sweep_into(c, x, 1, k, ks, W.f64(), Ht.f64(), B.f64(), false, 0.0, spec.l1_h, spec.l2_h, 1, HHt.f64());
         },
         read_loss);
-    if (w_out) nmf_emit_w(c, dt, W.f64(), n, k, ks, *w_out);
-    // the handle is an ordinary petal_nmf: H as kp x dp and H H^T as kp x kp in the dense entries' padding
-    const int64_t kp = nmf_padded_k(k), dp = round_up(d, 16);
-    dev_d2h(c.dev, hht.data(), Ht.p, Ht.bytes);
-    dev_sync(c.dev);
-    const std::vector<double> hd = nmf_transpose_out(hht, d, ks, k, kp, dp), hg = nmf_padded(hh2.data(), ks, k, k, kp, kp);
-    DBuf H(c.dev, sizeof(double) * hd.size()), G(c.dev, sizeof(double) * hg.size());
-    dev_h2d(c.dev, H.p, hd.data(), H.bytes);
-    dev_h2d(c.dev, G.p, hg.data(), G.bytes);
-    petal_nmf* h = nmf_finish_handle(c, timer, {dt, n, d, dp, k, kp}, spec, err_init, stop, true, NMF_LOSS_FROBENIUS, 0, H, G);
+    petal_nmf* h = nmf_csr_fit_finish(c, f, spec, err_init, stop, 0, w_out);
     if (kernel_path) *kernel_path = 1;
     return h;
 }
@@ -3917,12 +3979,8 @@ void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const pet
     csr_usable(c, x);
     if (kernel_path) *kernel_path = 0;
     if (h.solver != 0) invalid_input("Nmf: the coordinate-descent solver does not take CSR input in this version");
-    if (x.dtype != h.dtype) invalid_input("input dtype differs from the Nmf model's dtype");
-    if (x.cols != h.d) invalid_input("# of columns should be " + std::to_string(h.d));
+    const NmfScan sx = nmf_csr_transform_checks(c, h, x, w_out);
     const int64_t m = x.rows;
-    check_output(w_out, h.dtype, m, h.k);
-    const NmfScan sx = nmf_csr_scan(c, x);
-    nmf_reject(sx);
     if (h.loss != 0) {   // a Kullback-Leibler model (include/petal_hip_nmf_kl.h): its own sweep, never densified
         nmf_kl_transform_csr(c, h, x, w_out, sx, kernel_path);
         return;
@@ -3935,17 +3993,9 @@ void nmf_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const pet
     }
     if (m == 0) return;
     const Timer timer = start_unchecked_fit(c);
-    // H^T and H H^T in the sweep's padding, from the model's own blocks (a dense fit's among them)
     const int64_t ks = nmf_csr_padded_k(h.k);
-    std::vector<double> hd(size_t(h.kp) * h.dp), hg(size_t(h.kp) * h.kp), hht;
-    dev_d2h(c.dev, hd.data(), h.h, sizeof(double) * hd.size());
-    dev_d2h(c.dev, hg.data(), h.hht, sizeof(double) * hg.size());
-    dev_sync(c.dev);
-    nmf_transpose_in(hd.data(), h.dp, h.k, h.d, ks, hht);
-    const std::vector<double> hs = nmf_padded(hg.data(), h.kp, h.k, h.k, ks, ks);
-    DBuf Ht(c.dev, sizeof(double) * hht.size()), S(c.dev, sizeof(double) * hs.size()), W(c.dev, sizeof(double) * size_t(m) * ks);
-    dev_h2d(c.dev, Ht.p, hht.data(), Ht.bytes);
-    dev_h2d(c.dev, S.p, hs.data(), S.bytes);
+    DBuf Ht, S, W(c.dev, sizeof(double) * size_t(m) * ks);
+    nmf_csr_model_operands(c, h, ks, Ht, S);
     const double w0 = std::sqrt(sx.sum / (double(m) * double(h.d)) / double(h.k));
     nmf_sweep_into(c, x, 0, h.k, ks, Ht.f64(), W.f64(), S.f64(), true, w0, h.l1_w, h.l2_w, h.max_iter, nullptr);
     h.last_kernel = 1;
@@ -4673,6 +4723,28 @@ bool nmf_cd_hupdate_into(petal_ctx& c, int64_t k, int64_t kp, int64_t dp, const 
     return false;
 }
 
+// The stopping loop of coordinate descent (the solver's own rule, not nmf_mu_iterate's): step() is an iteration that leaves the W sweep's
+// violation at vw and the H sweep's at vh (DEVICE, one double each); with tol > 0 the two are read back after EVERY iteration and the fit
+// stops where violation_init == 0 or violation / violation_init <= tol.  tol = 0 queues the whole fit without a host round trip.
+// Returns n_iter.
+template <class Step>
+int64_t nmf_cd_iterate(petal_ctx& c, const NmfSpec& spec, Step step, const double* vw, const double* vh) {
+    double viol_init = 0.0;
+    for (int64_t it = 1; it <= spec.max_iter; ++it) {
+        step();
+        if (spec.tol > 0) {
+            double hv[2];
+            dev_d2h(c.dev, hv, vw, sizeof(double));
+            dev_d2h(c.dev, hv + 1, vh, sizeof(double));
+            dev_sync(c.dev);
+            const double v = hv[0] + hv[1];
+            if (it == 1) viol_init = v;
+            if (viol_init == 0.0 || v / viol_init <= spec.tol) return it;
+        }
+    }
+    return spec.max_iter;
+}
+
 petal_nmf* nmf_cd_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
                       int64_t seed, const petal_matrix* w_out) {
     NmfDenseFit f = nmf_dense_fit_front(c, x, k, spec, w0, h0, seed, w_out);
@@ -4685,21 +4757,13 @@ petal_nmf* nmf_cd_fit(petal_ctx& c, const petal_matrix& x, int64_t k, const NmfS
     // the loss at the start: A = W^T X and B = W^T W from a pass that leaves W alone
     bool kernel = nmf_cd_pass_into(c, f.X, H, HHt.f64(), k, kp, W, false, spec.l1_w, spec.l2_w, 0, A.f64(), B.f64(), nullptr);
     const double err_init = nmf_initial_loss_frobenius(c, f, A, B);
-    // (the stopping rule is this solver's own: the projected-gradient violation after every iteration, not nmf_mu_iterate's)
-    int64_t n_iter = spec.max_iter;
-    double viol_init = 0.0;
-    for (int64_t it = 1; it <= spec.max_iter; ++it) {
-        kernel = nmf_cd_pass_into(c, f.X, H, HHt.f64(), k, kp, W, false, spec.l1_w, spec.l2_w, 1, A.f64(), B.f64(), viol.f64()) && kernel;
-        nmf_cd_hupdate_into(c, k, kp, dp, A.f64(), B.f64(), H, HHt.f64(), spec.l1_h, spec.l2_h, dots.f64(), viol.f64() + 1);
-        if (spec.tol > 0) {   // (tol = 0 queues the whole fit without a host round trip)
-            double hv[2];
-            dev_d2h(c.dev, hv, viol.p, sizeof(hv));
-            dev_sync(c.dev);
-            const double v = hv[0] + hv[1];
-            if (it == 1) viol_init = v;
-            if (viol_init == 0.0 || v / viol_init <= spec.tol) { n_iter = it; break; }
-        }
-    }
+    const int64_t n_iter = nmf_cd_iterate(
+        c, spec,
+        [&]() {
+            kernel = nmf_cd_pass_into(c, f.X, H, HHt.f64(), k, kp, W, false, spec.l1_w, spec.l2_w, 1, A.f64(), B.f64(), viol.f64()) && kernel;
+            nmf_cd_hupdate_into(c, k, kp, dp, A.f64(), B.f64(), H, HHt.f64(), spec.l1_h, spec.l2_h, dots.f64(), viol.f64() + 1);
+        },
+        viol.f64(), viol.f64() + 1);
     double hd[2];
     dev_d2h(c.dev, hd, dots.p, sizeof(hd));
     dev_sync(c.dev);
@@ -4788,6 +4852,166 @@ void nmf_cd_hupdate(petal_ctx& c, int64_t k, int64_t d, const double* a, const d
     for (int64_t i = 0; i < k; ++i) std::copy(hh.begin() + i * dp, hh.begin() + i * dp + d, h_out + i * d);
     if (violation_out) *violation_out = hv[2];
     if (info1) info1[0] = ran ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Nmf by coordinate descent on sparse CSR data (include/petal_hip_nmf_cd_sparse.h; DESIGN.md sections 4 and 7).  An iteration is two
+// cd sweeps (op_nmf_cd_sweep_csr): over the rows of X with G = W, F = H^T, S = H H^T + l2_w I, and over the rows of the transposed image
+// with G = H^T, F = the new W, S = W^T W + l2_h I; each leaves its G, G^T G, sum_r <z_r, g_r> and its violation on the device.  The
+// front, the loss and the handle are nmf_fit_csr's, the stopping loop is nmf_cd_fit's.  A handle that is not resident (a device-op layer
+// without the kernels), PETAL_OPT_NMF_FALLBACK and k > 64 densify and run nmf_cd_fit / nmf_cd_transform: bit for bit their results.
+__attribute__((weak)) bool op_nmf_cd_sweep_csr(Dev*, int, const CsrImage&, int64_t, int64_t, const double*, double*, const double*, bool, double,
+                                               double, int64_t, double*) {
+    return false;
+}
+namespace {
+// one cd sweep under the hot-kernel tag; a layer that refuses here has refused nothing else
+void nmf_cd_sweep_into(petal_ctx& c, const petal_csr& x, int t, int64_t k, int64_t ks, const double* F, double* G, const double* S, bool from_zero,
+                       double l1, double l2, int64_t inner, double* gram_dot_viol) {
+    dev_set_tag(c.dev, TAG_POW);
+    const bool ran = op_nmf_cd_sweep_csr(c.dev, x.dtype, x.dev[t], k, ks, F, G, S, from_zero, l1, l2, inner, gram_dot_viol);
+    dev_set_tag(c.dev, TAG_NONE);
+    if (!ran) device_error("Nmf: the device-op layer refused the sparse coordinate-descent sweep");
+}
+
+petal_nmf* nmf_cd_fit_csr(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, const petal_matrix* w0, const petal_matrix* h0,
+                          int64_t seed, const petal_matrix* w_out, int64_t* kernel_path) {
+    const NmfScan sx = nmf_csr_fit_checks(c, x, k, spec, w0, h0, w_out, kernel_path);
+    if (!nmf_csr_sweeps(c, x, k)) {
+        NmfCsrDense dense;
+        nmf_csr_densify(c, x, dense);
+        return nmf_cd_fit(c, dense.m, k, spec, w0, h0, seed, w_out);
+    }
+    NmfCsrFit f = nmf_csr_fit_start(c, x, k, sx, w0, h0, seed, 1);   // (one more double behind each Gram block: the sweep's violation)
+    const int64_t ks = f.ks, kk1 = ks * ks + 1;
+    double *W = f.W.f64(), *Ht = f.Ht.f64(), *B = f.B.f64(), *HHt = f.HHt.f64();
+    // the loss at the start: Gram(W0) is in B; a column sweep that leaves H alone
+    nmf_cd_sweep_into(c, x, 1, k, ks, W, Ht, B, false, spec.l1_h, spec.l2_h, 0, HHt);
+    const double err_init = nmf_csr_read_loss(c, f);
+    const int64_t n_iter = nmf_cd_iterate(
+        c, spec,
+        [&]() {
+            nmf_cd_sweep_into(c, x, 0, k, ks, Ht, W, HHt, false, spec.l1_w, spec.l2_w, 1, B);
+            nmf_cd_sweep_into(c, x, 1, k, ks, W, Ht, B, false, spec.l1_h, spec.l2_h, 1, HHt);
+        },
+        B + kk1, HHt + kk1);
+    const double err = nmf_csr_read_loss(c, f);
+    petal_nmf* h = nmf_csr_fit_finish(c, f, spec, err_init, {n_iter, err}, 1, w_out);
+    if (kernel_path) *kernel_path = 1;
+    return h;
+}
+
+// transform of a coordinate-descent model on sparse rows: ONE row sweep from zero with inner = max_iter, no tolerance stop
+void nmf_cd_transform_csr(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, int64_t* kernel_path) {
+    const NmfScan sx = nmf_csr_transform_checks(c, h, x, w_out);
+    (void)sx;
+    const int64_t m = x.rows;
+    if (!nmf_csr_sweeps(c, x, h.k)) {
+        NmfCsrDense dense;
+        nmf_csr_densify(c, x, dense);
+        nmf_transform(c, h, dense.m, w_out);   // (a solver-1 handle: nmf_cd_transform)
+        return;
+    }
+    if (m == 0) return;
+    const Timer timer = start_unchecked_fit(c);
+    const int64_t ks = nmf_csr_padded_k(h.k);
+    DBuf Ht, S, W(c.dev, sizeof(double) * size_t(m) * ks);
+    nmf_csr_model_operands(c, h, ks, Ht, S);
+    nmf_cd_sweep_into(c, x, 0, h.k, ks, Ht.f64(), W.f64(), S.f64(), true, h.l1_w, h.l2_w, h.max_iter, nullptr);
+    h.last_kernel = 1;
+    nmf_emit_w(c, h.dtype, W.f64(), m, h.k, ks, w_out);
+    finish_stats(c, timer);
+    if (kernel_path) *kernel_path = 1;
+}
+}  // namespace
+
+petal_nmf* nmf_fit_csr_solver(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, int64_t solver, const petal_matrix* w0,
+                              const petal_matrix* h0, int64_t seed, const petal_matrix* w_out, int64_t* kernel_path) {
+    if (solver == 0) return nmf_fit_csr(c, x, k, spec, w0, h0, seed, w_out, kernel_path);
+    if (solver != 1) invalid_input("Nmf: unknown solver " + std::to_string(solver) + " (0: multiplicative updates, 1: coordinate descent)");
+    return nmf_cd_fit_csr(c, x, k, spec, w0, h0, seed, w_out, kernel_path);
+}
+
+void nmf_transform_csr_solver(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, int64_t* kernel_path) {
+    if (h.solver == 0) { nmf_transform_csr(c, h, x, w_out, kernel_path); return; }
+    nmf_usable(c, h);
+    csr_usable(c, x);
+    if (kernel_path) *kernel_path = 0;
+    nmf_cd_transform_csr(c, h, x, w_out, kernel_path);
+}
+
+void nmf_cd_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k, const double* g_in, const double* f, const NmfSpec& spec,
+                      int64_t inner, bool from_zero, double* g_out, double* gram_out, double* dot_out, double* violation_out, int64_t* info1) {
+    csr_usable(c, x);
+    if (info1) info1[0] = 0;
+    if (k < 1) invalid_input("nmf_cd_sweep: the number of components should be at least 1");
+    if (inner < 0) invalid_input("negative parameter");
+    if (inner > 1024) invalid_input("nmf_cd_sweep: at most 1024 sweeps");
+    nmf_check_penalties(spec.l1_w, spec.l2_w);
+    if (dot_out && !gram_out) invalid_input("dot_out comes with gram_out or not at all");
+    const int t = transposed ? 1 : 0, dt = x.dtype;
+    const int64_t R = transposed ? x.cols : x.rows, C = transposed ? x.rows : x.cols;
+    const double l1 = spec.l1_w, l2 = spec.l2_w;
+    const bool zero = from_zero && inner > 0;
+    if (!x.resident) {   // the plain host loop of a layer without the kernel: the statement in position order
+        const petal_csr::Image& im = x.host[t];
+        std::vector<double> S(size_t(k) * k, 0.0), z(static_cast<size_t>(k)), zl(static_cast<size_t>(k)), g(static_cast<size_t>(k));
+        for (int64_t r = 0; r < C; ++r)
+            for (int64_t i = 0; i < k; ++i)
+                for (int64_t j = 0; j < k; ++j) S[size_t(i) * k + j] += f[r * k + i] * f[r * k + j];
+        for (int64_t i = 0; i < k; ++i) S[size_t(i) * k + i] += l2;
+        if (gram_out) std::fill(gram_out, gram_out + k * k, 0.0);
+        if (violation_out) std::fill(violation_out, violation_out + inner, 0.0);
+        double dot = 0.0;
+        for (int64_t r = 0; r < R; ++r) {
+            std::fill(z.begin(), z.end(), 0.0);
+            for (int64_t q = im.ptr[r]; q < im.ptr[r + 1]; ++q) {
+                const double v = get_elem(im.val.data(), dt, q);
+                for (int64_t j = 0; j < k; ++j) z[j] += v * f[int64_t(im.idx[q]) * k + j];
+            }
+            for (int64_t j = 0; j < k; ++j) zl[j] = z[j] - l1;
+            if (zero) std::fill(g.begin(), g.end(), 0.0);
+            else std::copy(g_in + r * k, g_in + (r + 1) * k, g.begin());
+            for (int64_t it = 0; it < inner; ++it) {
+                const double v = nmf_cd_sweep_host(g.data(), 1, zl.data(), S.data(), k);
+                if (violation_out) violation_out[it] += v;
+            }
+            std::copy(g.begin(), g.end(), g_out + r * k);
+            if (gram_out) {
+                for (int64_t i = 0; i < k; ++i)
+                    for (int64_t j = 0; j < k; ++j) gram_out[i * k + j] += g[i] * g[j];
+                for (int64_t j = 0; j < k; ++j) dot += z[j] * g[j];
+            }
+        }
+        if (dot_out) *dot_out = dot;
+        return;
+    }
+    if (k > 64) invalid_input("nmf_cd_sweep: the sparse kernel takes at most 64 components");
+    if (R == 0) {
+        if (gram_out) std::fill(gram_out, gram_out + k * k, 0.0);
+        if (dot_out) *dot_out = 0.0;
+        if (violation_out) std::fill(violation_out, violation_out + inner, 0.0);
+        return;
+    }
+    const int64_t ks = nmf_csr_padded_k(k), kk1 = ks * ks + 1;
+    const bool want = gram_out || violation_out;
+    const std::vector<double> hf = nmf_padded(f, k, C, k, std::max<int64_t>(C, 1), ks);
+    const NmfGuarded Gd = nmf_guard_stage(c, g_in, R, k, ks, 0, 1);   // G with one guard row behind it
+    DBuf F(c.dev, sizeof(double) * hf.size()), S(c.dev, sizeof(double) * size_t(kk1)), GD;
+    if (want) GD = DBuf(c.dev, sizeof(double) * size_t(kk1 + inner));
+    dev_h2d(c.dev, F.p, hf.data(), F.bytes);
+    if (C == 0) dev_memset(c.dev, S.p, 0, S.bytes);
+    else if (!op_nmf_gram(c.dev, F.f64(), C, ks, nullptr, S.f64())) device_error("Nmf: the device-op layer refused the Gram product");
+    nmf_cd_sweep_into(c, x, t, k, ks, F.f64(), Gd.block(), S.f64(), zero, l1, l2, inner, want ? GD.f64() : nullptr);
+    std::vector<double> hgd(want ? size_t(kk1 + inner) : 0);
+    nmf_guard_collect(c, Gd, g_out, "nmf_cd_sweep wrote outside the R x k block", [&] {
+        if (want) dev_d2h(c.dev, hgd.data(), GD.p, GD.bytes);
+    });
+    if (gram_out)
+        for (int64_t i = 0; i < k; ++i) std::copy(hgd.begin() + i * ks, hgd.begin() + i * ks + k, gram_out + i * k);
+    if (dot_out) *dot_out = hgd[size_t(ks * ks)];
+    if (violation_out) std::copy(hgd.begin() + kk1, hgd.begin() + kk1 + inner, violation_out);
+    if (info1) info1[0] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 #include "../../include/petal_hip_nmf_kl.h"
 #include "../../include/petal_hip_nmf_kl_dense.h"
 #include "../../include/petal_hip_nmf_cd.h"
+#include "../../include/petal_hip_nmf_cd_sparse.h"
 #include "../../include/petal_hip_probe.h"
 
 using namespace petal;
@@ -575,6 +576,39 @@ int petal_nmf_cd_hupdate(petal_ctx* ctx, int64_t k, int64_t d, const double* a, 
         need(spec, "spec");
         need(h_out, "h_out");
         nmf_cd_hupdate(*ctx, k, d, a, b, h_in, nmf_spec(*spec), h_out, violation_out, info1);
+    });
+}
+
+// ---- include/petal_hip_nmf_cd_sparse.h: the coordinate-descent solver on a resident CSR matrix ------------------------------------------
+int petal_nmf_fit_csr_solver(petal_ctx* ctx, const petal_csr* x, int64_t k, const petal_nmf_spec* spec, int64_t solver, const petal_matrix* w0,
+                             const petal_matrix* h0, int64_t seed, petal_nmf** out, const petal_matrix* w_out, int64_t* kernel_path) {
+    if (out) *out = nullptr;
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(spec, "spec");
+        need(out, "out");
+        *out = nmf_fit_csr_solver(*ctx, *x, k, nmf_spec(*spec), solver, w0, h0, seed, w_out, kernel_path);
+    });
+}
+int petal_nmf_transform_csr_solver(petal_ctx* ctx, petal_nmf* h, const petal_csr* x, const petal_matrix* w_out, int64_t* kernel_path) {
+    return guarded(ctx, [&] {
+        need(h, "handle");
+        need(x, "x");
+        need(w_out, "w_out");
+        nmf_transform_csr_solver(*ctx, *h, *x, *w_out, kernel_path);
+    });
+}
+int petal_nmf_cd_sweep_csr(petal_ctx* ctx, const petal_csr* x, int transposed, int64_t k, const double* g_in, const double* f,
+                           const petal_nmf_spec* spec, int64_t inner_iters, int from_zero, double* g_out, double* gram_out, double* dot_out,
+                           double* violation_out, int64_t* info1) {
+    return guarded(ctx, [&] {
+        need(x, "x");
+        need(g_in, "g_in");
+        need(f, "f");
+        need(spec, "spec");
+        need(g_out, "g_out");
+        nmf_cd_sweep_csr(*ctx, *x, transposed != 0, k, g_in, f, nmf_spec(*spec), inner_iters, from_zero != 0, g_out, gram_out, dot_out,
+                         violation_out, info1);
     });
 }
 

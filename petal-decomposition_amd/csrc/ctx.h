@@ -226,6 +226,12 @@ void nmf_cd_pass(petal_ctx& c, const petal_matrix& x, int64_t k, const double* w
                  bool from_zero, double* w_out, double* a_out, double* b_out, double* violation_out, int64_t* info1);
 void nmf_cd_hupdate(petal_ctx& c, int64_t k, int64_t d, const double* a, const double* b, const double* h_in, const NmfSpec& spec, double* h_out,
                     double* violation_out, int64_t* info1);
+// include/petal_hip_nmf_cd_sparse.h: the coordinate-descent solver on a sparse matrix
+petal_nmf* nmf_fit_csr_solver(petal_ctx& c, const petal_csr& x, int64_t k, const NmfSpec& spec, int64_t solver, const petal_matrix* w0,
+                              const petal_matrix* h0, int64_t seed, const petal_matrix* w_out, int64_t* kernel_path);
+void nmf_transform_csr_solver(petal_ctx& c, petal_nmf& h, const petal_csr& x, const petal_matrix& w_out, int64_t* kernel_path);
+void nmf_cd_sweep_csr(petal_ctx& c, const petal_csr& x, bool transposed, int64_t k, const double* g_in, const double* f, const NmfSpec& spec,
+                      int64_t inner, bool from_zero, double* g_out, double* gram_out, double* dot_out, double* violation_out, int64_t* info1);
 // include/petal_hip_ipca.h: IncrementalPca
 petal_ipca* ipca_create(petal_ctx& c, int64_t d, int32_t dtype, bool centering);
 void ipca_destroy(petal_ipca* h);

@@ -600,4 +600,5 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 #include "kernels/k_nmf_kl.inc"    // Nmf with the Kullback-Leibler loss on sparse CSR data: the fused gather sweep (k_nmf_kl_sweep, k_nmf_kl_split), colsum(G) and the loss's term (k_nmf_kl_colsum), k_nmf_kl_vsum
 #include "kernels/k_nmf_kl_dense.inc"   // Nmf with the Kullback-Leibler loss on dense data: the fused pass (k_nmf_kl_pass), the H rule and the row sums of H (k_nmf_kl_hrule, k_nmf_kl_rowsum)
 #include "kernels/k_nmf_cd.inc"   // Nmf by coordinate descent: the fused pass with the Gauss-Seidel sweep (k_nmf_cd_pass), the sweep on the rows of H^T (k_nmf_cd_hrule), k_nmf_cd_violsum
+#include "kernels/k_nmf_cd_csr.inc"   // Nmf by coordinate descent on sparse CSR data: four rows per wave (k_nmf_cd_sweep, k_nmf_cd_sweep_split), G^T G with the dot and the violations (k_nmf_cd_gram)
 }  // namespace petal

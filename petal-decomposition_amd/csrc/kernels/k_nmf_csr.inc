@@ -69,22 +69,16 @@ __device__ __forceinline__ void nmf_load_s(double* sS, const double* __restrict_
     __syncthreads();
 }
 
-template <class T, int G, bool CONST>
-__global__ __launch_bounds__(256) void k_nmf_sweep(const CsrItem* __restrict__ items, int64_t n_items, const int32_t* __restrict__ idx,
-                                                   const T* __restrict__ val, const double* __restrict__ F, double* __restrict__ Gm,
-                                                   const double* __restrict__ S, int k, double gconst, double l1, double l2, int inner,
-                                                   double* __restrict__ part, double* __restrict__ dots) {
+// The gather of one work item by one whole wave (k_spmm's): lanes 0 .. G - 1 return z[c0], z[c0 + 1] of the item, c0 = 2 (lane % G), in
+// acc0 / acc1 (the other lanes: partial sums).  Shared with k_nmf_cd_csr.inc.
+template <class T, int G>
+__device__ __forceinline__ void nmf_csr_gather(const CsrItem& item, const int32_t* __restrict__ idx, const T* __restrict__ val,
+                                               const double* __restrict__ F, int lane, double& acc0, double& acc1) {
     constexpr int KP = 2 * G, NSUB = 64 / G;
-    __shared__ double sS[KP * KP];
-    __shared__ double sZG[4][2 * KP];
-    nmf_load_s<KP>(sS, S, inner);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane / G;
-    const int64_t it = int64_t(blockIdx.x) * 4 + wave;
-    if (it >= n_items) return;                        // (whole waves leave: the shuffles below see all 64 lanes)
-    const CsrItem item = items[it];
-    const int c0 = (lane % G) * 2;
-    const double* Fc = F + c0;
-    double acc0 = 0.0, acc1 = 0.0;
+    const int sub = lane / G;
+    const double* Fc = F + (lane % G) * 2;
+    acc0 = 0.0;
+    acc1 = 0.0;
     for (int base = 0; base < item.count; base += 64) {
         const int cnt = min(64, item.count - base);
         int my_i = 0;
@@ -113,6 +107,24 @@ __global__ __launch_bounds__(256) void k_nmf_sweep(const CsrItem* __restrict__ i
         acc0 += __shfl_down(acc0, off);
         acc1 += __shfl_down(acc1, off);
     }
+}
+
+template <class T, int G, bool CONST>
+__global__ __launch_bounds__(256) void k_nmf_sweep(const CsrItem* __restrict__ items, int64_t n_items, const int32_t* __restrict__ idx,
+                                                   const T* __restrict__ val, const double* __restrict__ F, double* __restrict__ Gm,
+                                                   const double* __restrict__ S, int k, double gconst, double l1, double l2, int inner,
+                                                   double* __restrict__ part, double* __restrict__ dots) {
+    constexpr int KP = 2 * G;
+    __shared__ double sS[KP * KP];
+    __shared__ double sZG[4][2 * KP];
+    nmf_load_s<KP>(sS, S, inner);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane / G;
+    const int64_t it = int64_t(blockIdx.x) * 4 + wave;
+    if (it >= n_items) return;                        // (whole waves leave: the shuffles below see all 64 lanes)
+    const CsrItem item = items[it];
+    const int c0 = (lane % G) * 2;
+    double acc0, acc1;
+    nmf_csr_gather<T, G>(item, idx, val, F, lane, acc0, acc1);
     if (item.slot >= 0) {                             // part of a split row: the partial sums, for k_nmf_sweep_split
         if (sub == 0) *reinterpret_cast<double2*>(part + int64_t(item.slot) * KP + c0) = make_double2(acc0, acc1);
         return;
@@ -145,12 +157,11 @@ __global__ __launch_bounds__(256) void k_nmf_sweep_split(const CsrSplit* __restr
 // slab[b] = { sum over the rows of workgroup b's tiles of g_r^T g_r (KP x KP), sum of dots[r] }.  Thread (ty, tx) = (tid / 16, tid % 16)
 // holds the KP / 16 x KP / 16 block at (ty, tx) KP / 16 of the product; a tile is 16 rows of G in LDS.
 constexpr int NMF_GRAM_MAX_WG = 256;
+// the slab of this workgroup into out (KP^2 + 1 doubles); tile: 16 x (KP + 1) doubles of LDS, red: 256.  Shared with k_nmf_cd_csr.inc.
 template <int KP>
-__global__ __launch_bounds__(256) void k_nmf_gram(const double* __restrict__ Gm, int64_t rows, const double* __restrict__ dots,
-                                                  double* __restrict__ slab) {
+__device__ __forceinline__ void nmf_gram_slab(const double* __restrict__ Gm, int64_t rows, const double* __restrict__ dots, double* __restrict__ out,
+                                              double (*tile)[KP + 1], double* red) {
     constexpr int B = KP / 16;
-    __shared__ double tile[16][KP + 1];
-    __shared__ double red[256];
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
     const int64_t ntiles = (rows + 15) / 16;
     double acc[B][B];
@@ -179,7 +190,6 @@ __global__ __launch_bounds__(256) void k_nmf_gram(const double* __restrict__ Gm,
                 for (int b = 0; b < B; ++b) acc[a][b] = fma(av[a], bv[b], acc[a][b]);
         }
     }
-    double* out = slab + int64_t(blockIdx.x) * (KP * KP + 1);
 #pragma unroll
     for (int a = 0; a < B; ++a)
 #pragma unroll
@@ -191,6 +201,13 @@ __global__ __launch_bounds__(256) void k_nmf_gram(const double* __restrict__ Gm,
         for (int i = 0; i < 16; ++i) s += red[i];
         out[KP * KP] = s;
     }
+}
+template <int KP>
+__global__ __launch_bounds__(256) void k_nmf_gram(const double* __restrict__ Gm, int64_t rows, const double* __restrict__ dots,
+                                                  double* __restrict__ slab) {
+    __shared__ double tile[16][KP + 1];
+    __shared__ double red[256];
+    nmf_gram_slab<KP>(Gm, rows, dots, slab + int64_t(blockIdx.x) * (KP * KP + 1), tile, red);
 }
 
 template <class T>

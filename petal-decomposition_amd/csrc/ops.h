@@ -304,6 +304,15 @@ bool op_nmf_cd_pass(Dev*, int dtype, const void* X, int64_t n, int64_t dp, int64
 // HHt = H H^T, dots2 (DEVICE) = { <A, H>, <B, HHt> } and viol1 (DEVICE) = the sweep's violation.  false, NOTHING done: kp not 16, 32 or 64.
 bool op_nmf_cd_hupdate(Dev*, int64_t k, int64_t kp, int64_t dp, const double* A, const double* B, double* H, double* HHt, double l1, double l2,
                        double* dots2, double* viol1);
+// Nmf by coordinate descent on sparse CSR data (include/petal_hip_nmf_cd_sparse.h).  One cd sweep of an image: G (R x kp, DEVICE fp64,
+// in place; from_zero: starts as zeros, needs inner >= 1), F (C x kp), S (kp x kp; the kernel adds l2 on its first k diagonal entries),
+// all ZERO in the padding, kp = nmf_csr_padded_k(k):
+//     z_r = op_nmf_sweep_csr's;  inner Gauss-Seidel sweeps of g_r over its coordinates with z = z_r - l1  (inner == 0: G is left alone)
+// gram_dot_viol (nullable, DEVICE, kp kp + 1 + inner doubles; then inner <= 1024): G^T G with the G just written, sum_r <z_r, g_r> (the raw
+// z_r), then the violation of every sweep.  No atomics; every order is fixed by the image's items and kp.  false, NOTHING done: k > 64 or
+// the layer lacks the op.
+bool op_nmf_cd_sweep_csr(Dev*, int dtype, const CsrImage& img, int64_t k, int64_t kp, const double* F, double* G, const double* S, bool from_zero,
+                         double l1, double l2, int64_t inner, double* gram_dot_viol);
 // out (img.rows x cols in dtype, ldo; DEVICE) = the dense image: zeros, then every stored entry added in position order.
 bool op_csr_densify(Dev*, int dtype, const CsrImage& img, void* out, int64_t cols, int64_t ldo);
 // One re-basing step of the power iteration: G (L x L, ldg) = R^T R, P_out (K x M fp64, ldpo) = A R^-1 (A: K x M, lda; columns

@@ -10,6 +10,7 @@ mod ffi_nmf_sparse;
 mod ffi_nmf_kl;
 mod ffi_nmf_kl_dense;
 mod ffi_nmf_cd;
+mod ffi_nmf_cd_sparse;
 mod ffi_score;
 mod ffi_segments;
 mod ffi_sparse;
@@ -24,7 +25,7 @@ pub use ffi_kpca::PETAL_OPT_KPCA_FALLBACK;
 pub use ffi_nmf::PETAL_OPT_NMF_FALLBACK;
 pub use ffi_wide::{PETAL_OPT_PCA_DUAL, PETAL_OPT_PCA_DUAL_FALLBACK};
 pub use kpca::{Kernel, KernelPca, KernelPcaInfo};
-pub use nmf::{Nmf, NmfDensePath, NmfInfo, NmfLoss, NmfParams, NmfSolver};
+pub use nmf::{Nmf, NmfDensePath, NmfInfo, NmfLoss, NmfParams, NmfSolver, NmfSparsePath};
 pub use pca::{CsrMatrix, IncrementalPca, Pca, PcaBuilder, PcaRoute, RandomizedPca, RandomizedPcaBuilder, SegmentedPca};
 
 use ndarray::{ArrayBase, Data, Ix2};

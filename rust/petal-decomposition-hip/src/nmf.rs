@@ -4,6 +4,7 @@
 use crate::ffi_nmf::{self, PetalNmf, PetalNmfSpec};
 use crate::ffi_nmf_kl;
 use crate::ffi_nmf_cd;
+use crate::ffi_nmf_cd_sparse;
 use crate::ffi_nmf_kl_dense;
 use crate::ffi_nmf_sparse;
 use crate::pca::CsrMatrix;
@@ -58,6 +59,17 @@ impl NmfSolver {
     }
 }
 
+/// What `fit_csr` / `transform_csr` do under `NmfSolver::CoordinateDescent` (include/petal_hip_nmf_cd_sparse.h; source only, unverified
+/// like the rest of this crate).  `Refuse` (the default) returns InvalidInput; `Sweep` sends the matrix to the coordinate-descent sweeps
+/// `k_nmf_cd_sweep` (at most 64 components on the kernel, otherwise the library densifies).  Under `MultiplicativeUpdate` it changes
+/// nothing.
+#[derive(Debug, Clone, Copy, PartialEq, Eq, Default)]
+pub enum NmfSparsePath {
+    #[default]
+    Refuse,
+    Sweep,
+}
+
 /// The parameters of a fit; `alpha_h: None` means the same as `alpha_w` (scikit-learn's "same").  `loss` is read by `fit_csr` and its
 /// siblings; `transform_csr` follows the loss the model was fitted with.
 #[derive(Debug, Clone, Copy, PartialEq)]
@@ -71,10 +83,11 @@ pub struct NmfParams {
     pub loss: NmfLoss,
     pub dense_path: NmfDensePath,
     pub solver: NmfSolver,
+    pub sparse_path: NmfSparsePath,
 }
 
 impl Default for NmfParams {
-    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0, loss: NmfLoss::Frobenius, dense_path: NmfDensePath::Compress, solver: NmfSolver::MultiplicativeUpdate } }
+    fn default() -> Self { Self { max_iter: 200, tol: 1e-4, seed: 0, alpha_w: 0.0, alpha_h: None, l1_ratio: 0.0, loss: NmfLoss::Frobenius, dense_path: NmfDensePath::Compress, solver: NmfSolver::MultiplicativeUpdate, sparse_path: NmfSparsePath::Refuse } }
 }
 
 /// { n, d, k, iterations run, k_nmf_pass ran in the fit, k_nmf_pass ran in the last transform (-1 before the first) }
@@ -177,7 +190,12 @@ impl<A: HipScalar> Nmf<A> {
         let mut w = Array2::<A>::default((input.nrows(), self.k));
         let wv = view(&w.view_mut());
         let mut path = 0i64;
-        with_ctx(|ctx| unsafe { ffi_nmf_sparse::petal_nmf_transform_csr(ctx, raw, input.raw(), &wv, &mut path) }, || ())?;
+        if self.params.sparse_path == NmfSparsePath::Sweep {
+            // dispatches on the model's solver; a multiplicative model: petal_nmf_transform_csr's bytes
+            with_ctx(|ctx| unsafe { ffi_nmf_cd_sparse::petal_nmf_transform_csr_solver(ctx, raw, input.raw(), &wv, &mut path) }, || ())?;
+        } else {
+            with_ctx(|ctx| unsafe { ffi_nmf_sparse::petal_nmf_transform_csr(ctx, raw, input.raw(), &wv, &mut path) }, || ())?;
+        }
         self.kernel_path = path;
         Ok(w)
     }
@@ -198,6 +216,14 @@ impl<A: HipScalar> Nmf<A> {
     }
     fn inner_fit_csr(&mut self, input: &CsrMatrix<A>, init: Option<(&Array2<A>, &Array2<A>)>, w: Option<&mut Array2<A>>)
         -> Result<(), DecompositionError> {
+        let solver = self.params.solver;
+        let cd = solver == NmfSolver::CoordinateDescent;
+        if cd && self.params.sparse_path != NmfSparsePath::Sweep {
+            return Err(DecompositionError::InvalidInput("Nmf: the coordinate-descent solver does not take a CsrMatrix in this version".into()));
+        }
+        if cd && self.params.loss != NmfLoss::Frobenius {
+            return Err(DecompositionError::InvalidInput("Nmf: the coordinate-descent solver does not take the kullback-leibler loss".into()));
+        }
         let wv = w.map(|w| view(&w.view_mut()));
         let iv = init.map(|(w0, h0)| (view(w0), view(h0)));
         let spec = self.spec(input.nrows() as f64, input.ncols() as f64);
@@ -208,7 +234,9 @@ impl<A: HipScalar> Nmf<A> {
             |ctx| unsafe {
                 let (w0, h0) = (iv.as_ref().map_or(std::ptr::null(), |m| &m.0 as *const _), iv.as_ref().map_or(std::ptr::null(), |m| &m.1 as *const _));
                 let wo = wv.as_ref().map_or(std::ptr::null(), |m| m as *const _);
-                if loss == NmfLoss::Frobenius {
+                if cd {
+                    ffi_nmf_cd_sparse::petal_nmf_fit_csr_solver(ctx, input.raw(), k, &spec, solver.code(), w0, h0, seed, &mut raw, wo, &mut path)
+                } else if loss == NmfLoss::Frobenius {
                     ffi_nmf_sparse::petal_nmf_fit_csr(ctx, input.raw(), k, &spec, w0, h0, seed, &mut raw, wo, &mut path)
                 } else {
                     ffi_nmf_kl::petal_nmf_fit_csr_loss(ctx, input.raw(), k, &spec, loss.code(), w0, h0, seed, &mut raw, wo, &mut path)
